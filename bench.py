@@ -10,11 +10,18 @@ region starts, output = float NHWC [0,1] images in HBM (PNG encode / dataset dec
         bench.py --gpus N --steps K --warmup W
 
 Images are independent: each rank transfers its own batches, no collective on the data path ("scaling": "weak").
-Rank 0 prints ONE JSON line.  At N = 1 (the driver's default run) that line also carries `side_workloads`: short legs of
-BASELINE.json's other configs -- configs[1] `train`, configs[3] `sd_train`, configs[4] `sd_img2img` in fp16 and bf16, and (round 6) the
-reference's own precision for the two pixel configs: `img2img_fp16` (configs[2]) and `train_fp16` (configs[1]) -- each run as a
-child process AFTER the headline's fields are final, each with its own value / ms_per_step / roofline / cpu_baseline
-(`--no-side-workloads` skips them; `--workload X` runs one of them as the main workload).
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, the
+outputs (`--dump-outputs DIR`: what the last timed step computed, as DIR/<name>.npy) and the line.
+
+`--full` adds everything else the benchmark measures: the roofline of the dominant kernel, the clock / power samples (`box`), the
+CPU baseline, the batch sweep, at N > 1 the start-up all-reduce self-test and the data-parallel step statistics, and at N = 1
+`side_workloads`: short legs of BASELINE.json's other configs -- configs[1] `train`, configs[3] `sd_train`, configs[4] `sd_img2img`
+in fp16 and bf16, and (round 6) the reference's own precision for the two pixel configs: `img2img_fp16` (configs[2]) and
+`train_fp16` (configs[1]) -- each run as a child process AFTER the headline's fields are final, each with its own value /
+ms_per_step / roofline / cpu_baseline (`--no-side-workloads` etc. still skip single parts of `--full`; `--workload X` runs one of
+them as the main workload).
+
+    python bench.py --full
 """
 import argparse
 import json
@@ -35,6 +42,23 @@ FWD_GFLOP_PER_IMAGE = 376.0
 FWD_ACT_MB_PER_IMAGE_BF16 = 691.8
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
 PEAK_MFMA_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "f32": 157.3}   # dense peaks, MI355X_MICROARCH.md (F16 = BF16 rate)
+
+
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all arrays together
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array of ``arrays`` (name -> tensor).  An array larger than its share of
+    DUMP_MAX_BYTES is written as a fixed sample of its flattened elements (indices drawn with seed 0, so the same on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (DUMP_MAX_BYTES - 4096 * len(arrays)) // len(arrays) // 4
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.float().cpu().numpy())
 
 
 def synth_batch(B, size, seed):
@@ -332,6 +356,8 @@ def main_train(args, P, world, rank, dev, dist):
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed, ranks = reduce_elapsed(dist, elapsed, dev, B * args.steps)
+    if args.dump_outputs and rank == 0:       # the last timed step's loss and the parameters it left (before anything below steps again)
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": tr.opt.flat})
     if dist is None and not args.no_box:      # clock / power under this workload, through a repeat of the steps AFTER the timed region
         def _again():
             for _ in range(min(args.steps, 3)):
@@ -380,7 +406,7 @@ def main_train(args, P, world, rank, dev, dist):
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_train(args.model, size, state_dict, args.cpu_baseline_seconds)
         res["gpu_over_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
-    if dist is not None:
+    if dist is not None and args.full:
         res["data_parallel"] = comm_step_stats(args, dev, dist, tr, step)
     if rank == 0:
         res["diagnostic_env"] = diagnostic_env()
@@ -624,7 +650,8 @@ def comm_step_stats(args, dev, dist, tr, step, steps=3):
     return out
 
 
-def _timed_steps(args, dev, dist, step, units_per_rank):
+def _timed_steps(args, dev, dist, step, units_per_rank, outputs):
+    """Warm-up, the timed steps, MAX over ranks; ``outputs(last step's result)`` -> the arrays --dump-outputs writes."""
     def barrier():
         torch.cuda.synchronize(dev)
         if dist is not None:
@@ -640,6 +667,8 @@ def _timed_steps(args, dev, dist, step, units_per_rank):
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed, ranks = reduce_elapsed(dist, elapsed, dev, units_per_rank)
+    if args.dump_outputs and (dist is None or dist.get_rank() == 0):      # before anything below steps again
+        dump_outputs(args.dump_outputs, outputs(out))
     if dist is None and not getattr(args, "no_box", False):
         # the clock / power the card holds under THIS workload (round 6: the latent-diffusion legs run at the board's power cap too --
         # LAB_r6 section 1), sampled through a repeat of up to 3 steps after the timed region, never inside it
@@ -788,7 +817,7 @@ def main_sd_img2img(args, P, world, rank, dev, dist):
         def step():
             host_out.copy_(graph.run(x, labels, 1 - labels, generator=gen).images, non_blocking=True)
             return host_out
-    elapsed, out, ranks = _timed_steps(args, dev, dist, step, B * args.steps)
+    elapsed, out, ranks = _timed_steps(args, dev, dist, step, B * args.steps, lambda out: {"images": out})
     assert out.shape == (B, size, size, 3) and torch.isfinite(out).all()
     value = world * B * args.steps / elapsed
     res = {"metric": "SD img2img images/sec (VAE encode + 50-step DDIM invert + 50-step denoise + VAE decode, 512x512)",
@@ -837,7 +866,7 @@ def main_sd_train(args, P, world, rank, dev, dist):
         count[0] += 1
         return tr.step(noisy, ts, clean, noise, labels, unconditional=(count[0] % 10 == 0))
 
-    elapsed, loss, ranks = _timed_steps(args, dev, dist, step, B * args.steps)
+    elapsed, loss, ranks = _timed_steps(args, dev, dist, step, B * args.steps, lambda loss: {"loss": loss, "params": tr.opt.flat})
     assert torch.isfinite(loss).all()
     value = world * B * args.steps / elapsed
     res = {"metric": f"SD-2.1 UNet fine-tuning samples/sec (64x64 latents = 512x512, {args.dtype})", "value": round(value, 3), "unit": "samples/s",
@@ -859,7 +888,7 @@ def main_sd_train(args, P, world, rank, dev, dist):
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_sd_train(P, size)
         res["gpu_over_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
-    if dist is not None:
+    if dist is not None and args.full:
         res["data_parallel"] = comm_step_stats(args, dev, dist, tr, step)
     if rank == 0:
         res["diagnostic_env"] = diagnostic_env()
@@ -896,7 +925,7 @@ SIDE_WORKLOADS = (
 
 
 def run_side_workloads(budget_s, only=None, headline_cpu_baseline=None):
-    """Each leg = `python bench.py --workload X ... --no-side-workloads` as a child; its JSON line is attached (trimmed of the
+    """Each leg = `python bench.py --workload X ... --full --no-side-workloads` as a child; its JSON line is attached (trimmed of the
     long prose fields).  A leg that does not fit what is left of the budget is skipped and the line says so."""
     import subprocess
     out, t_all = {}, time.time()
@@ -907,7 +936,7 @@ def run_side_workloads(budget_s, only=None, headline_cpu_baseline=None):
         if left < expect_s * 0.6:
             out[name] = {"skipped": f"side budget: {left:.0f} s left of {budget_s:.0f}, this leg needs ~{expect_s} s"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-side-workloads"] + argv
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-side-workloads"] + argv
         t0 = time.time()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=max(left, expect_s) + 60)
@@ -995,7 +1024,15 @@ def main():
                          "fp16 and bf16) that are attached to the line as `side_workloads`")
     ap.add_argument("--side-budget-s", type=float, default=330.0, help="wall-clock bound for all side workloads together")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=30.0, help="bound of the cpu_baseline sample (img2img, train)")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline figure too: roofline, box, CPU baseline, "
+                    "batch sweep, side workloads (N = 1), all-reduce self-test and data-parallel step statistics (N > 1); "
+                    "the --no-* switches above skip single parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, 64 MB at most: a fixed sample of a larger array)")
     args = ap.parse_args()
+    if not args.full:          # a plain run: set-up, warm-up, the timed steps, the outputs, the line
+        args.no_cpu_baseline = args.no_roofline = args.no_box = True
+        args.sweep = args.side_workloads = False
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher (the reference's `accelerate launch --multi_gpu --num_processes N`,
@@ -1032,7 +1069,7 @@ def main():
             sys.exit(3)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
-    if dist is not None and not os.environ.get("PD_BENCH_NO_SELFTEST"):
+    if dist is not None and args.full and not os.environ.get("PD_BENCH_NO_SELFTEST"):
         try:
             _SELFTEST["result"] = comm_selftest(dist, dev)
         except Exception as e:                                                     # noqa: BLE001 -- the self-test never takes the run down
@@ -1093,6 +1130,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed, ranks = reduce_elapsed(dist, elapsed, dev, B * args.steps)
+    if args.dump_outputs and rank == 0:       # the last timed batch's images (before anything below replays the trajectory again)
+        dump_outputs(args.dump_outputs, {"images": host_out})
     box = None
     if rank == 0 and world == 1 and not args.no_box:          # (one-GPU runs only: at N > 1 rank 0 would keep the other ranks waiting at the next barrier)
         def _again():

@@ -34,20 +34,20 @@ head)
   python3 scripts/collect_mfma_busy.py $R "$(ls /tmp/pmc_busy/*/*_counter_collection.csv | head -1)" > $OUT/mfma_busy.txt
   cp profiles/${R}_mfma_busy.json $OUT/
   # the default line last: it quotes the two PMC summaries just written (same kernel sources by construction)
-  python3 bench.py > $OUT/${R}_bench_default.json 2>$OUT/bench_default.err
+  python3 bench.py --full > $OUT/${R}_bench_default.json 2>$OUT/bench_default.err
   cut -c1-200 $OUT/${R}_bench_default.json
-  python3 bench.py --model small_denoiser_config --batch 16 --steps 1 --warmup 1 --no-cpu-baseline --no-sweep --no-side-workloads > $OUT/${R}_bench_small_denoiser_b16.json 2>/dev/null
+  python3 bench.py --full --model small_denoiser_config --batch 16 --steps 1 --warmup 1 --no-cpu-baseline --no-sweep --no-side-workloads > $OUT/${R}_bench_small_denoiser_b16.json 2>/dev/null
   ;;
 train)
-  python3 bench.py --workload train --steps 10 --warmup 2 > $OUT/${R}_bench_train.json 2>/dev/null
+  python3 bench.py --full --workload train --steps 10 --warmup 2 > $OUT/${R}_bench_train.json 2>/dev/null
   cut -c1-200 $OUT/${R}_bench_train.json
   stats train_b112 ${R}_train_bench_under_rocprof_b112.log 40 10 --workload train --steps 30 --warmup 10 --no-cpu-baseline --no-roofline --no-sweep --no-side-workloads
   mv $OUT/${R}_train_b112_kernel_stats.csv $OUT/${R}_train_kernel_stats_b112.csv
   ;;
 sd)
-  python3 bench.py --workload sd_img2img --steps 2 > $OUT/${R}_bench_sd_img2img.json 2>/dev/null
+  python3 bench.py --full --workload sd_img2img --steps 2 > $OUT/${R}_bench_sd_img2img.json 2>/dev/null
   cut -c1-200 $OUT/${R}_bench_sd_img2img.json
-  python3 bench.py --workload sd_train --steps 10 --warmup 2 > $OUT/${R}_bench_sd_train.json 2>/dev/null
+  python3 bench.py --full --workload sd_train --steps 10 --warmup 2 > $OUT/${R}_bench_sd_train.json 2>/dev/null
   cut -c1-200 $OUT/${R}_bench_sd_train.json
   # (rocprofv3 7.2 crashes once more than ~40 000 graph launches are queued between two host syncs: ONE 36 000-node replay per sync)
   stats sd_img2img_b32 ${R}_sd_img2img_bench_under_rocprof_b32.log 2 1 --workload sd_img2img --steps 1 --warmup 1 --no-roofline --no-cpu-baseline --no-side-workloads

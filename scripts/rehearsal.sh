@@ -17,7 +17,7 @@ for n in 2 4; do
     esac
     port=$((port + 1))
     timeout -k 10 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --steps 2 --warmup 1 \
-      --no-cpu-baseline --no-roofline --no-sweep $extra > $OUT/r6_rehearsal_${wl}_n$n.json 2> $OUT/r6_rehearsal_${wl}_n$n.err
+      --full --no-cpu-baseline --no-roofline --no-sweep $extra > $OUT/r6_rehearsal_${wl}_n$n.json 2> $OUT/r6_rehearsal_${wl}_n$n.err
     rc=$?
     echo "$wl n=$n rc=$rc $(python -c "import json,sys; ls=[l for l in open('$OUT/r6_rehearsal_${wl}_n$n.json') if l.startswith('{')]; j=json.loads(ls[-1]); print(len(ls),'line(s): value',j['value'],j['unit'],'n_gpus',j['n_gpus'],'world',j.get('rccl_world_size'),'ranks',len(j.get('per_rank_units_per_s',[])), 'selftest exact', j.get('allreduce_selftest',{}).get('exact'))" 2>&1 | tail -1)"
     [ $rc = 0 ] || tail -5 $OUT/r6_rehearsal_${wl}_n$n.err

@@ -50,3 +50,20 @@ def test_a_rank_whose_process_group_init_fails_exits_non_zero_with_one_line():
     lines = [ln for ln in r.stderr.splitlines() if ln.startswith("bench.py:")]
     assert r.returncode == 3 and len(lines) == 1 and "rank 1/2" in lines[0] and "init_process_group failed" in lines[0], r.stderr[-1500:]
     assert "Traceback" not in r.stderr
+
+
+def test_dump_outputs_writes_float32_and_samples_large_arrays_the_same_way_every_time(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 20)
+    small = torch.rand(2, 8, 8, 3)
+    big = torch.arange(1 << 20, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"images": small, "params": big, "loss": torch.tensor(0.5)})
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("images", "params", "loss")}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["images"], small.numpy()) and float(a["loss"]) == 0.5
+    assert sum(v.nbytes for v in a.values()) <= 1 << 20 and 0 < a["params"].size < big.numel()
+    assert np.all(np.diff(a["params"]) >= 0) and np.all(np.isin(a["params"], big.numpy()))     # a sorted sample of the elements
+    assert np.array_equal(a["params"], np.load(tmp_path / "b" / "params.npy"))

@@ -21,7 +21,7 @@ def _run(extra, **env_extra):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-roofline", "--no-sweep"] + extra
+           "--full", "--no-cpu-baseline", "--no-roofline", "--no-sweep"] + extra
     env = dict(os.environ, PD_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
     env.pop("PYTEST_CURRENT_TEST", None)
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
