@@ -255,11 +255,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
   constexpr int QPB = WPB * QPW;                     // queries per workgroup
   using E = Elem<T>;
   using Ops = AttnOps<T>;
-#ifdef PD_ABL_NOPIPE
-  constexpr bool PIPE = false;
-#else
   constexpr bool PIPE = sizeof(T) == 2 && QB == 1;   // 16 more registers: the other forms would lose a wave per SIMD
-#endif
   constexpr int KROW = Ops::KROW;
   constexpr int VBYTES = 10 * Ops::VT_PITCH;         // rows 0..7 = V^T, row 8 = 1.0, row 9 = 0
   __shared__ __attribute__((aligned(16))) unsigned char klds[2][KT * KROW + 16];   // + one 16-B slot: k-slots 8..15 of every row
@@ -290,11 +286,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
   // so s' = S - m leaves the matrix pipe ready for exp2.
   // m is only raised when some s' exceeds RESCALE_THR (p <= 2^THR otherwise).  A tile needs the exact row max only if
   // some score COULD exceed m + THR: s = q.k <= |q| * max|k| (Cauchy-Schwarz), checked once per 256-key tile.
-#ifdef PD_ABL_THR
-  constexpr float RESCALE_THR = 1e30f;   // ablation only: never take the exact-max path after the first tile
-#else
   constexpr float RESCALE_THR = Ops::RESCALE_THR;
-#endif
   int query[QB];
   typename Ops::QF qf[QB];
   f32x16 o[QB], negm[QB];
@@ -337,15 +329,11 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
   auto commit = [&](int b2, int k0) {
     if (!mine(k0 / KT)) return;
     E::store(klds[b2] + st * KROW, stk);
-#ifndef PD_ABL_NONORM
     float n2 = row16_max(Ops::k_norm2(stk));
     n2 = fmaxf(n2, __shfl_xor(n2, 16));
     n2 = fmaxf(n2, __shfl_xor(n2, 32));
     if ((st & 63) == 0) knmax[b2][st >> 6] = sqrtf(n2) * 1.00002f;
-#endif
-#ifndef PD_ABL_NOVT
     Ops::store_vt(vlds[b2], Ops::vpos(st), stv);
-#endif
   };
 
   issue(0);
@@ -363,11 +351,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
     bool need = false;
 #pragma unroll
     for (int j = 0; j < QB; ++j) need = need || first[j] || (qn[j] * kn8 - m[j] > RESCALE_THR);
-#ifdef PD_ABL_NOCHECK   // ablation only
-    if (full_tile && (k0 > 0 || !__builtin_amdgcn_ballot_w64(need))) {
-#else
     if (full_tile && !__builtin_amdgcn_ballot_w64(need)) {
-#endif
       // check-free body: per sub-tile one K and one V^T fragment read feed all QB query blocks
       if constexpr (PIPE) {
         // software-pipelined: the QK^T MFMA of sub-tile i+1 (and the LDS reads of its successors) are issued before the
@@ -450,15 +434,11 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
         }
       }
     }
-#ifndef PD_ABL_NOSTAGE   // ablation only: the first two tiles' LDS content is reused, no staging, no barrier
     if (k0 + KT < N) {
       commit(cur ^ 1, k0 + KT);              // tile k0+KT: loaded during the previous tile's math
       if (k0 + 2 * KT < N) issue(k0 + 2 * KT);
     }
-#ifndef PD_ABL_NOBARRIER
     __syncthreads();
-#endif
-#endif
   }
 
 #pragma unroll
@@ -487,14 +467,12 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
 //     16-lane group supplies key row q, d columns 4p..4p+3 (p < 2) or a block of ones (p >= 2: A rows 8..15 -> l),
 //   * the score bound uses the producer's max |k|^2 per (batch, head) instead of per-tile norms: once
 //     |q| * max|k| - m <= THR every later tile runs the check-free body with no LDS read in front of it.
-#ifndef PD_ATTN_DMA_KT
-#define PD_ATTN_DMA_KT 256
-#endif
+constexpr int ATTN_DMA_KT = 256;                                                      // keys per LDS tile (one barrier per tile)
 template <typename T>
 __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
   static_assert(sizeof(T) == 2, "16-bit element types");
   using Ops = AttnOps<T>;
-  constexpr int KT = PD_ATTN_DMA_KT;                                                  // keys per LDS tile (one barrier per tile)
+  constexpr int KT = ATTN_DMA_KT;
   constexpr int KROW = 16, TILE = KT * KROW;
   // one LDS array, addressed by byte offsets (plain integers keep every access a ds_* instruction):
   //   K tiles [2][TILE] | V tiles [2][TILE] | constants [ONES] ([1 0 0 0 | 0 0 0 0] per 16 bytes, see voff below) | k-slots 8..15 of every K row (16 B)
@@ -1053,11 +1031,9 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(const pd_attn_bwd_a
   // next one's vector work before it is read back -- the LDS round trip is hidden without a second pair of images.
   auto step = [&](int cur, int sub, f32x16& dq) {
     // LLVM's MFMA / exp interleaving strategy over the step (same box: none 1.228 ms per configs[1] layer incl. the reduce, (1) 1.300, (2) 1.215,
-    // (3) 1.210; -DPD_ATTN_BWD_IGLP=n builds another)
-#ifndef PD_ATTN_BWD_IGLP
-#define PD_ATTN_BWD_IGLP 3
-#endif
-    __builtin_amdgcn_iglp_opt(PD_ATTN_BWD_IGLP);
+    // (3) 1.210)
+    constexpr int ATTN_BWD_IGLP = 3;
+    __builtin_amdgcn_iglp_opt(ATTN_BWD_IGLP);
     const typename Ops::KF qa = Ops::load_k(lds + Q_OFF + cur * ROWS + ka0 + sub * kst);
     const typename Ops::KF doa = Ops::load_k(lds + DO_OFF + cur * ROWS + ka0 + sub * kst);
     const typename Ops::VF dotf = Ops::load_v(lds + DOT_OFF + cur * VTB + vrow_off, sub * 32);
@@ -1174,18 +1150,12 @@ extern "C" int pd_attn_d8(const pd_attn_args* a, void* stream) {
   PD_CHECK(a != nullptr, PD_ERR_ARG, "pd_attn_d8: null args");
   PD_CHECK(a->B > 0 && a->heads > 0 && a->N > 0, PD_ERR_SHAPE, "pd_attn_d8: bad shape");
   PD_CHECK(a->q && a->k && a->v && a->out, PD_ERR_ARG, "pd_attn_d8: null pointer");
-  // Query blocks per wave.  QB = 2 (K / V^T fragments shared by two independent chains, 2 waves/SIMD) measured 3 % slower
-  // than QB = 1 (4 waves/SIMD) at N = 4096: the tile time is pinned by the exp + MFMA issue mix (scripts/micro/), not by
-  // LDS traffic or occupancy.  Kept selectable for future shapes.
-#ifdef PD_ATTN_QB2
-  const int qbw = (a->N >= 2048) ? 2 : 1;
-#else
-  const int qbw = 1;
-#endif
+  // One query block per wave (attn_kernel QB = 1).  QB = 2 (K / V^T fragments shared by two independent chains, 2 waves/SIMD) measured 3 %
+  // slower at N = 4096: the tile time is pinned by the exp + MFMA issue mix (scripts/micro/), not by LDS traffic or occupancy.
   // 8-wave workgroups (256 queries share each staged tile) once there are enough query blocks to fill the chip with them
   const bool wpb4_only = diag_env("PD_ATTN_WPB4", 0) != 0;      // diagnostic: same-box A/B
-  const bool wide = !wpb4_only && qbw == 1 && a->N >= 1024 && (long long)(a->N / 256) * a->heads * a->B >= 1024;
-  const int qpb = wide ? 256 : 128 * qbw;
+  const bool wide = !wpb4_only && a->N >= 1024 && (long long)(a->N / 256) * a->heads * a->B >= 1024;
+  const int qpb = wide ? 256 : 128;
   PD_CHECK((long long)((a->N + qpb - 1) / qpb) * a->heads * a->B < (1ll << 31), PD_ERR_SHAPE, "pd_attn_d8: grid too large");
   dim3 grid(((a->N + qpb - 1) / qpb) * a->heads * a->B);
   hipStream_t st = (hipStream_t)stream;
@@ -1213,12 +1183,10 @@ extern "C" int pd_attn_d8(const pd_attn_args* a, void* stream) {
   if (a->dtype == PD_F32) {
     hipLaunchKernelGGL((attn_kernel<float, 1, 4>), dim3(((a->N + 127) / 128) * a->heads * a->B), dim3(256), 0, st, *a);
   } else if (a->dtype == PD_BF16) {
-    if (qbw == 2) hipLaunchKernelGGL((attn_kernel<bf16_t, 2, 4>), grid, dim3(256), 0, st, *a);
-    else if (wide) hipLaunchKernelGGL((attn_kernel<bf16_t, 1, 8>), grid, dim3(512), 0, st, *a);
+    if (wide) hipLaunchKernelGGL((attn_kernel<bf16_t, 1, 8>), grid, dim3(512), 0, st, *a);
     else hipLaunchKernelGGL((attn_kernel<bf16_t, 1, 4>), grid, dim3(256), 0, st, *a);
   } else if (a->dtype == PD_F16) {
-    if (qbw == 2) hipLaunchKernelGGL((attn_kernel<half_t, 2, 4>), grid, dim3(256), 0, st, *a);
-    else if (wide) hipLaunchKernelGGL((attn_kernel<half_t, 1, 8>), grid, dim3(512), 0, st, *a);
+    if (wide) hipLaunchKernelGGL((attn_kernel<half_t, 1, 8>), grid, dim3(512), 0, st, *a);
     else hipLaunchKernelGGL((attn_kernel<half_t, 1, 4>), grid, dim3(256), 0, st, *a);
   } else { set_error("pd_attn_d8: bad dtype"); return PD_ERR_ARG; }
   PD_LAUNCH_CHECK();

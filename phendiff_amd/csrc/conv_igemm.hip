@@ -21,79 +21,20 @@
 #include "pd_stage.h"
 #include "pd_conv.h"
 
-#ifndef PD_S2_SINGLE
-#define PD_S2_SINGLE 1
-#endif
-// Diagnostic (scripts/experiments/overlap_pair.py, -DPD_CONV_PRIO_BASE=2): wave priority of the conv kernel outside / inside its MFMA
-// clusters -- the controlled attention || convolution co-residency experiment of round 3.  The shipped build keeps 0 / 1.
-#ifndef PD_CONV_PRIO_BASE
-#define PD_CONV_PRIO_BASE 0
-#endif
-// 16-bit 3x3 stride-1 double-buffered variants multiply with v_mfma_f32_16x16x32 instead of 32x32x16 (see M16 in conv_kernel).
-// -DPD_CONV_M16=0 builds the 32x32x16 form everywhere (same-box A/B).
-// Round 6: depth of the weight-fragment register ring of the 8-wide 3x3 tiles (<= 128 pixels, 16-bit engines; 0: the general 3); must divide 18.
+namespace pd {
+
+// Round 6: depth of the weight-fragment register ring of the 8-wide 3x3 tiles (<= 128 pixels, 16-bit engines); must divide 18.
 // A 64-pixel tile has ONE 32-cycle MFMA per k-step and wave, so the general ring fetched a weight fragment 64 matrix cycles before its use -- far less
 // than an L2 round trip, let alone the HBM trip of the trajectory where 1.7 GB of weights pass between two uses of a layer.  Five k-steps ahead
 // (24 registers of 94): 1 280 -> 1 280 @8x8 with cold weights 117 -> 94 us, 2 560 -> 1 280 227 -> 170 us; same box, whole workloads: SD img2img
 // +1.9 %, SD fine-tuning +0.6 % (profiles/r6_ab_conv8_ring_*.log).  9 / 18 deep: no further gain.
-#ifndef PD_CONV_AR8
-#define PD_CONV_AR8 6
-#endif
-#ifndef PD_CONV_AR8_64   // ... of the 64-pixel tile (8 x 8 images)
-#define PD_CONV_AR8_64 PD_CONV_AR8
-#endif
-#ifndef PD_CONV_PIXMAP16   // 1: staging pieces dealt to the lanes pixel-fastest (conv_kernel PIXMAP16) -- diagnostic builds: removes the LDS store conflicts and is
-                           // 1.5 % SLOWER on the headline (15.25 vs 15.48 images/s, same box): a 16-lane group of the global load then touches 16 lines instead of 4
-#define PD_CONV_PIXMAP16 0
-#endif
-#ifndef PD_CONV_TAILPLAIN_WPS   // workgroups per CU the prologue-free convolutions with a fused 1x1 tail are compiled for (0: as the tail-free form, 3 -- where they spill 20 B / lane)
-#define PD_CONV_TAILPLAIN_WPS 0
-#endif
-#ifndef PD_CONV_RMAP     // 1: bank-conflict-free row order of the 8 x 8 tile's fragments (conv_kernel RMAP) -- diagnostic builds: parity-green, neutral as an op
-                         // (94.2 vs 94.4 us, 176 vs 177 us) and on SD img2img (9.943 vs 9.948): the LDS pipe was never what this tile waited for
-#define PD_CONV_RMAP 0
-#endif
-#ifndef PD_CONV_M16
-#define PD_CONV_M16 1
-#endif
-// Experiment switches (round 4): the 16x16x32 form behind a GroupNorm prologue too; the wave-priority raise of the MFMA clusters.
-#ifndef PD_CONV_M16_GN
-#define PD_CONV_M16_GN 0
-#endif
-#ifndef PD_CONV_MFMA_PRIO
-#define PD_CONV_MFMA_PRIO 1
-#endif
-// PRO (compile-time GroupNorm + SiLU prologue, branch-free staging, MFMA / vector interleave by sched_group_barrier): which launches take it
-// (0 = none, 1 = the two-tile form, 2 = the one-tile form too), its waves per SIMD (register budget), the MFMA slot at which the staging
-// work of a chunk starts, and whether the activation fragments of the next k-step are read ahead.
-#ifndef PD_CONV_PRO
-#define PD_CONV_PRO 1
-#endif
-#ifndef PD_CONV_PRO_WPS
-#define PD_CONV_PRO_WPS 3
-#endif
-#ifndef PD_CONV_PRO_START
-#define PD_CONV_PRO_START 8
-#endif
-#ifndef PD_CONV_PRO_DSR
-#define PD_CONV_PRO_DSR 1
-#endif
-#ifndef PD_CONV_PRO_M16
-#define PD_CONV_PRO_M16 0     /* 16x16x32 MFMAs in the PRO launches: 0 = none, 1 = the two-tile form, 2 = the one-tile form too */
-#endif
-#ifndef PD_CONV_PRO_PV
-#define PD_CONV_PRO_PV 24     /* non-transcendental vector instructions of one staged piece (counted in the ISA) */
-#endif
-namespace pd {
-
-
-
-// Ablation switches for diagnostic builds (scripts/ablate_conv.sh); never defined in the shipped library.
-#ifdef PD_ABL_W0
-#define PD_WIDX(i) 0            /* every weight fragment load hits fragment 0 (L1-resident): prices the weight stream */
-#else
-#define PD_WIDX(i) (i)
-#endif
+constexpr int CONV_AR8 = 6;
+// PRO (compile-time GroupNorm + SiLU prologue, branch-free staging, MFMA / vector interleave by sched_group_barrier): the two-tile form takes it
+// by default (dispatch_conv; the one-tile form under PRO was +-0.5 % and spilled 28-64 B), at this many waves per SIMD (register budget), with the
+// staging work of a chunk starting at this MFMA slot
+constexpr int CONV_PRO_DEFAULT = 1;
+constexpr int CONV_PRO_WPS = 3;
+constexpr int CONV_PRO_START = 8;
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{})
 template <int... I, typename F> __device__ __forceinline__ void pd_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, typename F> __device__ __forceinline__ void pd_static_for(F&& f) { pd_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
@@ -119,19 +60,6 @@ constexpr int pro_ops_done(int S, int NS, int PS0, int NIT) {
   return done;
 }
 __device__ __forceinline__ unsigned pd_lin_block() { return blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z); }
-#ifdef PD_STAMPS   // diagnostic build only (scripts/stamp_conv.py): phase timestamps of the first workgroups
-__device__ unsigned long long pd_conv_stamps[4096 * 16];
-#define PD_STAMP(k)                                                                                   \
-  do {                                                                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-    unsigned long long t_;                                                                            \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-    if (threadIdx.x == 0 && pd_lin_block() < 4096) pd_conv_stamps[pd_lin_block() * 16 + (k)] = t_;            \
-  } while (0)
-#else
-#define PD_STAMP(k) do {} while (0)
-#endif
 // NCO = 2 (3x3 stride 1, 256-pixel tiles, Cout % 128 == 0): a workgroup computes TWO 64-channel output tiles from one staged
 // halo tile -- every staged (GroupNorm + SiLU-transformed) activation and every LDS fragment read feeds twice the MFMAs, and the
 // grid of the 128 / 256-channel layers (4096 / 2048 workgroups of the NCO = 1 form on 768 slots = 5.33 / 2.67 rounds) becomes
@@ -139,8 +67,9 @@ __device__ unsigned long long pd_conv_stamps[4096 * 16];
 // PLAIN (compile time): no GroupNorm / SiLU prologue -- the input gradients of every convolution, the latent-diffusion UNet's convolutions
 // (its GroupNorms are applied by pd_gn_apply), the upsamplers.  The 16 scale / shift registers and the transform are gone, which is what lets
 // the 16x16x32 MFMA form (M16 below) fit the register budgets.
+// (the PLAIN launches with a fused 1x1 tail share the tail-free budget: 3 workgroups per CU for the 256-pixel 16-bit tiles, where they spill 20 B / lane)
 template <typename T, int KS, int STRIDE, int TH, int TW, bool DB, bool TAIL, int NCO = 1, bool PLAIN = false, int PRO = 0, bool STACK = false>
-__global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL && PLAIN && PD_CONV_TAILPLAIN_WPS) ? PD_CONV_TAILPLAIN_WPS : (((KS == 1 || (KS == 3 && STRIDE == 1 && TH * TW == 256)) && sizeof(T) == 2) ? 3 : 2)))) void conv_kernel(const ConvP p) {
+__global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? CONV_PRO_WPS : (((KS == 1 || (KS == 3 && STRIDE == 1 && TH * TW == 256)) && sizeof(T) == 2) ? 3 : 2))) void conv_kernel(const ConvP p) {
   static_assert(PRO == 0 || (!PLAIN && DB && KS == 3 && STRIDE == 1 && sizeof(T) == 2), "compile-time prologue: 16-bit 3x3 stride-1 double-buffered launches");   // 1x1: fits 168 registers without spilling -> 3 workgroups per CU
   static_assert(!TAIL || (DB && KS == 3 && STRIDE == 1), "fused shortcut tail: 3x3 stride-1 double-buffered variant only");
   static_assert(NCO == 1 || (NCO == 2 && DB && KS == 3 && STRIDE == 1), "two output tiles per workgroup: 3x3 stride-1 double-buffered variant only");
@@ -168,14 +97,14 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   // chip holds a higher clock on this shape under the convolution's load (it runs at 1.9-2.0 GHz, profiles/r3_conv_clock.json;
   // MI355X_MICROARCH.md "DVFS give-back" item 7; a timing-only build of this kernel with the shape swapped: -4.1 % on the sum of 3x3).
   // The form needs 4 (NCO = 1) / 8 (NCO = 2) registers more for its A operands (a tap's two operands are prefetched a whole tap ahead) and
-  // spilled behind a GroupNorm prologue (16 scale / shift registers): shipped for the PLAIN instantiations only, where it fits (162 VGPRs,
+  // spilled behind a GroupNorm prologue (16 scale / shift registers): used by the PLAIN instantiations only, where it fits (162 VGPRs,
   // no scratch) -- same box: the SD UNet's 3x3 convolutions -4.3 % (16 x 16 levels -12 %), SD img2img +1.4...1.6 %, SD fine-tuning +1.1 %.
   //   A: the PACKED weights are unchanged (32 co x 16 k fragments, lane (r, h) = 8 channels 16 half + 8 h of row r): lane (i, g) of the
   //      16 co x 32 k operand ti reads the 16 bytes of old lane (16 ti + i, g & 1) of half g >> 1 -- four 256-byte runs per wave;
   //   B: lane (i, g) reads pixel i of its 16-pixel run, channels 8 g .. 8 g + 7 (one ds_read_b128); pixel pitch 160 B (10 slots):
   //      the 144-byte pitch is 2-way conflicted for this access, 160 is conflict-free (brute force over the ds_read_b128 lane groups);
   //   D: acq[c][f][2 ti + tj]: lane (i, g) owns pixel 16 tj + i of fragment f and channels 16 ti + 4 g .. + 3 of tile c.
-  constexpr bool M16 = PD_CONV_M16 && (PLAIN || (PD_CONV_M16_GN && (NCO == 1 || PD_CONV_M16_GN >= 2)) || (PRO && PD_CONV_PRO_M16 >= (NCO == 2 ? 1 : 2))) && sizeof(T) == 2 && (KS == 3 || KS == 2) && STRIDE == 1 && DB && TW >= 16;
+  constexpr bool M16 = PLAIN && sizeof(T) == 2 && (KS == 3 || KS == 2) && STRIDE == 1 && DB && TW >= 16;
   constexpr int CHB = 32 * E::BYTES;                 // bytes of one 32-channel chunk of a pixel
   constexpr int PITCH = DB ? 2 * CHB + (M16 ? 32 : 16) : CHB + 16;
   constexpr int NIT = (NPIX * 4 + 255) / 256;
@@ -185,7 +114,6 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   static_assert(RPF >= 1 && TW * RPF == 32, "TW must divide 32");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  if (PD_CONV_PRIO_BASE) __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE);
 
   // ---- block -> (pixel tile, co tile, sample) = (x, y, z): the co tiles of one pixel tile are tiles-per-image blocks
   // apart in dispatch order, i.e. on the same XCD / L2 whenever tiles-per-image % 8 == 0 (speed only)
@@ -202,7 +130,6 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   int tx, ty;
   if (p.tiles_x_shift >= 0) { tx = bx & (p.tiles_x - 1); ty = bx >> p.tiles_x_shift; }
   else { ty = bx / p.tiles_x; tx = bx - ty * p.tiles_x; }
-  PD_STAMP(0);
   const int y0 = ty * TH, x0 = tx * TW;
 
   const int tid = threadIdx.x;
@@ -219,15 +146,11 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   const __amdgpu_buffer_rsrc_t rt0 = __builtin_amdgcn_make_buffer_rsrc((void*)(TAIL ? p.t0 : p.x0), 0, TAIL ? p.tbytes0 : p.bytes0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rt1 = __builtin_amdgcn_make_buffer_rsrc((void*)((TAIL && p.t1) ? p.t1 : p.x0), 0, (TAIL && p.t1) ? p.tbytes1 : p.bytes0, 0x00020000);
 
-  // ---- staging bookkeeping: this thread's pieces (pixel, 8-channel sub-block)
-  // Round 6: which (pixel, 8-channel sub-block) piece a thread stages.  Per 64 lanes the pieces are the same 16 pixels x 4 sub-blocks either way (same global
-  // lines), but with lane = 4 pixel + sub a 16-lane pass of the LDS store covers 4 pixels x 64 B, and at the 144-byte (and 80-byte) pixel pitch pixels p and
-  // p + 2 overlap in 8 banks: every store pass ran twice (PMC: 19-28 % of the convolutions' LDS-active cycles were conflict cycles).  lane = 16 sub + pixel puts
-  // 16 different pixels' same sub-block into a pass: 36 p mod 64 = 16 different multiples of 4, conflict-free.  (The 160-byte pitch of the 16x16x32 form repeats
-  // every 8 pixels: it keeps the old map.)
-  constexpr bool PIXMAP16 = PD_CONV_PIXMAP16 && !M16;
-  const int sub = PIXMAP16 ? (tid >> 4) & 3 : tid & 3;
-  auto stage_pix = [&](int i) { return PIXMAP16 ? ((tid >> 6) + 4 * i) * 16 + (tid & 15) : (tid + 256 * i) >> 2; };
+  // ---- staging bookkeeping: this thread's pieces (pixel, 8-channel sub-block), lane = 4 pixel + sub
+  // (round 6: the pixel-fastest map lane = 16 sub + pixel removes the LDS store conflicts of the 144- / 80-byte pitch but was 1.5 % SLOWER on the headline,
+  // 15.25 vs 15.48 images/s, same box: a 16-lane group of the global load then touches 16 lines instead of 4)
+  const int sub = tid & 3;
+  auto stage_pix = [&](int i) { return (tid + 256 * i) >> 2; };
   const int Hc = p.upsample ? p.Hin * 2 : p.Hin;
   const int Wc = p.upsample ? p.Win * 2 : p.Win;
   int spix[NIT];   // linear source pixel index (n, sy, sx) or -1 (zero padding / no such piece)
@@ -276,12 +199,8 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
     const unsigned cbytes = (unsigned)(cch + sub * 8) * E::BYTES;
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
-#ifdef PD_ABL_X0
-      const unsigned off = OOB_OFF;   // ablation: no activation traffic
-#else
       const bool want = TAIL ? (stage_plain ? spix[i] >= TAIL_CENTRE : spix[i] >= 0) : spix[i] >= 0;
       const unsigned off = want ? (unsigned)(TAIL ? spix[i] & (TAIL_CENTRE - 1) : spix[i]) * cs * E::BYTES + cbytes : OOB_OFF;
-#endif
       stage[i] = src == 0 ? Stage<T>::load(rs0, off) : (src == 1 ? Stage<T>::load(rs1, off)
                  : (src == 2 ? Stage<T>::load(rt0, off) : Stage<T>::load(rt1, off)));
     }
@@ -366,12 +285,9 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   };
 
   // ---- per-lane LDS read bases for the B (activation) fragments
-  // RMAP (round 6, the 8 x 8 tile = 8 x 8 images): the four 8-pixel rows of fragment fi are tile rows {0, 4, 1, 5} + 2 fi instead of 4 fi + {0..3}.  A 16-lane pass
-  // of the ds_read_b128 then covers halo-tile pixels 10 y + (0..7) and 10 (y + 4) + (0..7) = 16 different residues mod 16 (the 144-byte pixel pitch repeats
-  // its banks every 16 pixels); rows y and y + 1 put pixels p and p + 16 into one pass: every pass ran twice (PMC: conflict cycles 0.64 of the LDS-active
-  // cycles of this instantiation, by far the most conflicted kernel of the SD workloads).  Only the lane -> pixel map changes (here and in the epilogue).
-  constexpr bool RMAP = PD_CONV_RMAP && TH == 8 && TW == 8 && KS == 3 && STRIDE == 1 && !STACK;
-  auto frag_row = [&](int fi, int q) { return RMAP ? (q >> 1) + 4 * (q & 1) + 2 * fi : fi * RPF + q; };     // tile row of 8-pixel run q of fragment fi
+  // (round 6: a bank-conflict-free row order {0, 4, 1, 5} + 2 fi for the 8 x 8 tile's fragments was parity-green but neutral as an op, 94.2 vs 94.4 us,
+  // and on SD img2img, 9.943 vs 9.948 images/s: the LDS pipe was never what this tile waited for)
+  auto frag_row = [&](int fi, int q) { return fi * RPF + q; };     // tile row of 8-pixel run q of fragment fi
   const int li = lane & 15, lg = lane >> 4;          // M16: row / column within a 16 x 16 operand, k group
   constexpr int TJ_STEP = (TW >= 32 ? 16 : IN_TW) * PITCH;   // M16: bytes from the first to the second 16-pixel run of a fragment
   int rbase[NF];
@@ -400,14 +316,14 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   const unsigned wlane = (unsigned)lane * 8u * E::BYTES;
   const unsigned wtile = (unsigned)ct32 * (unsigned)all_ksteps * wfrag;         // this wave's (first) 32-co tile
   const unsigned wstep = 2u * (unsigned)all_ksteps * wfrag;                     // NCO = 2: bytes between this wave's two 32-co tiles
-  auto load_w = [&](int c, int kstep) { return E::load_buf(rw, wlane, wtile + (unsigned)c * wstep + (unsigned)PD_WIDX(kstep) * wfrag); };
+  auto load_w = [&](int c, int kstep) { return E::load_buf(rw, wlane, wtile + (unsigned)c * wstep + (unsigned)kstep * wfrag); };
 
   // Weight (A) fragments live in a register ring of AR entries, prefetched AD k-steps ahead and CONTINUOUSLY across
   // chunk boundaries (a chunk's fragments are contiguous with the next chunk's), so L2 latency (~600-800 cycles under
   // load) is covered by AD x 4 MFMAs.  The ring index is static because AR divides KSTEPS.  The MFMA loop is kept
   // free of branches (prefetch index clamped, not guarded; have_next / wave_active are compile-time) so that it stays
   // ONE scheduling region with counted waits.
-  constexpr int AR = (KS == 3 && TW == 8 && STRIDE == 1 && sizeof(T) == 2 && TP <= 128 && PD_CONV_AR8 > 0) ? (TP == 64 ? PD_CONV_AR8_64 : PD_CONV_AR8) : ((KSTEPS % 3 == 0) ? 3 : 2);
+  constexpr int AR = (KS == 3 && TW == 8 && STRIDE == 1 && sizeof(T) == 2 && TP <= 128) ? CONV_AR8 : ((KSTEPS % 3 == 0) ? 3 : 2);
   static_assert(KSTEPS % AR == 0, "the ring index is static");
   constexpr int AD = AR - 1;
   Frag aring[AR][NCO];
@@ -417,7 +333,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   Frag aq[2][NCO][2];
   const unsigned wlane16 = (unsigned)(((lg >> 1) * 64 + (lg & 1) * 32 + li) * 16);
   auto load_w16 = [&](int c, int tap_index, int ti) {
-    return E::load_buf(rw, wlane16 + (unsigned)ti * 256u, wtile + (unsigned)c * wstep + (unsigned)PD_WIDX(2 * tap_index) * wfrag);
+    return E::load_buf(rw, wlane16 + (unsigned)ti * 256u, wtile + (unsigned)c * wstep + (unsigned)(2 * tap_index) * wfrag);
   };
 
   // one chunk of MFMAs out of `buf`; when DB, pieces of the NEXT chunk are transformed + written to `nbuf` in between
@@ -428,23 +344,20 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
     const int g0 = chunk * KSTEPS;
     Frag bc[NF];                           // activation fragments of the current k-step (3 waves per SIMD cover the LDS latency)
     int piece = 0;
-#ifndef PD_NO_IGLP
     if constexpr (!PRO) __builtin_amdgcn_iglp_opt(0);          // interleave the region's LDS reads / staging VALU work with the MFMAs (same-box A/B: -1 % per forward)
-#endif
     if constexpr (PRO && ACTIVE) {
       // PRO: the chunk is ONE basic block whose instruction order is written out slot by slot (a slot = one MFMA = 32 matrix-pipe
       // cycles during which the vector issue port is free for ~24) and pinned by sched_barrier(0): after every MFMA the LDS read that
       // refills the fragment it just consumed with the NEXT k-step's (four slots ahead of its use), then this slot's share of the
       // staging work of the next chunk.  A piece (8 channels of one pixel) is 9 steps per channel pair -- unpack, affine, scale,
       // exp, exp, +1, rcp, rcp, multiply + pack -- walked two pairs at a time so that consecutive instructions are independent;
-      // steps are dealt to the slots from PD_CONV_PRO_START on by their issue cost (transcendentals 8.7 cycles, packed fp32 5.8,
+      // steps are dealt to the slots from CONV_PRO_START on by their issue cost (transcendentals 8.7 cycles, packed fp32 5.8,
       // the rest ~3-5: profiles/r3_exp_variants.log).  Without this order every piece was a block of ~45 vector instructions BEHIND
       // its three k-steps of MFMAs: an in-order wave ran them one after the other (matrix and vector pipes co-executed in 18 % of the
       // matrix-busy cycles, r3_conv64_inst_mix.txt).
       constexpr int NM = NCO * NF;                    // MFMAs per k-step
       constexpr int NS = KSTEPS * NM;                 // MFMA slots per chunk
-      constexpr int PS0 = PD_CONV_PRO_START < NS - 8 ? PD_CONV_PRO_START : 0;
-      constexpr int NS16 = 2 * NS, PS16 = 2 * PS0;    // the 16x16x32 form: twice the slots of half the length
+      constexpr int PS0 = CONV_PRO_START < NS - 8 ? CONV_PRO_START : 0;
       f32x2 py[4], pw[4];
       u32x4 po;
       auto piece_op = [&](auto ic, auto kc) __attribute__((always_inline)) {
@@ -473,73 +386,38 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
           *(u32x4*)(ok ? nbuf + pix * PITCH + sub * 8 * E::BYTES : lds + NPIX * PITCH) = NEXT_PLAIN ? Stage<T>::raw(stage[i]) : po;
         }
       };
-      // steps [lo, hi) of the chunk's staging work that slot S of NSL runs (a fused-tail chunk: only the NIT stores, spread evenly)
-      auto run_ops = [&](auto s_c, auto nsl_c, auto ps_c) __attribute__((always_inline)) {
-        constexpr int S = decltype(s_c)::value, NSL = decltype(nsl_c)::value, PS = decltype(ps_c)::value;
+      // steps [lo, hi) of the chunk's staging work that slot S runs (a fused-tail chunk: only the NIT stores, spread evenly)
+      auto run_ops = [&](auto s_c) __attribute__((always_inline)) {
+        constexpr int S = decltype(s_c)::value;
         if constexpr (NEXT_PLAIN) {
-          constexpr int lo = (S * NIT) / NSL, hi = ((S + 1) * NIT) / NSL;
+          constexpr int lo = (S * NIT) / NS, hi = ((S + 1) * NIT) / NS;
           pd_static_for<hi - lo>([&](auto gc) __attribute__((always_inline)) {
             piece_op(std::integral_constant<int, lo + decltype(gc)::value>{}, std::integral_constant<int, 36>{});
           });
         } else if constexpr (HAVE_NEXT) {
-          constexpr int lo = S == 0 ? 0 : pro_ops_done(S - 1, NSL, PS, NIT), hi = pro_ops_done(S, NSL, PS, NIT);
+          constexpr int lo = S == 0 ? 0 : pro_ops_done(S - 1, NS, PS0, NIT), hi = pro_ops_done(S, NS, PS0, NIT);
           pd_static_for<hi - lo>([&](auto gc) __attribute__((always_inline)) {
             constexpr int g = lo + decltype(gc)::value;
             piece_op(std::integral_constant<int, g / PRO_OPS>{}, std::integral_constant<int, g % PRO_OPS>{});
           });
         }
       };
-      if constexpr (!M16) {
 #pragma unroll
-        for (int f = 0; f < NF; ++f) bc[f] = E::load(buf + rbase[f]);                    // k-step 0: tap 0, first half
+      for (int f = 0; f < NF; ++f) bc[f] = E::load(buf + rbase[f]);                    // k-step 0: tap 0, first half
+      __builtin_amdgcn_sched_barrier(0);
+      pd_static_for<NS>([&](auto sc_) __attribute__((always_inline)) {
+        constexpr int S = decltype(sc_)::value, ks = S / NM, m = S % NM, f = m / NCO, c = m % NCO;
+        constexpr int tapn = (ks + 1) >> 1, sn = (ks + 1) & 1;
+        constexpr int toffn = ((tapn / KS) * IN_TW + (tapn % KS)) * PITCH + sn * 16 * E::BYTES;
+        if constexpr (m == 0) {
+#pragma unroll
+          for (int cc = 0; cc < NCO; ++cc) aring[(ks + AD) % AR][cc] = load_w(cc, g0 + ks + AD);
+        }
+        acc[c][f] = E::mma(aring[ks % AR][c], bc[f], acc[c][f]);
+        if constexpr (c == NCO - 1 && ks + 1 < KSTEPS) bc[f] = E::load(buf + rbase[f] + toffn);
+        run_ops(sc_);
         __builtin_amdgcn_sched_barrier(0);
-        pd_static_for<NS>([&](auto sc_) __attribute__((always_inline)) {
-          constexpr int S = decltype(sc_)::value, ks = S / NM, m = S % NM, f = m / NCO, c = m % NCO;
-          constexpr int tapn = (ks + 1) >> 1, sn = (ks + 1) & 1;
-          constexpr int toffn = ((tapn / KS) * IN_TW + (tapn % KS)) * PITCH + sn * 16 * E::BYTES;
-          if constexpr (m == 0) {
-  #pragma unroll
-            for (int cc = 0; cc < NCO; ++cc) aring[(ks + AD) % AR][cc] = load_w(cc, g0 + ks + AD);
-          }
-          acc[c][f] = E::mma(aring[ks % AR][c], bc[f], acc[c][f]);
-          if constexpr (c == NCO - 1 && ks + 1 < KSTEPS) bc[f] = E::load(buf + rbase[f] + toffn);
-          run_ops(sc_, std::integral_constant<int, NS>{}, std::integral_constant<int, PS0>{});
-          __builtin_amdgcn_sched_barrier(0);
-        });
-  } else {
-        // 16x16x32 form: a slot is one 16-cycle MFMA; half-step hs = (tap, pixel half s) = 16 NCO / 2 MFMAs over the tap's A operands
-        // aq[tap & 1][c][ti] (the next tap's are loaded at s == 0) and the B operands bq[f][tj] of fragments 2 s, 2 s + 1 -- each
-        // bq is consumed by NCO x 2 consecutive MFMAs and then refilled with the NEXT half-step's fragment (>= 6 slots ahead of its use)
-        constexpr int FH = NF / 2;
-        constexpr int MH = NCO * FH * 4;                // MFMAs per half-step
-        static_assert(NS16 == KSTEPS * MH, "slot count");
-        Frag bq[FH][2];
-#pragma unroll
-        for (int f = 0; f < FH; ++f)
-#pragma unroll
-          for (int tj = 0; tj < 2; ++tj) bq[f][tj] = E::load(buf + rbase[0] + f * (RPF * IN_TW * PITCH) + tj * TJ_STEP);
-        __builtin_amdgcn_sched_barrier(0);
-        pd_static_for<NS16>([&](auto sc_) __attribute__((always_inline)) {
-          constexpr int S = decltype(sc_)::value, hs = S / MH, m = S % MH, tap = hs >> 1, s2 = hs & 1;
-          // slot order inside a half-step: (f, tj) outer -- one B operand --, (c, ti) inner
-          constexpr int f = m / (2 * NCO * 2), tj = (m / (NCO * 2)) % 2, c = (m / 2) % NCO, ti = m % 2;
-          constexpr int tapn = (hs + 1) >> 1, sn = (hs + 1) & 1;
-          constexpr int toffn = ((tapn / KS) * IN_TW + (tapn % KS)) * PITCH;
-          if constexpr (m == 0 && s2 == 0) {
-#pragma unroll
-            for (int cc = 0; cc < NCO; ++cc)
-#pragma unroll
-              for (int t2 = 0; t2 < 2; ++t2) aq[(tap + 1) & 1][cc][t2] = load_w16(cc, chunk * TAPS + tap + 1, t2);
-          }
-          acq[c][s2 * FH + f][2 * ti + tj] = E::mma_16x16x32(aq[tap & 1][c][ti], bq[f][tj], acq[c][s2 * FH + f][2 * ti + tj]);
-          if constexpr (c == NCO - 1 && ti == 1 && hs + 1 < KSTEPS)
-            bq[f][tj] = E::load(buf + rbase[0] + (sn * FH + f) * (RPF * IN_TW * PITCH) + tj * TJ_STEP + toffn);
-          run_ops(sc_, std::integral_constant<int, NS16>{}, std::integral_constant<int, PS16>{});
-          __builtin_amdgcn_sched_barrier(0);
-        });
-#pragma unroll
-        for (int c = 0; c < NCO; ++c) { aq[0][c][0] = aq[1][c][0]; aq[0][c][1] = aq[1][c][1]; }      // (TAPS is odd: see the general form below)
-      }
+      });
     } else
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks) {
@@ -559,7 +437,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
         for (int f = 0; f < FH; ++f)
 #pragma unroll
           for (int tj = 0; tj < 2; ++tj) bq[f][tj] = E::load(buf + rbase[0] + (s * FH + f) * (RPF * IN_TW * PITCH) + tj * TJ_STEP + toff);
-        __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE + PD_CONV_MFMA_PRIO);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int c = 0; c < NCO; ++c)
 #pragma unroll
@@ -569,7 +447,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
 #pragma unroll
               for (int tj = 0; tj < 2; ++tj)
                 acq[c][s * FH + f][2 * ti + tj] = E::mma_16x16x32(aq[tap & 1][c][ti], bq[f][tj], acq[c][s * FH + f][2 * ti + tj]);
-        __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE);
+        __builtin_amdgcn_s_setprio(0);
       } else if constexpr (ACTIVE) {
 #pragma unroll
         for (int c = 0; c < NCO; ++c) aring[(ks + AD) % AR][c] = load_w(c, g0 + ks + AD);
@@ -579,12 +457,12 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
 #pragma unroll
           for (int f = 0; f < NF; ++f) bc[f] = E::load(buf + rbase[f] + toff);
         }
-        __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE + PD_CONV_MFMA_PRIO);   // keeps the 4-MFMA cluster together and ahead of the other wave's VALU work (+5 %)
+        __builtin_amdgcn_s_setprio(1);   // keeps the 4-MFMA cluster together and ahead of the other wave's VALU work (+5 %)
 #pragma unroll
         for (int c = 0; c < NCO; ++c)
 #pragma unroll
           for (int f = 0; f < NF; ++f) acc[c][f] = E::mma(aring[ks % AR][c], bc[f], acc[c][f]);
-        __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE);
+        __builtin_amdgcn_s_setprio(0);
       }
       if constexpr (DB && HAVE_NEXT) {
         // spread the NIT pieces of the next chunk evenly over the k-steps
@@ -618,7 +496,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
         for (int f = 0; f < FH; ++f)
 #pragma unroll
           for (int tj = 0; tj < 2; ++tj) bq[f][tj] = E::load(buf + rbase[0] + (s * FH + f) * (RPF * IN_TW * PITCH) + tj * TJ_STEP + CENTER);
-        __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE + PD_CONV_MFMA_PRIO);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int c = 0; c < NCO; ++c)
 #pragma unroll
@@ -628,7 +506,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
 #pragma unroll
               for (int tj = 0; tj < 2; ++tj)
                 acq[c][s * FH + f][2 * ti + tj] = E::mma_16x16x32(ta[c][ti], bq[f][tj], acq[c][s * FH + f][2 * ti + tj]);
-        __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE);
+        __builtin_amdgcn_s_setprio(0);
       }
     } else if constexpr (ACTIVE) {
       const int kt = main_ksteps + (chunk - p.n_main) * 2;
@@ -638,7 +516,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
       Frag b0[NF], b1[NF];
 #pragma unroll
       for (int f = 0; f < NF; ++f) { b0[f] = E::load(buf + rbase[f] + CENTER); b1[f] = E::load(buf + rbase[f] + CENTER + 16 * E::BYTES); }
-      __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE + PD_CONV_MFMA_PRIO);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int c = 0; c < NCO; ++c) {
 #pragma unroll
@@ -646,7 +524,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
 #pragma unroll
         for (int f = 0; f < NF; ++f) acc[c][f] = E::mma(a1[c], b1[f], acc[c][f]);
       }
-      __builtin_amdgcn_s_setprio(PD_CONV_PRIO_BASE);
+      __builtin_amdgcn_s_setprio(0);
     }
     if constexpr (HAVE_NEXT) {
 #pragma unroll
@@ -657,7 +535,6 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
   // instead of an if/else diamond (which made the register allocator keep two accumulator sets)
   using std::true_type; using std::false_type;
 
-  PD_STAMP(7);
   // bias / temb first: they are older than the HBM loads below in the in-order vmcnt queue, so initialising the
   // accumulators does not wait for the activation tile
   // Round 3: all of them issued back to back, ONE wait -- the per-group `if (temb) { load; add }` form made the compiler wait for
@@ -703,7 +580,6 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
 #pragma unroll
         for (int i = 0; i < 4; ++i) bt[c][g][i] += __uint_as_float(tv[c][g][i]);
   }
-  PD_STAMP(8);
   // accumulators start at bias[co] + temb[n][co] (lane (pixel, h), register i <-> co = 8(i>>2) + 4h + (i&3)):
   // the epilogue then has no per-channel loads at all
   if constexpr (M16) {
@@ -737,21 +613,17 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
       for (int c = 0; c < NCO; ++c) aring[i][c] = load_w(c, i);
   }
   }
-  PD_STAMP(9);
   if (!p.im2col3) zero_padding();
   if (DB) {
     if (p.im2col3) {
       stage_im2col(lds);
     } else {
       write_piece(0, lds);
-      PD_STAMP(10);
 #pragma unroll
       for (int i = 1; i < NIT; ++i) write_piece(i, lds);
     }
     if (p.nchunks > 1) issue_loads(1);
-    PD_STAMP(1);
     __syncthreads();
-    PD_STAMP(2);
     int chunk = 0;
     // with a tail every main chunk has a successor; PRO: the last main chunk (which stages the first tail chunk as it is) is peeled below
     const int main_loop_end = TAIL ? (PRO ? p.n_main - 1 : p.n_main) : p.nchunks - 1;
@@ -762,9 +634,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
       else if (wave_active) mma_chunk(chunk, buf, nbuf, true_type{}, true_type{});
       else mma_chunk(chunk, buf, nbuf, true_type{}, false_type{});
       if (chunk + 2 < p.nchunks) issue_loads(chunk + 2);
-      if (chunk == 0) PD_STAMP(3);
       __syncthreads();
-      if (chunk == 0) PD_STAMP(4);
     }
     if constexpr (TAIL && PRO) {
       mma_chunk(chunk, lds + (chunk & 1) * LDS_TILE, lds + ((chunk + 1) & 1) * LDS_TILE, std::integral_constant<int, 2>{}, true_type{});
@@ -786,7 +656,6 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
       if (wave_active) mma_chunk(chunk, lds + (chunk & 1) * LDS_TILE, lds, false_type{}, true_type{});
     }
     __syncthreads();
-    PD_STAMP(5);
   } else {
     for (int chunk = 0; chunk < p.nchunks; ++chunk) {
       if (chunk > 0) __syncthreads();
@@ -892,7 +761,7 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
     } else {
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-      const int plin = RMAP ? frag_row(wp * NF + f, r / TW) * TW + r % TW : (wp * NF + f) * 32 + r;
+      const int plin = (wp * NF + f) * 32 + r;
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         store4((T*)(lds + plin * EP_PITCH) + wc * 32 + 8 * g + 4 * h, acc[cth][f][4 * g], acc[cth][f][4 * g + 1], acc[cth][f][4 * g + 2], acc[cth][f][4 * g + 3]);
@@ -986,7 +855,6 @@ __global__ __launch_bounds__(256, NCO == 2 ? 2 : (PRO ? PD_CONV_PRO_WPS : ((TAIL
     }
   }
   }   // cth
-  PD_STAMP(6);
 }
 
 template <typename T, int KS, int STRIDE, int TH, int TW, bool TAIL = false, int NCO = 1, bool PLAIN = false, int PRO = 0, bool STACK = false>
@@ -996,8 +864,8 @@ static int launch_conv(const ConvP& p, hipStream_t st) {
   constexpr int LDS_TILE = ((IN_TH * IN_TW * PITCH + 15) / 16) * 16;
   // double-buffer when two tiles fit comfortably -- and leave room for a second workgroup: the stride-2 halo tile (9 x 65 pixels)
   // double-buffered is 84 KB = ONE workgroup (4 waves) per CU; single-buffered 47 KB admits two, which overlap each other
-  constexpr bool DB = 2 * LDS_TILE <= 100 * 1024 && !(STRIDE == 2 && PD_S2_SINGLE);
-  constexpr bool M16 = PD_CONV_M16 && (PLAIN || (PD_CONV_M16_GN && (NCO == 1 || PD_CONV_M16_GN >= 2)) || (PRO && PD_CONV_PRO_M16 >= (NCO == 2 ? 1 : 2))) && sizeof(T) == 2 && (KS == 3 || KS == 2) && STRIDE == 1 && TW >= 16;        // (conv_kernel: 160-byte pixels)
+  constexpr bool DB = 2 * LDS_TILE <= 100 * 1024 && STRIDE != 2;
+  constexpr bool M16 = PLAIN && sizeof(T) == 2 && (KS == 3 || KS == 2) && STRIDE == 1 && TW >= 16;        // (conv_kernel: 160-byte pixels when DB)
   constexpr int LDS_DB = ((IN_TH * IN_TW * (2 * 32 * Elem<T>::BYTES + (M16 ? 32 : 16)) + 15) / 16) * 16;   // interleaved buffers, one shared pad
   constexpr int EPI_BYTES = TH * TW * (64 * Elem<T>::BYTES + 16) + 256 * 64;   // output tile + stats scratch [256][2*EPC] fp32
   constexpr int LDS_MAIN = (DB ? LDS_DB : LDS_TILE) + (PRO ? 16 : 0);          // PRO: + the dump slot behind the tile
@@ -1076,15 +944,11 @@ static int dispatch_conv(const ConvP& p, int ksize, int stride, hipStream_t st) 
       const bool plain_off = diag_env("PD_CONV_PLAIN", 1) == 0;      // diagnostic: same-box A/B
       const bool plain = !plain_off && p.scale == nullptr && !p.silu && !p.im2col3 && w >= 16;
       // (the two-tile form keeps the 32x32x16 MFMAs: its 16x16x32 form needs 32 registers of A operands and spills at 256)
-      // GroupNorm + SiLU prologue known at compile time (PRO): branch-free staging interleaved with the MFMAs.  PD_CONV_PRO=0 / 1 / 2: diagnostic override (none / the two-tile form / the one-tile form too)
-      const int pro_lvl = diag_env("PD_CONV_PRO", PD_CONV_PRO);
+      // GroupNorm + SiLU prologue known at compile time (PRO): branch-free staging interleaved with the MFMAs.  PD_CONV_PRO=0: diagnostic override (none)
+      const int pro_lvl = diag_env("PD_CONV_PRO", CONV_PRO_DEFAULT);
       const bool gs = p.scale != nullptr && p.silu != 0 && !p.im2col3 && w >= 32 && p.Cout_pad % 64 == 0 && p.out_mode != PD_OUT_NCHW_F32;
       if (nco2 && gs && pro_lvl >= 1)
         return p.n_tail > 0 ? launch_conv<T, 3, 1, 8, 32, true, 2, false, 1>(p, st) : launch_conv<T, 3, 1, 8, 32, false, 2, false, 1>(p, st);
-#ifdef PD_CONV_PRO_NCO1     // diagnostic builds only (-DPD_CONV_PRO_NCO1, then PD_CONV_PRO=2): the one-tile form under PRO is +-0.5 % and spills 28-64 B -- not in the shipped library
-      if (!nco2 && gs && pro_lvl >= 2)
-        return p.n_tail > 0 ? launch_conv<T, 3, 1, 8, 32, true, 1, false, 1>(p, st) : launch_conv<T, 3, 1, 8, 32, false, 1, false, 1>(p, st);
-#endif
       if (nco2) return p.n_tail > 0 ? launch_conv<T, 3, 1, 8, 32, true, 2>(p, st) : launch_conv<T, 3, 1, 8, 32, false, 2>(p, st);
       if (plain) {
         if (p.n_tail > 0) return w >= 32 ? launch_conv<T, 3, 1, 8, 32, true, 1, true>(p, st) : launch_conv<T, 3, 1, 16, 16, true, 1, true>(p, st);
@@ -1219,28 +1083,6 @@ extern "C" int pd_conv(const pd_conv_args* a, void* stream) {
   if (a->dtype == PD_F16) return dispatch_conv<half_t>(p, a->ksize, a->stride, st);
   return dispatch_conv<bf16_t>(p, a->ksize, a->stride, st);
 }
-
-#ifdef PD_STAMPS
-extern "C" int pd_debug_conv_occupancy(int lds_bytes) {
-  int nb = -1;
-  const void* kerns[2] = {(const void*)pd::conv_kernel<pd::bf16_t, 3, 1, 8, 32, true, false>,
-                          (const void*)pd::conv_kernel<pd::bf16_t, 3, 1, 8, 32, true, false, 1, true>};      // GroupNorm-prologue form; PLAIN (16x16x32, 160-byte pixels: 54 400 B)
-  for (int k = 0; k < 2; ++k) {
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kerns[k], 256, (size_t)lds_bytes);
-    hipFuncAttributes fa;
-    hipFuncGetAttributes(&fa, kerns[k]);
-    printf("occupancy API (%s): %d blocks/CU at %d B dyn LDS (err %d); numRegs %d sharedStatic %zu maxDyn %d\n", k ? "PLAIN" : "GN", nb, lds_bytes, (int)e,
-           fa.numRegs, fa.sharedSizeBytes, fa.maxDynamicSharedSizeBytes);
-  }
-  hipDeviceProp_t pr; hipGetDeviceProperties(&pr, 0);
-  printf("device: sharedMemPerBlock %zu sharedMemPerMultiprocessor %zu regsPerBlock %d CUs %d maxThreadsPerMP %d\n", pr.sharedMemPerBlock,
-         pr.sharedMemPerMultiprocessor, pr.regsPerBlock, pr.multiProcessorCount, pr.maxThreadsPerMultiProcessor);
-  return nb;
-}
-extern "C" int pd_debug_read_conv_stamps(unsigned long long* host, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(pd::pd_conv_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 extern "C" int pd_conv_stat_tiles(int Hout, int Wout, int ksize, int stride) {
   int th, tw;

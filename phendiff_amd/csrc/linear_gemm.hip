@@ -78,11 +78,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && NC == 2) ? 3 : 2) void line
   auto issue = [&](int chunk) {
     const unsigned cb = (unsigned)(chunk * CK * ES);
 #pragma unroll
-#ifdef PD_LIN_ABL_X          /* diagnostic build: no activation traffic (prices the X stream) */
-    for (int i = 0; i < NIT; ++i) stage[i] = Stage<T>::load(rsx, OOB_OFF + 0 * cb);
-#else
     for (int i = 0; i < NIT; ++i) stage[i] = Stage<T>::load(rsx, soff[i] == OOB_OFF ? OOB_OFF : soff[i] + cb);
-#endif
     if (affine) {
       const int kc = min(chunk * CK, p.K - 8 - (tid & 7) * 8);       // a trailing half chunk's upper sub-blocks are never read
       const float* ps = p.scale + aff_row + kc;
@@ -123,12 +119,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && NC == 2) ? 3 : 2) void line
     // wide tiles (big grids): weight fragments two k-steps ahead in registers, activation fragments read at the top of the
     // k-step; the kernel is held at 3 workgroups per CU (__launch_bounds__: 164-166 registers, accumulators in VGPRs) --
     // prefetching the activation fragments as well spills there (measured), the other resident waves cover that latency
-#ifdef PD_LIN_AD                                       // diagnostic builds: same-box A/B of the prefetch depth
-    constexpr int AD = PD_LIN_AD, AR = 4;
-#else
     constexpr int AD = NC == 4 ? 1 : 2, AR = NC == 4 ? 2 : 4;   // weight fragments 2 k-steps ahead in a ring of 4 (static indices: 4 k-steps / chunk);
                                                                 // NC = 4 (256-channel tiles, 128 accumulator registers): 1 ahead in a ring of 2
-#endif
     Frag aring[AR][NC];
     const int last_kstep = ksteps - 1;
 #pragma unroll
@@ -148,11 +140,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && NC == 2) ? 3 : 2) void line
         if (ks < nks) {
           const int gn = min(g0 + ks + AD, last_kstep);   // clamped at the end
 #pragma unroll
-#ifdef PD_LIN_ABL_W          /* diagnostic build: every weight fragment load hits fragment 0 (prices the weight stream) */
-          for (int c = 0; c < NC; ++c) aring[(ks + AD) % AR][c] = E::load(wb[c] + (size_t)(gn & 0) * 512);
-#else
           for (int c = 0; c < NC; ++c) aring[(ks + AD) % AR][c] = E::load(wb[c] + (size_t)gn * 512);
-#endif
           const Frag b0 = E::load(buf + b_lane + ks * 16 * ES), b1 = E::load(buf + b_lane + 32 * PITCH + ks * 16 * ES);
           __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -635,7 +623,7 @@ static void token_wgrad_plan(long long M, int K, int N, int esz, int* n_tiles, i
 static void token_wgrad_plan_dma(long long M, int K, int N, int tn, int tk, int* n_tiles, int* k_tiles, int* splits, int* cps, int* nchunks) {
   *n_tiles = (N + tn - 1) / tn; *k_tiles = (K + tk - 1) / tk;
   *nchunks = (int)(M / 32);
-  const int s = token_wgrad_splits(*nchunks, *n_tiles * *k_tiles, diag_env("PD_TW_SLOTS", 512), 16);   // >= 16 stages (448 KB staged) per slab tile written (160 KB)
+  const int s = token_wgrad_splits(*nchunks, *n_tiles * *k_tiles, 512, 16);   // >= 16 stages (448 KB staged) per slab tile written (160 KB)
   *cps = (*nchunks + s - 1) / s;
   *splits = (*nchunks + *cps - 1) / *cps;
 }

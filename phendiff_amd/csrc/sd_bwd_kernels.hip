@@ -602,10 +602,10 @@ extern "C" int pd_layernorm_bwd_blocks(long long rows) {
 }
 // Workgroups actually launched (<= the bound above): every workgroup leaves one row of the partial, and the fold of those rows was as long as
 // the kernel itself at 2 048 of them (C = 1 280: 94 us for kernel + fold, 39 us with 512; C = 640: 90 -> 61; C = 320: 132 -> 108 with 1 024,
-// 149 with 512 -- scripts/experiments/bench_ln_bwd.py).  PD_LN_BWD_BLOCKS: diagnostic override.
+// 149 with 512 -- scripts/experiments/bench_ln_bwd.py).
 static int ln_bwd_grid(long long rows, int C) {
   const long long nb = (rows + 3) / 4;
-  const int cap = diag_env("PD_LN_BWD_BLOCKS", C <= 384 ? 1024 : 512);
+  const int cap = C <= 384 ? 1024 : 512;
   const int bound = pd_layernorm_bwd_blocks(rows);
   const long long g = nb < cap ? nb : cap;
   return (int)(g < bound ? g : bound);

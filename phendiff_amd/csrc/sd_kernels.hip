@@ -12,19 +12,6 @@
 
 namespace pd {
 
-#ifndef PD_ATTN64_PIPE      // attn_d64_kernel, two-fragment form.  0: sub-tile by sub-tile; 1: the two query fragments as a two-stage pipeline; 2 (diagnostic builds): + both sub-tiles' scores up front, Q parked in LDS -- parity-green, 912 vs 928 TF/s: the vector issue port binds, not the overlap
-#define PD_ATTN64_PIPE 1
-#endif
-#ifndef PD_ATTN64_PARKQ     // 1: the Q fragments are parked in LDS (lane-private slots) and re-read per MFMA: 32 registers
-#define PD_ATTN64_PARKQ 0
-#endif
-#ifndef PD_ATTN64_QK_SPLIT
-#define PD_ATTN64_QK_SPLIT 0
-#endif
-#ifndef PD_ATTN64_LAZYMAX   // 1: the pipelined form takes the row maximum only when the lane sums of the probabilities say it has to (0: every sub-tile)
-#define PD_ATTN64_LAZYMAX 1
-#endif
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Attention, head_dim 64.  Workgroup = 4 waves = 128 queries of one (batch, head); keys/values stream through LDS in
 // double-buffered tiles of 64.  Per wave and 32-key sub-tile:
@@ -76,21 +63,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && QB == 1) ? 3 : 2) void attn
       qf[j][ks] = E::pack(v);
     }
   }
-  // PIPE2: the Q fragments live in LDS, each lane reading back exactly the 16-byte slots it wrote ([fragment][k-step][thread]: consecutive lanes,
-  // consecutive slots -- no conflict, no barrier): 32 registers for the second sub-tile's scores (see the key loop)
-  constexpr bool PIPE2 = PD_ATTN64_PIPE >= 2 && QB == 2 && sizeof(T) == 2;
-  constexpr bool PARKQ = (PIPE2 || PD_ATTN64_PARKQ) && QB == 2 && sizeof(T) == 2;
-  unsigned char* qpark = lds + 2 * (KBYTES + VBYTES) + tid * 16;
-  if constexpr (PARKQ) {
-#pragma unroll
-    for (int j = 0; j < QB; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) E::store(qpark + (j * 4 + ks) * 4096, qf[j][ks]);
-  }
-  auto qfrag = [&](int j, int ks) __attribute__((always_inline)) -> Frag {
-    if constexpr (PARKQ) return E::load(qpark + (j * 4 + ks) * 4096);
-    else return qf[j][ks];
-  };
   // Deferred-rescale online softmax (as pd_attn_d8): `m` is a REFERENCE maximum (log2 domain) shared by both lane halves of a
   // query, p = exp2(s - m).  It is only raised when some score of the sub-tile exceeds m + RESCALE_THR (p <= 2^THR
   // otherwise: harmless in fp32 / bf16), so the accumulator rescale (32 multiplies), the cross-half exchange and the second
@@ -146,7 +118,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && QB == 1) ? 3 : 2) void attn
       for (int ks = 0; ks < 4; ++ks) {
         const Frag kf = E::load(kb + k_lane + sub * 32 * KP + ks * 16 * ES);
 #pragma unroll
-        for (int j = 0; j < QB; ++j) s[j] = E::mma(kf, qfrag(j, ks), ks == 0 ? negm[j] : s[j]);     // s = S - m
+        for (int j = 0; j < QB; ++j) s[j] = E::mma(kf, qf[j][ks], ks == 0 ? negm[j] : s[j]);     // s = S - m
       }
     };
     // (`ahead`: the scores of the NEXT sub-tile, already computed against the old reference -- a rescale moves them too)
@@ -205,48 +177,26 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && QB == 1) ? 3 : 2) void attn
         }
       }
     };
-    if constexpr (PD_ATTN64_PIPE && QB == 2) {      // (dispatch: QB = 2 only with Nkv % 64 == 0)
+    if constexpr (QB == 2) {      // (dispatch: QB = 2 only with Nkv % 64 == 0)
       // Round 6, whole 64-key tiles of the two-fragment form: the wave's two query fragments are walked as a two-stage pipeline -- scores of
       // fragment 0, scores of fragment 1 (4 + 4 MFMAs from the same K fragments), then softmax(0) while the matrix pipe still works on the
       // scores of 1, PV(0), softmax(1) under PV(0), PV(1).  In the old order (both score chains interleaved, both softmaxes, both PVs) a wave's
       // own MFMAs and vector work never overlapped -- only the other wave of the SIMD filled the gaps (matrix pipe 0.41 busy, LAB_r6 section 3).
       // No extra registers: the V^T fragments are read per query fragment (the LDS pipe was 8.5 % busy).
-      // PIPE2: the scores of BOTH sub-tiles are issued up front (8 + 8 MFMAs; the second sub-tile's run under the first one's softmaxes)
-      f32x16 sall[PIPE2 ? 2 : 1][QB];
-      if constexpr (PIPE2) {
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const Frag kf1 = E::load(kb + k_lane + sub * 32 * KP + ks * 16 * ES);
-#pragma unroll
-            for (int j = 0; j < QB; ++j) sall[sub][j] = E::mma(kf1, qfrag(j, ks), ks == 0 ? negm[j] : sall[sub][j]);
-          }
-      }
+      // (both sub-tiles' scores up front, Q parked in LDS: parity-green, 912 vs 928 TF/s -- the vector issue port binds, not the overlap)
+      f32x16 sall[QB];
 #pragma unroll
       for (int sub = 0; sub < KT / 32; ++sub) {
-        if constexpr (!PIPE2) {
-#if PD_ATTN64_QK_SPLIT      // diagnostic: the two fragments' score chains one after the other (K fragments held in 16 registers)
-          Frag kf[4];
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) kf[ks] = E::load(kb + k_lane + sub * 32 * KP + ks * 16 * ES);
-#pragma unroll
-          for (int j = 0; j < QB; ++j)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) sall[0][j] = E::mma(kf[ks], qfrag(j, ks), ks == 0 ? negm[j] : sall[0][j]);
-#else
-          qk(sub, sall[0]);
-#endif
-        }
+        qk(sub, sall);
         const bool was_first = first;
 #pragma unroll
         for (int j = 0; j < QB; ++j) {
-          f32x16& sc = sall[PIPE2 ? sub : 0][j];
+          f32x16& sc = sall[j];
           // Common path WITHOUT the row maximum (16 v_max3 + compares of ~130 vector instructions per sub-tile; the vector issue port is what binds
           // this kernel): exponentiate against the current reference and look at the lane's SUM of the 16 probabilities, which the row sum needs
           // anyway -- sum <= 2^15 proves every p <= 2^15 (the deferred-rescale invariant p <= 2^THR); a larger or non-finite sum on any lane sends
           // the wave to the exact path below, which recomputes the four score MFMAs (K fragments re-read from LDS) and takes the maximum as before.
-          bool exact = was_first || !PD_ATTN64_LAZYMAX;     // the first sub-tile sets the reference to the exact maximum
+          bool exact = was_first;                             // the first sub-tile sets the reference to the exact maximum
           f32x16 pe;                                          // the probabilities (the scores stay intact for the exact path)
           if (!exact) {
             f32x2 acc2 = (f32x2)(0.f);
@@ -275,12 +225,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && QB == 1) ? 3 : 2) void attn
               l[j] *= alpha;
 #pragma unroll
               for (int i = 0; i < 16; ++i) { o0[j][i] *= alpha; o1[j][i] *= alpha; }
-              if constexpr (PIPE2) {
-                if (sub == 0) {                    // the second sub-tile's scores were computed against the old reference
-#pragma unroll
-                  for (int i = 0; i < 16; ++i) sall[1][j][i] -= delta;
-                }
-              }
               negm[j] = (f32x16)(-m[j]);
             }
             f32x2 acc2 = (f32x2)(0.f);
@@ -433,7 +377,7 @@ __global__ __launch_bounds__(256) void geglu_kernel(const pd_geglu_args a) {
 
 template <typename T, int QB>
 static int launch_attn_d64(const pd_attn_d64_args* a, hipStream_t st) {
-  constexpr int LDS = 2 * 64 * (D64<T>::KP + D64<T>::VP) + (((PD_ATTN64_PIPE >= 2 || PD_ATTN64_PARKQ) && QB == 2 && sizeof(T) == 2) ? QB * 4 * 4096 : 0);
+  constexpr int LDS = 2 * 64 * (D64<T>::KP + D64<T>::VP);
   auto kern = attn_d64_kernel<T, QB>;
   static LdsAttr attr;
   if (!ensure_lds(attr, kern, LDS)) {
@@ -463,11 +407,11 @@ extern "C" int pd_attn_d64(const pd_attn_d64_args* a, void* stream) {
     // two query fragments per wave once that still fills the chip (256 CUs x 2 resident workgroups) and the key sequence is
     // long enough for the LDS traffic to matter
     const bool qb1_only = diag_env("PD_ATTN64_QB1", 0) != 0;      // diagnostic: same-box A/B
-    const bool wide = !qb1_only && a->Nkv >= 512 && (!PD_ATTN64_PIPE || a->Nkv % 64 == 0) && (long long)(a->Nq / 256) * a->heads * a->B >= 1024;
+    const bool wide = !qb1_only && a->Nkv >= 512 && a->Nkv % 64 == 0 && (long long)(a->Nq / 256) * a->heads * a->B >= 1024;
     return wide ? launch_attn_d64<bf16_t, 2>(a, (hipStream_t)stream) : launch_attn_d64<bf16_t, 1>(a, (hipStream_t)stream);
   }
   if (a->dtype == PD_F16) {
-    const bool wide = a->Nkv >= 512 && (!PD_ATTN64_PIPE || a->Nkv % 64 == 0) && (long long)(a->Nq / 256) * a->heads * a->B >= 1024;
+    const bool wide = a->Nkv >= 512 && a->Nkv % 64 == 0 && (long long)(a->Nq / 256) * a->heads * a->B >= 1024;
     return wide ? launch_attn_d64<half_t, 2>(a, (hipStream_t)stream) : launch_attn_d64<half_t, 1>(a, (hipStream_t)stream);
   }
   set_error("pd_attn_d64: bad dtype");

@@ -12,7 +12,6 @@ gradient of the class token (``pd_token_embedding_grad``) -- the only trainable 
 from __future__ import annotations
 
 import ctypes as C
-import os
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -25,8 +24,6 @@ from .sd_unet import (CustomEmbedding, SDUNet2DConditionModel, SDUNetPlan, _SDPa
 from .unet import _Resnet, _Sampler, _copy_into
 from .unet_train import UNetTrainer, UNetTrainPlan, _contiguous_after, run_pack_jobs
 
-# diagnostic switch (same-box A/B): PD_BIAS_FUSE=0 -> every bias gradient of the transformer blocks is a pd_channel_sum pass over its dY again
-_BIAS_FUSE = os.environ.get("PD_BIAS_FUSE", "1") != "0"
 
 EMB_NAME = "class_embedding.inner_module.weight"
 
@@ -196,7 +193,7 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         dx = self._tmp((B, h, w, ch), tag)
         partial = None
         dgam, dbet = self._G2(pname + ".weight", pname + ".bias")
-        fuse = bias_name is not None and dgam is not None and ch <= 1536 and _BIAS_FUSE and bias_name not in self.frozen
+        fuse = bias_name is not None and dgam is not None and ch <= 1536 and bias_name not in self.frozen
         dxsum = self._G(bias_name) if fuse else None
         if dgam is not None:
             partial = self._tmp((self.lib.pd_layernorm_bwd_blocks(rows) * (3 if fuse else 2) * ch,), "lnpart3" if fuse else "lnpart", torch.float32)
@@ -232,7 +229,7 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         dgg = self._dgrad(dh3, te.wff2_d, 4 * ch, ksize=1, tag="t_dgg")
         dff = self._tmp((B, h, w, 8 * ch), "t_dff")
         ga = L.GegluBwdArgs(dtype=self.code, rows=B * N, inner=4 * ch, x=rec.ff.data_ptr(), dy=dgg.data_ptr(), dx=dff.data_ptr())
-        if _BIAS_FUSE and self.param_grads and (4 * ch) % 256 == 0 and (blk + ".ff.net.0.proj.bias") not in self.frozen:
+        if self.param_grads and (4 * ch) % 256 == 0 and (blk + ".ff.net.0.proj.bias") not in self.frozen:
             # the gate's backward also leaves the per-split column sums of dff (the widest gradient of the block): the bias gradient folds
             # those (B x splits x 8 ch floats) instead of reading dff back
             gs = max(1, min(64, N // 64))

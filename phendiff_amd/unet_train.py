@@ -34,8 +34,7 @@ from .unet import CustomCondUNet2DModel, UNetPlan, _Attention, _Op, _PackedWeigh
 _NO_LINEAR_GRADS = bool(os.environ.get("PD_NO_LINEAR_GRADS"))
 # Round 6: every weight-gradient launch is two kernels -- the GEMM that leaves per-split partial tiles in a slab, and the ordered fold of the slab
 # into the fp32 gradient (bandwidth-bound, few workgroups, ~150 + 70 of them per SD-2.1 step).  With ONE slab PER LAUNCH (288 GB of HBM: ~18 GB for the
-# SD-2.1 UNet at B = 32) the folds run on a second stream under the next layers' GEMMs.  PD_WGRAD_SIDE=0: one shared slab, one stream (same-box A/B).
-_WGRAD_SIDE = os.environ.get("PD_WGRAD_SIDE", "1") != "0"
+# SD-2.1 UNet at B = 32) the folds run on a second stream under the next layers' GEMMs.
 # diagnostic (same-box A/B): keep the GroupNorm-prologue 1x1 weight gradients on pd_conv_wgrad (round 3 routes them through
 # pd_gn_apply + pd_token_wgrad)
 _NO_PREAPPLY_WGRAD = bool(os.environ.get("PD_NO_PREAPPLY_WGRAD"))
@@ -295,7 +294,7 @@ class UNetTrainPlan(UNetPlan):
             # the GroupNorm backward that stored the final value of this gradient also left its per-split channel sums
             ws, splits = fused[0], fused[1]
             # (round 6) sums in a workspace no other launch reuses, no per-sample consumer: the fold may run on the second stream with the slab folds
-            side = _WGRAD_SIDE and per_sample is None and len(fused) > 2 and fused[2]
+            side = per_sample is None and len(fused) > 2 and fused[2]
             if side:
                 out = self._tmp((B, ch), "chsum_side", torch.float32)
             a = L.ChannelSumArgs(dtype=self.code, B=B, HW=h * w, C=ch, x=None, out=out.data_ptr(), out_stride=per_stride or ch,
@@ -357,12 +356,8 @@ class UNetTrainPlan(UNetPlan):
         self._emit_wgrad(self.lib.pd_conv_wgrad, a, f"wgrad{ksize}x{ksize}", flops, nbytes, self._wgrad_args)
 
     def _emit_wgrad(self, fn, a, what, flops, nbytes, arglist):
-        """One weight-gradient launch.  Side mode (``_WGRAD_SIDE``): two ops -- stage 1 (the GEMM) in the main sequence and stage 2 (the fold of its
-        slab into the gradient) flagged ``side``, which :meth:`backward` runs on the plan's second stream; the gradient is final after the fold."""
-        if not _WGRAD_SIDE:
-            arglist.append((a, None))
-            self._b(fn, a, what, flops, nbytes)
-            return
+        """One weight-gradient launch as two ops: stage 1 (the GEMM) in the main sequence and stage 2 (the fold of its slab into the gradient)
+        flagged ``side``, which :meth:`backward` runs on the plan's second stream; the gradient is final after the fold."""
         a.stage = 1
         a2 = type(a)()
         C.memmove(C.byref(a2), C.byref(a), C.sizeof(a))
@@ -458,24 +453,14 @@ class UNetTrainPlan(UNetPlan):
         if not self.param_grads:
             return
         self._temb_bwd()
-        # slabs of the weight-gradient launches: ONE per launch in side mode (its fold runs later, on the second stream), else one shared by all
-        # (they then run back to back on one stream)
+        # slabs of the weight-gradient launches: ONE per launch (its fold runs later, on the second stream)
         for pairs, ws in ((self._wgrad_args, self.lib.pd_conv_wgrad_workspace), (self._twgrad_args, self.lib.pd_token_wgrad_workspace)):
-            if not pairs:               # (no convolution weight gradients when every convolution is frozen: attention-only fine-tuning)
-                continue
-            if _WGRAD_SIDE:
-                for a, a2 in pairs:
-                    need = ws(C.byref(a))
-                    slab = torch.empty(need // 4 + 16, dtype=torch.float32, device=self.device)
-                    self.bufs.append(slab)
-                    a.slab = a2.slab = slab.data_ptr()
-                    a.slab_bytes = a2.slab_bytes = need
-            else:
-                need = max(ws(C.byref(a)) for a, _ in pairs)
+            for a, a2 in pairs:         # (none for the convolutions when every convolution is frozen: attention-only fine-tuning)
+                need = ws(C.byref(a))
                 slab = torch.empty(need // 4 + 16, dtype=torch.float32, device=self.device)
                 self.bufs.append(slab)
-                for a, _ in pairs:
-                    a.slab, a.slab_bytes = slab.data_ptr(), need
+                a.slab = a2.slab = slab.data_ptr()
+                a.slab_bytes = a2.slab_bytes = need
 
     def _bwd_record(self, rec):
         """Emit the backward launches of one forward tape record."""
@@ -812,8 +797,6 @@ def fuse_pack_jobs(jobs):
     """A weight is re-packed twice after every optimizer step -- the forward layout and the input-gradient layout (transposed, taps
     flipped) -- from the same fp32 master tensor.  Pairs whose 32 x 32 blocks coincide become ONE job with ``dst2`` (ABI 7): the master
     weights are read once (the re-pack of the SD-2.1 UNet: 6.9 -> 3.5 GB of reads per step).  Jobs without a partner stay as they are."""
-    if os.environ.get("PD_PACK_FUSE", "1") == "0":      # diagnostic override (same-box A/B)
-        return list(jobs)
     fwd = {}
     for a in jobs:
         if not a.dgrad and not a.dst2:

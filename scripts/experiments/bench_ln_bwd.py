@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Round 6 probe: pd_layernorm_bwd (kernel + its partial reduce) against the number of workgroups (= rows of the partial the reduce folds)."""
+"""Round 6 probe: pd_layernorm_bwd (kernel + its partial reduce) against the number of workgroups (= rows of the partial the reduce folds).
+Record only: the PD_LN_BWD_BLOCKS override it sweeps is retired (ln_bwd_grid in sd_bwd_kernels.hip keeps the cap this probe chose)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -6,7 +6,7 @@ their CU residency and wave priority are CONTROLLED?  One layer pair of the head
 on two HIP streams, against the same launches back to back on one stream.  Knobs (environment, read by the library):
     PD_ATTN_LDS_PAD=<bytes>    dynamic LDS per attention workgroup: 70000 -> ONE attention workgroup (8 waves = 2 per SIMD, 127 VGPRs) per CU,
                                leaving registers (512 - 256 = 256 per SIMD) and LDS (~90 KB) for one NCO = 2 conv workgroup (250 VGPRs, 49 KB)
-    PD_LIB=<lib built with -DPD_CONV_PRIO_BASE=2>   conv waves at s_setprio 2 / 3 (attention stays at 0)
+    PD_LIB=<lib>               round 3 ran the conv waves at s_setprio 2 / 3 (attention at 0) from a build whose compile-time base priority is gone
 Prints: alone / serial / concurrent wall times; gain = serial / concurrent.   GPU only.
     python scripts/experiments/overlap_pair.py [--reps 20] [--convs 9]"""
 import argparse, ctypes as C, os, sys, time
