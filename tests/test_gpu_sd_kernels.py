@@ -5,9 +5,22 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from guard_bands import guard_size, guarded
 from test_gpu_kernels import DT, bf16_round, env, rel, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+
+# relative L2 bounds of the parity tests below, by engine (named so that tests/test_gpu_guard_bands.py asserts the SAME numbers)
+ATTN_D64_TOL = {"f32": 5e-6, "bf16": 8e-3, "fp16": 1e-3}       # measured 7.6e-7 / 2.9e-3 / 3.7e-4
+ATTN_D64_BWD_TOL = {"f32": 3e-5, "bf16": 2.5e-2}
+ATTN_D64_LSE_TOL = {"f32": 1e-5, "bf16": 2e-3}
+ROW_OP_TOL = {"f32": 2e-6, "bf16": 4e-3, "fp16": 5e-4}         # pd_layernorm, pd_geglu, pd_linear
+TOKEN_WGRAD_TOL = {"f32": 2e-5, "bf16": 2e-3}
+LINEAR_GN_TOL = {"f32": 3e-6, "bf16": 4e-3, "fp16": 4e-3}      # GroupNorm prologue, head-major output
+LINEAR_FOLD_TOL = {"bf16": 5e-3, "fp16": 6e-4}                 # GroupNorm folded into per-sample weights; measured 2.2e-3 / 2.8e-4
+LN_BWD_TOL = {"f32": 3e-6, "bf16": 5e-3}
+LN_BWD_PARAM_TOL = 2e-5                                        # dgamma / dbeta: fp32 sums
+KMAX2_RTOL = 1e-5                                              # kmax2_out against the stored key rows: exact up to fp32 summation order
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
@@ -39,7 +52,7 @@ def test_attention_d64(env, mode, cfg):
     torch.cuda.synchronize()
     sp = lambda t, n: t.reshape(B, n, heads, 64).transpose(1, 2)
     ref = F.scaled_dot_product_attention(sp(q, Nq), sp(k, Nkv), sp(v, Nkv)).transpose(1, 2).reshape(B, Nq, Cc)
-    assert rel(out.float(), ref) < {"f32": 5e-6, "bf16": 8e-3, "fp16": 1e-3}[mode]       # measured 7.6e-7 / 2.9e-3 / 3.7e-4
+    assert rel(out.float(), ref) < ATTN_D64_TOL[mode]
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
@@ -56,7 +69,7 @@ def test_layernorm(env, mode, cfg):
     a = L.LayerNormArgs(dtype=code, rows=rows, C=Cc, eps=1e-5, x=X.data_ptr(), gamma=gm.data_ptr(), beta=bt.data_ptr(), y=y.data_ptr())
     L.check(lib.pd_layernorm(C.byref(a), stream()), "pd_layernorm")
     torch.cuda.synchronize()
-    assert rel(y.float(), F.layer_norm(x, (Cc,), gamma, beta, 1e-5)) < {"f32": 2e-6, "bf16": 4e-3, "fp16": 5e-4}[mode]
+    assert rel(y.float(), F.layer_norm(x, (Cc,), gamma, beta, 1e-5)) < ROW_OP_TOL[mode]
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
@@ -70,7 +83,7 @@ def test_geglu(env, mode):
     L.check(lib.pd_geglu(C.byref(a), stream()), "pd_geglu")
     torch.cuda.synchronize()
     h, gate = x.chunk(2, -1)
-    assert rel(y.float(), h * F.gelu(gate)) < {"f32": 2e-6, "bf16": 4e-3, "fp16": 5e-4}[mode]
+    assert rel(y.float(), h * F.gelu(gate)) < ROW_OP_TOL[mode]
 
 
 # ---- backward kernels of the Transformer2D blocks: against autograd over plain PyTorch fp32 ---------------------------------
@@ -137,7 +150,7 @@ def test_attention_d64_backward(env, mode, cfg):
     L.check(lib.pd_attn_d64(C.byref(a), stream()), "pd_attn_d64")
     # lse: log2-domain log-sum-exp of the scaled scores
     s = torch.einsum("bhid,bhjd->bhij", sp(q.detach(), Nq), sp(kv.detach()[..., :Cc], Nkv)) / 8
-    assert rel(lse.cpu(), torch.logsumexp(s, -1) * 1.4426950408889634) < (1e-5 if mode == "f32" else 2e-3)
+    assert rel(lse.cpu(), torch.logsumexp(s, -1) * 1.4426950408889634) < ATTN_D64_LSE_TOL[mode]
     dq = torch.full((B, Nq, Cc), float("nan"), dtype=tdt, device=dev)
     dkv = torch.full((B, Nkv, 2 * Cc), float("nan"), dtype=tdt, device=dev)
     delta = torch.empty((B, heads, Nq), dtype=torch.float32, device=dev)
@@ -147,7 +160,7 @@ def test_attention_d64_backward(env, mode, cfg):
                          dv=dkv.data_ptr() + Cc * esz, dkv_stride=2 * Cc)
     L.check(lib.pd_attn_d64_bwd(C.byref(b), stream()), "pd_attn_d64_bwd")
     torch.cuda.synchronize()
-    tol = 3e-5 if mode == "f32" else 2.5e-2
+    tol = ATTN_D64_BWD_TOL[mode]
     assert rel(dq.float(), q.grad) < tol, rel(dq.float(), q.grad)
     assert rel(dkv.float()[..., :Cc], kv.grad[..., :Cc]) < tol
     assert rel(dkv.float()[..., Cc:], kv.grad[..., Cc:]) < tol
@@ -180,8 +193,8 @@ def test_layernorm_backward(env, mode, cfg, with_res):
     L.check(lib.pd_layernorm_bwd(C.byref(a), stream()), "pd_layernorm_bwd")
     torch.cuda.synchronize()
     want = x.grad + (res if with_res else 0)
-    assert rel(dx.float(), want) < (3e-6 if mode == "f32" else 5e-3)
-    assert rel(dgm - 1.0, gamma.grad) < 2e-5 and rel(dbt + 2.0, beta.grad) < 2e-5
+    assert rel(dx.float(), want) < LN_BWD_TOL[mode]
+    assert rel(dgm - 1.0, gamma.grad) < LN_BWD_PARAM_TOL and rel(dbt + 2.0, beta.grad) < LN_BWD_PARAM_TOL
     # round 6: + the column sums of the stored dx (the bias gradient of the Linear layer dx is the output gradient of), C <= 1536
     if Cc <= 1536:
         part3 = torch.empty(nb * 3 * Cc, dtype=torch.float32, device=dev)
@@ -271,7 +284,7 @@ def test_linear_gemm(env, mode, cfg):
     L.check(lib.pd_linear(C.byref(a), stream()), "pd_linear")
     torch.cuda.synchronize()
     ref = F.linear(xfull[:, :K], w, bias) + (res if with_res else 0)
-    assert rel(y.float(), ref) < {"f32": 2e-6, "bf16": 4e-3, "fp16": 5e-4}[mode]
+    assert rel(y.float(), ref) < ROW_OP_TOL[mode]
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
@@ -304,7 +317,7 @@ def test_linear_gemm_fused_geglu(env, mode, cfg):
     assert not torch.isnan(wp.float()).any()
     proj = F.linear(x.double(), w.double(), bias.double())
     ref = proj[:, :inner] * F.gelu(proj[:, inner:])
-    assert rel(y.float(), ref) < {"f32": 2e-6, "bf16": 4e-3, "fp16": 5e-4}[mode]
+    assert rel(y.float(), ref) < ROW_OP_TOL[mode]
     a.N = a.N_pad = 2 * inner + 32                                             # halves that are not whole tiles: refused
     assert lib.pd_linear(C.byref(a), stream()) == -2
 
@@ -338,7 +351,7 @@ def test_token_wgrad(env, mode, cfg, accumulate):
     torch.cuda.synchronize()
     ref = dy[:, :N].double().t() @ x[:, :K].double()
     got = dw.cpu().double() - (prev.double() if accumulate else 0)
-    assert rel(got.float(), ref.float()) < (2e-5 if mode == "f32" else 2e-3)
+    assert rel(got.float(), ref.float()) < TOKEN_WGRAD_TOL[mode]
     # bitwise reproducible
     dw2 = prev.clone().to(dev) if accumulate else torch.full((N, K), float("nan"), device=dev)
     a.dw = dw2.data_ptr()
@@ -384,7 +397,7 @@ def test_linear_gemm_groupnorm_prologue_and_head_major_output(env, mode):
                      rows_per_sample=Ntok, qkv_heads=heads)
     L.check(lib.pd_linear(C.byref(a), stream()), "pd_linear")
     torch.cuda.synchronize()
-    assert rel(y.float(), ref) < (3e-6 if mode == "f32" else 4e-3)
+    assert rel(y.float(), ref) < LINEAR_GN_TOL[mode]
     kmax2 = torch.zeros(B, heads, device=dev)
     a.kmax2_out = kmax2.data_ptr()
     if mode == "f32":
@@ -394,7 +407,7 @@ def test_linear_gemm_groupnorm_prologue_and_head_major_output(env, mode):
         L.check(lib.pd_linear(C.byref(a), stream()), "pd_linear")
         torch.cuda.synchronize()
         want = (y[1].float() ** 2).sum(-1).amax(-1)
-        assert torch.allclose(kmax2, want, rtol=1e-5, atol=0)
+        assert torch.allclose(kmax2, want, rtol=KMAX2_RTOL, atol=0)
     a.kmax2_out = None
     a.rows_per_sample = 200                                                   # not a multiple of 128: refused, not mis-addressed
     assert lib.pd_linear(C.byref(a), stream()) == -2
@@ -435,9 +448,9 @@ def test_linear_gemm_groupnorm_folded_into_per_sample_weights(env, mode, shape):
         a.fold_ws, a.fold_ws_bytes = (ws.data_ptr(), need) if route == "folded" else (None, 0)
         L.check(lib.pd_linear(C.byref(a), stream()), "pd_linear")
         torch.cuda.synchronize()
-        assert rel(y.float(), ref) < (5e-3 if mode == "bf16" else 6e-4), route      # measured 2.2e-3 / 2.8e-4
+        assert rel(y.float(), ref) < LINEAR_FOLD_TOL[mode], route
         want = (y[1].float() ** 2).sum(-1).amax(-1)                           # the bound is over the key rows AS STORED
-        assert torch.allclose(kmax2, want, rtol=1e-5, atol=0), route
+        assert torch.allclose(kmax2, want, rtol=KMAX2_RTOL, atol=0), route
         outs[route] = y.float()
     assert rel(outs["folded"], outs["staged"]) < (6e-3 if mode == "bf16" else 8e-4)      # measured 2.8e-3 / 3.5e-4
     # a workspace that is too small is not used (the staged route answers), a tile that would straddle samples has no folded route
@@ -484,14 +497,16 @@ def test_linear_gemm_eight_phase(env, mode, cfg, monkeypatch):
     outs = {}
     for p8 in ("1", "0"):
         monkeypatch.setenv("PD_LIN_P8", p8)
-        y = torch.full((M + 3, N), float("nan"), dtype=tdt, device=dev)      # three guard rows: nothing may be written past M
+        # guard bands before and after y (two 256-row tiles, tests/guard_bands.py): nothing may be written past M rows, nor in front of row 0
+        y, yguard = guarded(torch.full((M, N), float("nan"), dtype=tdt), guard_size(256, N, tdt), dev, name="y")
+        yguard.canary()
         a = L.LinearArgs(dtype=code, M=M, K=K, N=N, N_pad=npad, x=X.data_ptr(), x_stride=xs, w_packed=wp.data_ptr(), bias=Bv.data_ptr(),
                          residual=L.ptr(R), y=y.data_ptr())
         L.check(lib.pd_linear(C.byref(a), stream()), "pd_linear")
         torch.cuda.synchronize()
-        assert torch.isnan(y[M:].float()).all()
-        outs[p8] = y[:M].float().cpu()
-        assert rel(outs[p8], ref.float()) < {"bf16": 4e-3, "fp16": 5e-4}[mode], p8
+        assert yguard.intact()
+        outs[p8] = y.float().cpu()
+        assert rel(outs[p8], ref.float()) < ROW_OP_TOL[mode], p8
     assert rel(outs["1"], outs["0"]) < {"bf16": 3e-3, "fp16": 4e-4}[mode]
 
 
@@ -524,7 +539,7 @@ def test_linear_gemm_eight_phase_fused_geglu(env, mode, cfg, monkeypatch):
     L.check(lib.pd_linear(C.byref(a), stream()), "pd_linear")
     torch.cuda.synchronize()
     assert torch.isnan(y[M:].float()).all()
-    assert rel(y[:M].float().cpu(), ref) < {"bf16": 4e-3, "fp16": 5e-4}[mode]
+    assert rel(y[:M].float().cpu(), ref) < ROW_OP_TOL[mode]
 
 
 def test_linear_gemm_eight_phase_is_deterministic_under_load(env, monkeypatch):
