@@ -598,6 +598,24 @@ int pd_attn_wide_bwd(const pd_attn_wide_bwd_args* a, void* stream);
 typedef struct { int B, C, HW; float scale; const float* moments; const float* noise; float* out; } pd_latent_sample_args;
 int pd_latent_sample(const pd_latent_sample_args* a, void* stream);
 
+/* pd_latent_chain_bwd: the step between the UNet's input gradient and the encoder's output gradient when the autoencoder trains
+ * (`--components_to_train autoencoder`, train.py:189-199; utils_training.py:237-256 encodes inside the step).  Backward of
+ *   z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps)  ->  noisy = sa z + sb noise  ->  loss(model_out, target(z)):
+ *   g_clean  = sa[n] * g_noisy + { epsilon: 0;  sample: -g_out;  v_prediction: sb[n] * g_out }
+ *              (the reference does not detach clean_images in the target, utils_training.py:415-433)
+ *   d mean   = scale * g_clean
+ *   d logvar = (-30 <= logvar <= 20) ? scale * g_clean * eps * 0.5 * exp(0.5 * logvar) : 0       (torch's clamp backward)
+ * g_noisy, g_out, eps: [B][C][HW] fp32 (g_out may be NULL for epsilon; eps NULL = .mode(): d logvar = 0); moments [B][2C][HW] fp32.
+ * out: [B][HW][Cpad] in `dtype`, channels [d mean | d logvar | zeros up to Cpad] -- quant_conv's NHWC output gradient.
+ * fp32 arithmetic, one cast at the store.  Any loss scale is already inside g_noisy / g_out. */
+typedef struct {
+  int dtype; int B, C, HW, Cpad; int pred_type; float scale;
+  const float* g_noisy; const float* g_out; const float* moments; const float* eps;
+  const float* sa; const float* sb;
+  void* out;
+} pd_latent_chain_bwd_args;
+int pd_latent_chain_bwd(const pd_latent_chain_bwd_args* a, void* stream);
+
 /* pd_layernorm: y[r][c] = (x[r][c] - mean_r) * rstd_r * gamma[c] + beta[c]  (nn.LayerNorm(C), biased variance) */
 typedef struct { int dtype; long long rows; int C; float eps; const void* x; const float* gamma; const float* beta; void* y; } pd_layernorm_args;
 int pd_layernorm(const pd_layernorm_args* a, void* stream);

@@ -210,6 +210,11 @@ class LatentSampleArgs(C.Structure):
     _fields_ = [("B", C.c_int), ("C", C.c_int), ("HW", C.c_int), ("scale", C.c_float), ("moments", vp), ("noise", vp), ("out", vp)]
 
 
+class LatentChainBwdArgs(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("C", C.c_int), ("HW", C.c_int), ("Cpad", C.c_int), ("pred_type", C.c_int),
+                ("scale", C.c_float), ("g_noisy", vp), ("g_out", vp), ("moments", vp), ("eps", vp), ("sa", vp), ("sb", vp), ("out", vp)]
+
+
 class LayerNormArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("rows", C.c_longlong), ("C", C.c_int), ("eps", C.c_float), ("x", vp), ("gamma", vp),
                 ("beta", vp), ("y", vp)]
@@ -335,6 +340,7 @@ SYMBOLS = {
     "pd_comm_query": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pd_comm_destroy": (C.c_int, [vp]),
     "pd_latent_sample": (C.c_int, [C.POINTER(LatentSampleArgs), vp]),
+    "pd_latent_chain_bwd": (C.c_int, [C.POINTER(LatentChainBwdArgs), vp]),
     "pd_attn_d64_bwd": (C.c_int, [C.POINTER(AttnD64BwdArgs), vp]),
     "pd_layernorm_bwd": (C.c_int, [C.POINTER(LayerNormBwdArgs), vp]),
     "pd_layernorm_bwd_blocks": (C.c_int, [C.c_longlong]),

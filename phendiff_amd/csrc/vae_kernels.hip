@@ -403,6 +403,41 @@ __global__ __launch_bounds__(256) void latent_sample_kernel(const pd_latent_samp
   }
 }
 
+// Backward of the latent chain (pd_latent_sample -> pd_add_noise -> pd_diffusion_loss's target) down to quant_conv's output:
+// one thread per (pixel, 8-channel piece) of the NHWC gradient [d mean | d logvar | 0 ...]; fp32 throughout, one cast at the store.
+template <typename T>
+__global__ __launch_bounds__(256) void latent_chain_bwd_kernel(const pd_latent_chain_bwd_args a) {
+  const int PP = a.Cpad / 8;
+  const size_t total = (size_t)a.B * a.HW * PP;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const int sub = (int)(idx % PP);
+    const size_t pix = idx / PP;
+    const int n = (int)(pix / a.HW), p = (int)(pix % a.HW);
+    const float sa = a.sa[n], sb = a.sb[n];
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = sub * 8 + j;
+      float r = 0.f;
+      if (c < 2 * a.C) {
+        const int cc = c < a.C ? c : c - a.C;
+        const size_t li = ((size_t)n * a.C + cc) * a.HW + p;
+        float g = sa * a.g_noisy[li];
+        if (a.pred_type == 1) g -= a.g_out[li];
+        else if (a.pred_type == 2) g += sb * a.g_out[li];
+        g *= a.scale;
+        if (c < a.C) r = g;
+        else if (a.eps) {
+          const float logvar = a.moments[((size_t)n * 2 * a.C + c) * a.HW + p];
+          if (logvar >= -30.0f && logvar <= 20.0f) r = g * a.eps[li] * 0.5f * expf(0.5f * logvar);
+        }
+      }
+      v[j] = r;
+    }
+    Elem<T>::store((T*)a.out + pix * a.Cpad + sub * 8, Elem<T>::pack(v));
+  }
+}
+
 // GroupNorm apply (+ SiLU) as its own pass: y[n][p][c] = silu?(x[n][p][c] * scale[n][c] + shift[n][c]) over the channel concat
 // [x0 | x1].  pd_conv applies this transform while staging, once per 64-channel OUTPUT tile: with Cout = 1280 the same halo
 // tile is transformed 20 times and the exp/rcp issue slots, not the MFMAs, pace the convolution.  Wide layers therefore read
@@ -455,6 +490,22 @@ extern "C" int pd_latent_sample(const pd_latent_sample_args* a, void* stream) {
   const int64_t total = (int64_t)a->B * a->C * a->HW;
   const unsigned grid = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(latent_sample_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+extern "C" int pd_latent_chain_bwd(const pd_latent_chain_bwd_args* a, void* stream) {
+  PD_CHECK(a != nullptr && a->B > 0 && a->C > 0 && a->HW > 0, PD_ERR_SHAPE, "pd_latent_chain_bwd: bad shape");
+  PD_CHECK(a->Cpad % 8 == 0 && a->Cpad >= 2 * a->C, PD_ERR_SHAPE, "pd_latent_chain_bwd: Cpad=%d must be a multiple of 8 and hold 2 C=%d channels",
+           a->Cpad, 2 * a->C);
+  PD_CHECK(a->pred_type >= 0 && a->pred_type <= 2, PD_ERR_ARG, "pd_latent_chain_bwd: pred_type %d", a->pred_type);
+  PD_CHECK(a->g_noisy && a->moments && a->sa && a->sb && a->out && (a->pred_type == 0 || a->g_out), PD_ERR_ARG, "pd_latent_chain_bwd: null pointer");
+  const size_t total = (size_t)a->B * a->HW * (a->Cpad / 8);
+  const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  if (a->dtype == PD_F32) hipLaunchKernelGGL(latent_chain_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+  else if (a->dtype == PD_BF16) hipLaunchKernelGGL(latent_chain_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+  else if (a->dtype == PD_F16) hipLaunchKernelGGL(latent_chain_bwd_kernel<half_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+  else { set_error("pd_latent_chain_bwd: bad dtype"); return PD_ERR_ARG; }
   PD_LAUNCH_CHECK();
   return PD_OK;
 }

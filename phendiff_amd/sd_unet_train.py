@@ -282,6 +282,62 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         return self.param_grads and EMB_NAME in self.grads and EMB_NAME not in self.frozen
 
 
+def sd_training_layout(model, class_embedding, vae=None, train_class_embedding: bool = True, trainable=None):
+    """(order, flags, never_graded, vae_trains) of an :class:`SDUNetTrainer`'s flat buffers -- pure host logic.
+
+    ``order``: (name, parameter) pairs.  With a training autoencoder the order follows the reference's ``params_to_optimize``
+    (train.py:268-272), which walks the pipeline's components in the order of its constructor (vae, unet, class_embedding;
+    custom_pipeline_stable_diffusion_img2img.py:62-68): the VAE's parameters (names prefixed ``vae.``) come first, then the UNet's,
+    the class table stays the tail.  ``flags``: what ``requires_grad`` / ``trainable`` say.  ``never_graded``: trainable names the
+    loss never reaches (``vae.decoder.*``, ``vae.post_quant_conv.*``): ``torch.optim.AdamW`` skips them (``grad is None``).
+    A VAE none of whose parameters trains (``pipeline.vae.requires_grad_(False)``, train.py:189-191) stays out of the buffers."""
+    from .training import resolve_trainable
+    from .vae_train import VAE_PREFIX, vae_never_graded, vae_training_param_order
+    uorder = sd_training_param_order(model)
+    emb = [(EMB_NAME, class_embedding.inner_module.weight)] if train_class_embedding else []
+    vorder = [(VAE_PREFIX + n, p) for n, p in vae_training_param_order(vae)] if vae is not None else []
+    if trainable is not None:
+        flags = resolve_trainable(vorder + uorder + emb, None, trainable)
+        vflags, rest = flags[:len(vorder)], flags[len(vorder):]
+    else:
+        vflags = resolve_trainable(vorder, vae) if vorder else []
+        rest = resolve_trainable(uorder, model) + (resolve_trainable(emb, class_embedding) if emb else [])
+    if not any(vflags):
+        return uorder + emb, rest, frozenset(), False
+    skip = {VAE_PREFIX + n for n in vae_never_graded(vae)}
+    never = frozenset(n for (n, _), f in zip(vorder, vflags) if f and n in skip)
+    if not any(f and n not in skip for (n, _), f in zip(vorder, vflags)):
+        raise ValueError("SDUNetTrainer: the trainable autoencoder parameters (decoder / post_quant_conv) never receive a gradient")
+    return vorder + uorder + emb, vflags + rest, never, True
+
+
+def sd_checkpoint_modules(model, class_embedding, vae, names):
+    """accelerate's numbering of the prepared models (train.py:318-326): unet 0, vae 1, class embedding 2, as
+    [(file index, module, flat-name prefix)] in the order of the optimizer's parameter list (vae, unet, class embedding)."""
+    from .vae_train import VAE_PREFIX
+    mods = []
+    if vae is not None and any(n.startswith(VAE_PREFIX) for n in names):
+        mods.append((1, vae, VAE_PREFIX))
+    mods.append((0, model, ""))
+    if EMB_NAME in names:
+        mods.append((2, class_embedding, "class_embedding."))
+    return mods
+
+
+def check_training_images(vae, images):
+    """Argument guards of :meth:`SDUNetTrainer.step_images`."""
+    if vae is None:
+        raise ValueError("step_images needs the autoencoder: build the trainer with SDUNetTrainer(..., vae=pipeline.vae)")
+    c = vae.config
+    if images.ndim != 4 or images.shape[1] != c.in_channels:
+        raise ValueError(f"step_images: expected images (B, {c.in_channels}, H, W), got {tuple(images.shape)}")
+    s = 1 << (len(c.block_out_channels) - 1)
+    if images.shape[2] % s or images.shape[3] % s:
+        raise ValueError(f"step_images: image size {tuple(images.shape[2:])} must be a multiple of {s}")
+    if not images.is_cuda:
+        raise L.PhenDiffHipError("phendiff_amd trains on MI355X only (no CPU fallback): move the images to 'cuda'")
+
+
 class _SDRepacker:
     """After an optimizer step: fp32 master parameters -> every kernel-layout copy the plans read, IN PLACE
     (``pd_pack_weight`` launches + a few small fp32 copies).  fp32 vectors the kernels read directly (norm affines, biases)
@@ -393,26 +449,27 @@ class SDUNetTrainer(UNetTrainer):
 
     def __init__(self, model: SDUNet2DConditionModel, class_embedding: CustomEmbedding, scheduler, lr: float, *, device=None,
                  train_class_embedding: bool = True, use_ema: bool = True, max_grad_norm: Optional[float] = 1.0, group=None,
-                 trainable=None, **adamw):
-        """``trainable``: as for :class:`UNetTrainer` (names carry ``EMB_NAME`` for the class table); default: the ``requires_grad``
-        flags of the UNet's parameters decide for the UNet (``components_to_train`` / ``--attention_fine_tuning``, train.py:189-220),
-        ``train_class_embedding`` and the table's own flag for the ``CustomEmbedding``."""
-        from .training import DiffusionLoss, FlatAdamWEMA, broadcast_from_rank0_, resolve_trainable
-        self.model, self.class_embedding, self.scheduler = model, class_embedding, scheduler
+                 trainable=None, vae=None, _vae_chunk: Optional[int] = None, **adamw):
+        """``trainable``: as for :class:`UNetTrainer` (names carry ``EMB_NAME`` for the class table, the ``vae.`` prefix for the
+        autoencoder); default: the ``requires_grad`` flags of the UNet's parameters decide for the UNet (``components_to_train`` /
+        ``--attention_fine_tuning``, train.py:189-220), ``train_class_embedding`` and the table's own flag for the ``CustomEmbedding``.
+        ``vae``: the pipeline's :class:`phendiff_amd.vae.AutoencoderKL` (``components_to_train autoencoder``): it trains when at
+        least one of its parameters does (:func:`sd_training_layout`); :meth:`step_images` then encodes inside the step and sends
+        the loss gradient back through ``quant_conv`` and the encoder.  ``_vae_chunk``: tests force the encoder's chunk size."""
+        from .training import DiffusionLoss, FlatAdamWEMA, broadcast_from_rank0_
+        self.model, self.class_embedding, self.scheduler, self.vae = model, class_embedding, scheduler, vae
         dev = device or model.device
         if torch.device(dev).type != "cuda":
             raise L.PhenDiffHipError("phendiff_amd trains on MI355X only (no CPU fallback): move the model to 'cuda'")
-        order = sd_training_param_order(model)
-        if trainable is None:
-            flags = resolve_trainable(order, model)
-            if train_class_embedding:
-                flags = flags + resolve_trainable([(EMB_NAME, class_embedding.inner_module.weight)], class_embedding)
-        if train_class_embedding:
-            order = order + [(EMB_NAME, class_embedding.inner_module.weight)]
-        if trainable is not None:
-            flags = resolve_trainable(order, None, trainable)
+        order, flags, never, self._vae_trains = sd_training_layout(model, class_embedding, vae, train_class_embedding, trainable)
         if not any(flags):
             raise ValueError("SDUNetTrainer: no trainable parameter (every parameter is frozen)")
+        if self._vae_trains and torch.device(vae.device) != torch.device(dev):
+            raise L.PhenDiffHipError("SDUNetTrainer: the autoencoder must live on the UNet's device")
+        # parameters the loss never reaches get what torch.optim.AdamW gives `grad is None`: no update, no decay, no moments -- the
+        # optimizer treats them as frozen (their EMA shadow is the parameter itself), and so do the all-reduce buckets
+        self.trainable_flags, self.never_graded, self._vae_chunk = list(flags), never, _vae_chunk
+        flags = [f and n not in never for (n, _), f in zip(order, flags)]
         self.frozen = frozenset(n for (n, _), f in zip(order, flags) if not f)
         self.opt = FlatAdamWEMA([p for _, p in order], lr, use_ema=use_ema, max_grad_norm=max_grad_norm, **adamw)
         self.opt.set_trainable(flags)
@@ -425,6 +482,16 @@ class SDUNetTrainer(UNetTrainer):
         self.params = {n: p.data for n, p in order}
         self.grads = {n: p.grad for n, p in order}
         model.invalidate()
+        if self._vae_trains:
+            if vae.compute_dtype != model.compute_dtype:
+                raise ValueError("SDUNetTrainer: the autoencoder and the UNet must share one compute_dtype")
+            from .vae_train import VAE_PREFIX
+            k = len(VAE_PREFIX)
+            self._vparams = {n[k:]: t for n, t in self.params.items() if n.startswith(VAE_PREFIX)}
+            self._vgrads = {n[k:]: t for n, t in self.grads.items() if n.startswith(VAE_PREFIX)}
+            self._vfrozen = frozenset(n[k:] for n in self.frozen if n.startswith(VAE_PREFIX))
+            vae.invalidate()
+        self._vplans, self._vtw, self._vrepack, self._bound_vw = {}, None, None, None
         self.loss_fn = DiffusionLoss(scheduler, dev)
         if getattr(model, "compute_dtype", None) == "fp16":      # --mixed_precision fp16: accelerate's GradScaler (training.LossScaler)
             from .training import LossScaler
@@ -436,12 +503,9 @@ class SDUNetTrainer(UNetTrainer):
         self._uncond = False
 
     def checkpoint_modules(self):
-        """accelerate's numbering of the prepared models (train.py:318-326): unet 0, vae 1 (frozen, not the trainer's), class
-        embedding 2 -- flat names of the embedding carry the ``class_embedding.`` prefix."""
-        mods = [(0, self.model, "")]
-        if EMB_NAME in self.params:
-            mods.append((2, self.class_embedding, "class_embedding."))
-        return mods
+        """accelerate's numbering of the prepared models (train.py:318-326): unet 0, vae 1 (only when it trains: a frozen one is not
+        the trainer's), class embedding 2 -- flat names carry the ``vae.`` / ``class_embedding.`` prefixes."""
+        return sd_checkpoint_modules(self.model, self.class_embedding, getattr(self, "vae", None), self.params)
 
     def _optimizer_step(self, lr):
         # an unconditional step leaves the CustomEmbedding without a gradient: torch's AdamW skips it (EMA still steps)
@@ -458,7 +522,8 @@ class SDUNetTrainer(UNetTrainer):
 
     def _make_plan(self, key):
         m = self.model
-        return SDUNetTrainPlan(m, m._weights, self._tw, *key, self.device, self.params, self.grads, frozen=self.frozen)
+        return SDUNetTrainPlan(m, m._weights, self._tw, *key, self.device, self.params, self.grads, frozen=self.frozen,
+                               input_grad=getattr(self, "_vae_trains", False))      # d loss / d noisy latents feeds the encoder's backward
 
     def plan_for(self, B, H, W, tokens=77):
         self._bind_weights()
@@ -496,6 +561,132 @@ class SDUNetTrainer(UNetTrainer):
     def step(self, noisy, timesteps, clean, noise, class_labels, unconditional: bool = False, lr: Optional[float] = None,
              group=None, overlap: bool = True, bucket_bytes: int = 64 << 20):
         """3.46 GB of fp32 gradients per step: 64 MB buckets (xGMI rings are per-link bound: few, large messages)."""
+        if getattr(self, "_vae_trains", False):
+            raise ValueError("SDUNetTrainer: the autoencoder trains -- the step starts from images (step_images), not from latents")
         self._uncond = bool(unconditional)
         return super().step(noisy, timesteps, clean, noise, class_labels=class_labels, class_emb=None, lr=lr, group=group,
                             overlap=overlap, bucket_bytes=bucket_bytes)
+
+    # ---- components_to_train autoencoder: the step starts from images --------------------------------------------------------
+    def _bind_vae_weights(self):
+        """The VAE's kernel-layout weights the trainer's encoder plans, gradient-layout set and re-packer are bound to: rebuilt
+        when the model dropped them (``vae.to()`` / ``load_state_dict`` -> ``invalidate``)."""
+        from .vae import _VaeWeights
+        from .vae_train import VaeTrainWeights
+        vae = self.vae
+        if vae._weights is not None and vae._weights is self._bound_vw:
+            return
+        for n, p in vae.named_parameters():
+            if p.data_ptr() != self._vparams[n].data_ptr():
+                raise L.PhenDiffHipError(f"parameter vae.{n} no longer aliases the trainer's flat buffer (the autoencoder was converted "
+                                         "or moved after the trainer was built): build a new trainer")
+        if vae._weights is None:
+            vae._weights = _VaeWeights(vae, self.device)
+        self._vtw = VaeTrainWeights(vae, self.device, vae._weights.tdt)
+        self._vrepack, self._vplans, self._bound_vw = None, {}, vae._weights
+
+    def vae_plan_for(self, B, H, W, slot=0):
+        """The encoder's training plan of chunk ``slot`` (every chunk of a step keeps its own activations until its backward)."""
+        from .vae_train import VaeEncodeTrainPlan
+        self._bind_vae_weights()
+        key = (B, H, W, slot)
+        p = self._vplans.get(key)
+        if p is None:
+            p = VaeEncodeTrainPlan(self.vae, self.vae._weights, self._vtw, B, H, W, self.device, self._vparams, self._vgrads,
+                                   frozen=self._vfrozen)
+            self._vplans[key] = p
+        return p
+
+    def refresh_weights(self):
+        super().refresh_weights()
+        if getattr(self, "_vae_trains", False) and not (self.vae._weights is None and self._bound_vw is None):
+            from .vae_train import _VaeRepacker
+            self._bind_vae_weights()
+            if self._vrepack is None:
+                self._vrepack = _VaeRepacker(self.vae, self.vae._weights, self._vtw)
+            self._vrepack.run(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _coefficients(self, timesteps):
+        """sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t) per sample: the host-computed fp32 tables ``DDIMScheduler.add_noise`` gathers from."""
+        idx = timesteps.detach().to(device=self.device, dtype=torch.long)
+        if self.loss_fn.tables[0].device != idx.device:
+            self.loss_fn.tables = tuple(t.to(idx.device) for t in self.loss_fn.tables)
+        return self.loss_fn.tables[1][idx].contiguous(), self.loss_fn.tables[2][idx].contiguous()
+
+    def images_forward_backward(self, images, timesteps, noise, class_labels, posterior_noise=None, unconditional=None):
+        """Loss of one image batch and the gradients of every trained component (accumulated into the flat gradient buffer):
+        encode (train plan) -> ``pd_latent_sample`` -> ``pd_add_noise`` -> UNet forward -> ``pd_diffusion_loss`` -> UNet backward
+        with the input gradient -> ``pd_latent_chain_bwd`` -> encoder backward.  Returns (loss, latents)."""
+        from .vae import DiagonalGaussianDistribution
+        from .vae_train import latent_chain_bwd
+        if unconditional is None:
+            unconditional = getattr(self, "_uncond", False)
+        vae, c = self.vae, self.vae.config
+        B, _, H, W = images.shape
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        x = images.contiguous().float()
+        nlev = len(c.block_out_channels)
+        h, w, lat = H >> (nlev - 1), W >> (nlev - 1), c.latent_channels
+        sf = float(c.scaling_factor)
+        chunk = self._vae_chunk or vae._max_batch(H, W, "enc")      # pd_conv's 2 GiB source-offset limit holds for training too
+        moments = torch.empty((B, 2 * lat, h, w), dtype=torch.float32, device=self.device)
+        chunks = [(b0, min(chunk, B - b0)) for b0 in range(0, B, chunk)]
+        vplans = []
+        for slot, (b0, nb) in enumerate(chunks):
+            vp = self.vae_plan_for(nb, H, W, slot)
+            vp.forward(x[b0:b0 + nb], moments[b0:b0 + nb], st)
+            vplans.append(vp)
+        if posterior_noise is None:
+            posterior_noise = torch.randn((B, lat, h, w), dtype=torch.float32, device=self.device)      # randn_tensor on the device
+        pn = posterior_noise.to(device=self.device, dtype=torch.float32).contiguous()
+        latents = DiagonalGaussianDistribution(moments).sample(noise=pn, scale=sf)
+        nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
+        sa, sb = self._coefficients(timesteps)
+        noisy = torch.empty_like(latents)
+        a = L.AddNoiseArgs(numel=latents.numel(), per_sample=latents[0].numel(), velocity=0, x=latents.data_ptr(), noise=nz.data_ptr(),
+                           sa=sa.data_ptr(), sb=sb.data_ptr(), out=noisy.data_ptr())
+        L.check(L.lib().pd_add_noise(C.byref(a), st), "pd_add_noise")
+        plan = self.plan_for(B, h, w)
+        ts = timesteps.to(device=self.device, dtype=torch.float32).contiguous()
+        labels = class_labels.to(device=self.device, dtype=torch.int64).contiguous()
+        ehs = self.encoder_hidden_states(labels, unconditional)
+        out = torch.empty_like(noisy)
+        plan.forward(noisy, ts, ehs, out, st, labels=None if unconditional else labels)
+        loss, dout = self.loss_fn(out, latents, nz, timesteps, grad_scale=self.opt.scaler.scale if self.opt.scaler is not None else 1.0)
+        plan.backward(dout, st)
+        pt = self.scheduler.config.prediction_type
+        for vp, (b0, nb) in zip(vplans, chunks):
+            sl = slice(b0, b0 + nb)
+            latent_chain_bwd(plan.dsample[sl], dout[sl], moments[sl], pn[sl], sa[sl], sb[sl], pt, sf, vp.dmom, vp.code, st)
+            vp.backward(vp.dmom, st)      # weight gradients accumulate across the chunks
+        self._keep_images = (x, moments, pn, nz, latents, noisy, out, dout, sa, sb, ts, labels, ehs)
+        return loss, latents
+
+    def step_images(self, images, timesteps, noise, class_labels, posterior_noise=None, unconditional: bool = False,
+                    lr: Optional[float] = None, group=None, overlap: bool = True, bucket_bytes: int = 64 << 20):
+        """One optimisation step from IMAGES (``utils_training.py:237-256``: the batch is encoded inside the step): with a training
+        autoencoder, :meth:`images_forward_backward`, then the bucketed gradient all-reduce over the trainable runs of the flat buffer
+        (VAE segments included; never-graded ones, like frozen ones, are not exchanged), the joint clip over all trained parameters,
+        AdamW + EMA and the in-place re-pack of the UNet's and the encoder's kernel-layout weights.  With a frozen autoencoder
+        (``pipeline.vae.requires_grad_(False)``): encode -> sample -> add_noise -> :meth:`step`, i.e. today's step.
+        ``noise`` / ``posterior_noise``: (B, latent, H/8, W/8); the posterior noise is drawn on the device when None."""
+        check_training_images(getattr(self, "vae", None), images)
+        vae = self.vae
+        if not self._vae_trains:
+            sf = float(vae.config.scaling_factor)
+            latents = vae.encode(images).latent_dist.sample(noise=posterior_noise, scale=sf)
+            nz = noise.to(device=latents.device, dtype=torch.float32)
+            noisy = self.scheduler.add_noise(latents, nz, timesteps)
+            return self.step(noisy, timesteps, latents, nz, class_labels, unconditional=unconditional, lr=lr, group=group,
+                             overlap=overlap, bucket_bytes=bucket_bytes)
+        import torch.distributed as dist
+        self._uncond = bool(unconditional)
+        loss, _ = self.images_forward_backward(images, timesteps, noise, class_labels, posterior_noise)
+        world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+        if world > 1 or getattr(self, "force_collectives", False):
+            # the buckets are exchanged once both backward plans have run (the overlapped schedule of `step` follows ONE plan's launches)
+            from .training import allreduce_mean_ranges_
+            allreduce_mean_ranges_(self.opt.grad, self.opt.trainable_ranges(), group, bucket_bytes=bucket_bytes)
+        self._optimizer_step(lr)
+        self.refresh_weights()
+        return loss

@@ -147,7 +147,7 @@ class UNetTrainPlan(UNetPlan):
         self.dsample = self._f32(B, m.config.in_channels, H, W) if input_grad else None
         if self.param_grads:
             self._check_layout()
-        c0, tdim = m.config.block_out_channels[0], m.time_embed_dim
+        c0, tdim = m.config.block_out_channels[0], getattr(m, "time_embed_dim", 0)      # (0: no time embedding -- the VAE encoder's plan)
         self.t_feat, self.t_z1, self.t_emb = self._f32(B, c0), self._f32(B, tdim), self._f32(B, tdim)
         if self._class_mlp:
             self.c_feat, self.c_z1, self.c_emb, self.c_scratch = self._f32(B, c0), self._f32(B, tdim), self._f32(B, tdim), self._f32(B, w.proj_dim)
@@ -584,7 +584,7 @@ class UNetTrainPlan(UNetPlan):
         # gradient [d scale | d shift] comes out of the GroupNorm backward (pd_gn_bwd_args.mod / dmod) instead of conv1's epilogue
         self._gn_bwd(rec.gn2, dz2, 1, wname=n + ".norm2", mod_off=e.temb_off if ss else None)
         dh1 = self._g(rec.h1)[0]
-        if ss:
+        if ss or e.temb_off is None:        # (None: a ResNet block without a time embedding -- the VAE's)
             self._bias_grad(dh1, G(n + ".conv1.bias"))
         else:
             # d time_emb_proj output [n][co] = sum over pixels of d h1 (the projection is broadcast over the pixels)

@@ -343,7 +343,7 @@ class _VaePlan(UNetPlan):
         self.m, self.w = m, w
         self.B, self.H, self.W, self.device = B, H, W, device      # H, W: spatial size of the plan's INPUT tensor
         self.code, self.tdt = w.code, w.tdt
-        self.train = False
+        self.train = bool(getattr(self, "train", False))      # set by VaeEncodeTrainPlan before the forward is laid out
         self.tape, self.gn_saved, self.ops, self.bufs, self.stats = [], {}, [], [], {}
         self.groups = m.config.norm_num_groups
         self._temb_ptr_fields = []
@@ -377,16 +377,22 @@ class VaeEncodePlan(_VaePlan):
                                       src_shape=(B, H, W, 32))
         self.ops[-1].what = "conv_in"
         self.ops[-1].flops = 2.0 * B * H * W * boc[0] * c.in_channels * 9
+        rec = self.tape.append if self.train else (lambda r: None)      # the records VaeEncodeTrainPlan's backward walks (beside _resnet's / _attn_nhwc's)
+        rec(SimpleNamespace(kind="vae_conv_in", out=h))
         for i, blk in enumerate(m.encoder.down_blocks):
             for j in range(len(blk.resnets)):
                 h = self._resnet(f"encoder.down_blocks.{i}.resnets.{j}", h)
             if blk.downsamplers is not None:
-                s = w.samplers[f"encoder.down_blocks.{i}.downsamplers.0"]
-                h, _ = self._conv(h, None, s.w, s.b, h.shape[3], stride=2, pad=0)
+                name = f"encoder.down_blocks.{i}.downsamplers.0"
+                s = w.samplers[name]
+                hd, _ = self._conv(h, None, s.w, s.b, h.shape[3], stride=2, pad=0)
+                rec(SimpleNamespace(kind="down", name=name, x=h, out=hd, e=s))
+                h = hd
         h = self._mid("encoder", h)
         g, be, eps = w.enc_gn
         gn = self._gn(h, None, g, be, eps)
         z, _ = self._conv(h, None, w.enc_out_w, w.enc_out_b, 32, silu=1, gn=gn, stats=False)
+        rec(SimpleNamespace(kind="vae_out", x=h, gn=gn, z=z))
         _, self._out_args = self._conv(z, None, w.quant_w, w.quant_b, 2 * c.latent_channels, ksize=1, pad=0,
                                        out_mode=L.PD_OUT_NCHW_F32, cout_pad=32, y=None)
 
