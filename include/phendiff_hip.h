@@ -35,7 +35,8 @@ extern "C" {
  * pd_attn_d8_bwd_workspace (the one-pass backward); 7 = round 6: pd_gn_bwd_args.mod / mod_stride / dmod (scale_shift ResNet blocks train);
  * pd_resize_tf1, pd_conv_rect, pd_pool2d, pd_fc_f32 (the evaluation metrics' feature extractor); pd_pack_weight_args.dst2 / dst2_ct_stride;
  * 8 = pd_geglu_bwd_args.sums / sum_splits / B, pd_layernorm_bwd_args.dxsum (bias gradients without a pass over dY), pd_upsample_phase_weights,
- * pd_token_wgrad_args.stage / pd_wgrad_args.stage. */
+ * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
+ * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess. */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -734,6 +735,36 @@ typedef struct { int dtype; int B, Hin, Win, C, Hout, Wout, k, stride, pad, mode
 int pd_pool2d(const pd_pool2d_args* a, void* stream);
 typedef struct { int rows, in_dim, out_dim; const float* x; const float* wt; const float* bias; float* y; } pd_fc_f32_args;
 int pd_fc_f32(const pd_fc_f32_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_image_preprocess (added under ABI 8): decoded uint8 images -> the float32 NCHW tensor in [-1, 1] every entry point of the engine starts from.
+ * Replaces the per-image host transforms of src/utils_dataset.py:104-127 (Resize(BILINEAR) -> ToTensor -> Normalize [-> RandomHorizontalFlip
+ * -> RandomVerticalFlip], and the uint8 "raw" twin Resize -> PILToTensor) and of src/utils_Img2Img.py:197-206.  csrc/data_kernels.hip; host
+ * side phendiff_amd/data.py (resample_tables builds the tables).  The resize is Pillow's 8-bit bilinear resample bit for bit: separable,
+ * 22-bit fixed-point coefficients, horizontal pass first into uint8, then the vertical pass; an axis whose size does not change is skipped.
+ *   x: N images of H x W pixels, uint8, channels interleaved; byte strides image_stride / row_stride / pixel_stride (row_stride >=
+ *      W * pixel_stride, image_stride >= the extent of one image).  Cin = 1 | 3 channels are read from every pixel (pixel_stride >= Cin, so
+ *      pixel_stride 4 with Cin 3 reads RGBA and drops alpha); one channel is replicated to three (PIL convert("RGB") of mode L).
+ *   coef_x int32 [OW][ksize_x], bounds_x int32 [OW][2] = (first source column, count <= ksize_x): the horizontal tables; coef_y [OH][ksize_y],
+ *      bounds_y [OH][2] the vertical ones.  ksize = 2 * ceil(max(in / out, 1)) + 1 (checked).  The tables of an axis with in == out are not
+ *      read (may be null).  per output: acc = 1 << 21; acc += src[first + k] * coef[k]; out = clamp(acc >> 22, 0, 255).
+ *   out_index int32 [N] (null: image n -> slot n): the output slot of each image, 0 <= slot < out_slots (an image whose slot is out of range is
+ *      not written) -- a list of mixed source sizes fills one batch in several launches.
+ *   y_u8 (may be null): uint8 NHWC [out_slots][OH][OW][3], the resized bytes (never flipped).
+ *   y_f32 (may be null): float32 NCHW [out_slots][3][OH][OW] = ((float)u8 / 255.f - mean_c) / std_c (IEEE division, no contraction), written
+ *      mirrored per flips[n] (uint8 [N], null = none): bit 0 horizontal, bit 1 vertical.
+ * Refused (PD_ERR_SHAPE): a down-scale factor above 32 on an axis; source or output arrays of 4 GiB or more per launch. */
+typedef struct {
+  int N, H, W, Cin, OH, OW, out_slots;
+  long long image_stride, row_stride; int pixel_stride;
+  int ksize_x, ksize_y;
+  const unsigned char* x;
+  const int* coef_x; const int* bounds_x; const int* coef_y; const int* bounds_y;
+  const int* out_index; const unsigned char* flips;
+  float mean0, mean1, mean2, std0, std1, std2;
+  float* y_f32; unsigned char* y_u8;
+} pd_image_preprocess_args;
+int pd_image_preprocess(const pd_image_preprocess_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_comm_*: the data-parallel gradient exchange -- DistributedDataParallel's bucketed all-reduce under accelerator.backward(loss)

@@ -26,3 +26,5 @@ from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline, hack_class_embedd
 from .sd_unet_train import SDUNetTrainer, SDUNetTrainPlan, sd_training_param_order, sd_training_layout  # noqa: F401
 from .vae_train import VaeEncodeTrainPlan, vae_training_param_order  # noqa: F401
 from . import metrics  # noqa: F401,E402  (FID / IS / KID: InceptionV3Features, calculate_metrics, class_metrics_hook)
+from . import data  # noqa: F401,E402  (uint8 images -> the engine's input: ImagePreprocessor, resample_tables, draw_flips)
+from .data import ImagePreprocessor  # noqa: F401,E402

@@ -296,6 +296,14 @@ class FcF32Args(C.Structure):
     _fields_ = [("rows", C.c_int), ("in_dim", C.c_int), ("out_dim", C.c_int), ("x", vp), ("wt", vp), ("bias", vp), ("y", vp)]
 
 
+class ImagePreprocessArgs(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("OH", C.c_int), ("OW", C.c_int),
+                ("out_slots", C.c_int), ("image_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_int),
+                ("ksize_x", C.c_int), ("ksize_y", C.c_int), ("x", vp), ("coef_x", vp), ("bounds_x", vp), ("coef_y", vp),
+                ("bounds_y", vp), ("out_index", vp), ("flips", vp), ("mean0", C.c_float), ("mean1", C.c_float), ("mean2", C.c_float),
+                ("std0", C.c_float), ("std1", C.c_float), ("std2", C.c_float), ("y_f32", vp), ("y_u8", vp)]
+
+
 # every symbol include/phendiff_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pd_abi_version": (C.c_int, []),
@@ -357,6 +365,7 @@ SYMBOLS = {
     "pd_conv_rect": (C.c_int, [C.POINTER(ConvRectArgs), vp]),
     "pd_pool2d": (C.c_int, [C.POINTER(Pool2dArgs), vp]),
     "pd_fc_f32": (C.c_int, [C.POINTER(FcF32Args), vp]),
+    "pd_image_preprocess": (C.c_int, [C.POINTER(ImagePreprocessArgs), vp]),
     "pd_graph_begin": (C.c_int, [vp]),
     "pd_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
     "pd_graph_launch": (C.c_int, [vp, vp]),
