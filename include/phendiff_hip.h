@@ -577,6 +577,24 @@ typedef struct {
 } pd_attn_wide_args;
 int pd_attn_wide(const pd_attn_wide_args* a, void* stream);
 
+/* pd_attn_hd: softmax(q k^T * scale) v per (batch, head) for the head dimensions of the Stable-Diffusion 1.x denoisers,
+ * D in {40, 80, 160} (attention_head_dim = 8: eight heads on 320 / 640 / 1280 channels; BasicTransformerBlock.attn1 / .attn2 of
+ * the CompVis/stable-diffusion-v1-* and runwayml/stable-diffusion-v1-5 UNets that custom_pipeline_stable_diffusion_img2img.py:108-130
+ * names).  Operand addressing as pd_attn_d64 (token-major with element strides, multiples of 8; channel = head*D + d), so q/k/v may
+ * be slices of one fused projection output.  scale = D^-1/2 for diffusers' Attention.  Any other D: PD_ERR_SHAPE.  D is padded to
+ * the MFMA step in LDS / registers only, with zeros; nothing beyond a head's D channels or a sample's Nkv rows is used.
+ * No backward yet: lse is what it will recompute P from. */
+typedef struct {
+  int dtype;
+  int B, heads, D, Nq, Nkv;
+  float scale;
+  const void* q; int q_stride;
+  const void* k; const void* v; int kv_stride;
+  void* out; int out_stride;
+  float* lse;   /* optional out [B][heads][Nq]: log2-domain log-sum-exp of the scaled scores (as pd_attn_d64_args.lse), or NULL */
+} pd_attn_hd_args;
+int pd_attn_hd(const pd_attn_hd_args* a, void* stream);
+
 /* pd_attn_wide_bwd: gradient of pd_attn_wide (autograd of F.scaled_dot_product_attention, one wide head per D channels): what
  * accelerator.backward(loss) (utils_training.py:436) runs for the attention blocks of orig_google_ddpm_model_denoiser.json
  * (attention_head_dim null -> one 512-channel head, cond_unet_2d.py:176-197).  P is recomputed from the forward's lse.

@@ -170,6 +170,12 @@ class AttnWideArgs(C.Structure):
                 ("out_stride", C.c_int), ("lse", vp)]
 
 
+class AttnHdArgs(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("heads", C.c_int), ("D", C.c_int), ("Nq", C.c_int), ("Nkv", C.c_int),
+                ("scale", C.c_float), ("q", vp), ("q_stride", C.c_int), ("k", vp), ("v", vp), ("kv_stride", C.c_int), ("out", vp),
+                ("out_stride", C.c_int), ("lse", vp)]
+
+
 class CommId(C.Structure):
     _fields_ = [("bytes", C.c_char * 128)]
 
@@ -341,6 +347,7 @@ SYMBOLS = {
     "pd_linear": (C.c_int, [C.POINTER(LinearArgs), vp]),
     "pd_linear_fold_workspace": (C.c_size_t, [C.POINTER(LinearArgs)]),
     "pd_attn_wide": (C.c_int, [C.POINTER(AttnWideArgs), vp]),
+    "pd_attn_hd": (C.c_int, [C.POINTER(AttnHdArgs), vp]),
     "pd_attn_wide_bwd": (C.c_int, [C.POINTER(AttnWideBwdArgs), vp]),
     "pd_comm_unique_id": (C.c_int, [C.POINTER(CommId)]),
     "pd_comm_init": (C.c_int, [C.POINTER(CommId), C.c_int, C.c_int, C.POINTER(vp)]),

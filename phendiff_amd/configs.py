@@ -65,3 +65,14 @@ SCHEDULER_CONFIGS = {
         num_train_timesteps=3000, prediction_type="v_prediction", rescale_betas_zero_snr=True,
         timestep_spacing="trailing"),
 }
+
+# The Stable Diffusion 1.x UNet2DConditionModel (CompVis/stable-diffusion-v1-1 .. v1-4, runwayml/stable-diffusion-v1-5: the checkpoints
+# custom_pipeline_stable_diffusion_img2img.py:108-130 names) -- 859 520 964 parameters.  Against SD 2.1: eight heads per block
+# (head_dim 40 / 80 / 160 -> pd_attn_hd), 1x1-conv proj_in / proj_out, a 768-wide text context.  Its AutoencoderKL is SD 2.1's
+# architecture with scaling_factor 0.18215.
+SD15_UNET_CONFIG = dict(
+    in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
+    down_block_types=("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+    up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D"),
+    attention_head_dim=8, cross_attention_dim=768, norm_num_groups=32, norm_eps=1e-5,
+    flip_sin_to_cos=True, freq_shift=0, use_linear_projection=False, sample_size=64)

@@ -9,7 +9,7 @@ namespace pd {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OOB_OFF = 0xC0000000u;   // > any tensor we accept (< 2 GiB): buffer loads return 0
+constexpr unsigned OOB_OFF = 0xC0000000u;   // beyond any resource an entry point accepts (spans < 2 GiB; pd_attn_hd: < 3 GiB): buffer loads return 0
 
 // primary template: the 16-bit element types (bf16, fp16); fp32 is the specialisation below
 template <typename T> struct Stage {

@@ -25,6 +25,8 @@ from .packing import pack_conv_weight, upsample_phase_weights_stacked
 from .training import mark_requires_grad_calls
 from .unet import UNet2DOutput, UNetPlan, _Block, _DT, _Op, _Resnet, _Sampler, _TimestepEmbedding
 
+ATTN_HEAD_DIMS = (40, 64, 80, 160)      # pd_attn_d64 for 64, pd_attn_hd for the SD 1.x widths
+
 SD21_UNET_CONFIG = dict(
     in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
     down_block_types=("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
@@ -69,14 +71,16 @@ class _BasicTransformerBlock(nn.Module):
 
 
 class _Transformer2D(nn.Module):
-    def __init__(self, heads, dim_head, in_channels, cross_attention_dim, groups):
+    def __init__(self, heads, dim_head, in_channels, cross_attention_dim, groups, use_linear_projection=True):
         super().__init__()
         inner = heads * dim_head
-        self.heads = heads
+        self.heads, self.dim_head = heads, dim_head
         self.norm = nn.GroupNorm(groups, in_channels, eps=1e-6, affine=True)
-        self.proj_in = nn.Linear(in_channels, inner)
+        # SD 2.x: nn.Linear; SD 1.x (use_linear_projection=False): the same numbers as a 1x1 nn.Conv2d, weight (C, C, 1, 1)
+        proj = (lambda i, o: nn.Linear(i, o)) if use_linear_projection else (lambda i, o: nn.Conv2d(i, o, 1))
+        self.proj_in = proj(in_channels, inner)
         self.transformer_blocks = nn.ModuleList([_BasicTransformerBlock(inner, heads, dim_head, cross_attention_dim)])
-        self.proj_out = nn.Linear(inner, in_channels)
+        self.proj_out = proj(inner, in_channels)
 
 
 @mark_requires_grad_calls
@@ -103,8 +107,11 @@ _SD_DEFAULTS = dict(SD21_UNET_CONFIG)
 
 @mark_requires_grad_calls
 class SDUNet2DConditionModel(nn.Module):
-    """Drop-in for diffusers ``UNet2DConditionModel`` in the SD-2.1 configuration (``use_linear_projection=True``, one
-    transformer layer per block, head_dim 64).  ``compute_dtype``: "bf16" (fast) or "f32" (exact-fp32 MFMA, parity mode)."""
+    """Drop-in for diffusers ``UNet2DConditionModel`` in the SD 2.x configuration (``use_linear_projection=True``, head_dim 64) and
+    the SD 1.x one (``use_linear_projection=False``: 1x1-conv ``proj_in`` / ``proj_out``; ``attention_head_dim=8`` heads, head_dim
+    40 / 80 / 160 through ``pd_attn_hd``); one transformer layer per block, per-block head_dim in ``ATTN_HEAD_DIMS`` (blocks may mix).
+    ``compute_dtype``: "bf16" (fast), "fp16" or "f32" (exact-fp32 MFMA, parity mode).  Training and the input-gradient plan need
+    head_dim 64 everywhere (``pd_attn_hd`` has no backward yet)."""
 
     def __init__(self, compute_dtype: str = "bf16", **kwargs):
         super().__init__()
@@ -120,13 +127,13 @@ class SDUNet2DConditionModel(nn.Module):
                    up_block_types=tuple(cfg["up_block_types"]))
         self.config = SimpleNamespace(**cfg)
         c = self.config
-        if not c.use_linear_projection:
-            raise NotImplementedError("phendiff_amd: use_linear_projection=True (SD 2.x) only")
+        c.use_linear_projection = bool(c.use_linear_projection)
         if len(c.down_block_types) != len(c.up_block_types) or len(boc) != len(c.down_block_types):
             raise ValueError("block type / channel lists must have the same length")
         for ch, nh in zip(boc, heads):
-            if ch % 32 or ch // nh != 64 or ch % nh:
-                raise NotImplementedError("phendiff_amd: channels must be multiples of 32 with head_dim 64 (pd_attn_d64)")
+            if ch % 32 or nh <= 0 or ch % nh or ch // nh not in ATTN_HEAD_DIMS:
+                raise NotImplementedError(f"phendiff_amd: channels must be multiples of 32 with a head_dim of 40 / 64 / 80 / 160 "
+                                          f"(pd_attn_d64: 64; pd_attn_hd: 40, 80, 160), got {ch} channels on {nh} heads")
         if c.cross_attention_dim % 32 or c.in_channels > 32:
             raise NotImplementedError("cross_attention_dim must be a multiple of 32; in_channels <= 32")
         if compute_dtype not in _DT:
@@ -136,7 +143,7 @@ class SDUNet2DConditionModel(nn.Module):
         self.time_embed_dim = tdim
         self.conv_in = nn.Conv2d(c.in_channels, boc[0], 3, padding=1)
         self.time_embedding = _TimestepEmbedding(boc[0], tdim)
-        tf = lambda ch, nh: _Transformer2D(nh, ch // nh, ch, c.cross_attention_dim, g)
+        tf = lambda ch, nh: _Transformer2D(nh, ch // nh, ch, c.cross_attention_dim, g, c.use_linear_projection)
         self.down_blocks = nn.ModuleList()
         out_ch = boc[0]
         n = c.layers_per_block
@@ -223,11 +230,25 @@ class SDUNet2DConditionModel(nn.Module):
     def invalidate(self):
         self._plans, self._weights, self._grad_weights = {}, None, None
 
+    @property
+    def head_dims(self):
+        """The head dimensions of the attention blocks this network holds (sorted, unique)."""
+        return tuple(sorted({mod.dim_head for mod in self.modules() if isinstance(mod, _Transformer2D)}))
+
+    def require_attention_backward(self, what):
+        """Training / input-gradient plans exist for head_dim 64 only: raised before anything is packed or launched."""
+        other = [d for d in self.head_dims if d != 64]
+        if other:
+            raise NotImplementedError(f"phendiff_amd: {what} needs the attention backward, and pd_attn_hd (head_dim "
+                                      f"{' / '.join(map(str, other))}) has no backward kernel yet -- only head_dim 64 "
+                                      f"(pd_attn_d64_bwd) trains; SD 1.x-shaped denoisers run inference only")
+
     def input_grad_plan(self, B, H, W, tokens, device):
         """Forward + input-gradient-only backward plan (d loss / d latents through the UNet, no parameter gradients): what
         ``torch.autograd.grad(losses_seq, images)`` needs in the gradient-guided transfer with a latent-diffusion pipeline
         (utils_Img2Img.py:718-745)."""
         from .sd_unet_train import SDTrainWeights, SDUNetTrainPlan
+        self.require_attention_backward("the input-gradient plan (gradient-guided transfer)")
         # (compute_dtype='fp16': the caller scales `dout` / un-scales `dlatents`, as for the pixel UNet -- img2img.custom_guided_generation)
         key = ("input_grad", B, H, W, tokens, str(device), self.compute_dtype)
         p = self._plans.get(key)
@@ -281,7 +302,7 @@ class _SDPackedWeights:
         dev = device
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
         pk = lambda w, cp=None: pack_conv_weight(w.detach().to(device=dev, dtype=torch.float32), self.tdt, cp)
-        lin = lambda w: w.detach()[:, :, None, None]
+        lin = lambda w: w.detach() if w.ndim == 4 else w.detach()[:, :, None, None]      # (proj_in / proj_out of SD 1.x are 1x1 convs already)
         c = m.config
         # conv_in over the latents padded to 32 NHWC channels (zero weights on the padding)
         wi = torch.zeros((c.block_out_channels[0], 32, 3, 3), dtype=torch.float32, device=dev)
@@ -313,7 +334,7 @@ class _SDPackedWeights:
             elif isinstance(r, _Transformer2D):
                 blk = r.transformer_blocks[0]
                 ch = r.proj_in.weight.shape[0]
-                e = SimpleNamespace(heads=r.heads, ch=ch, g=f32(r.norm.weight), be=f32(r.norm.bias), eps=r.norm.eps)
+                e = SimpleNamespace(heads=r.heads, dim_head=r.dim_head, ch=ch, g=f32(r.norm.weight), be=f32(r.norm.bias), eps=r.norm.eps)
                 e.w_in, e.b_in = pk(lin(r.proj_in.weight)), f32(r.proj_in.bias)
                 e.w_out, e.b_out = pk(lin(r.proj_out.weight)), f32(r.proj_out.bias)
                 for i, nrm in enumerate((blk.norm1, blk.norm2, blk.norm3), 1):
@@ -371,13 +392,18 @@ class SDUNetPlan(UNetPlan):
         self.ops.append(_Op(self.lib.pd_layernorm, a, "layernorm", 0.0, 2.0 * x.numel() * self._esz()))
         return y
 
-    def _attention(self, q, qs, k, v, kvs, heads, nq, nkv):
-        out = self._act(1, nq, heads * 64).view(self.B, 1, nq, heads * 64)
+    def _attention(self, q, qs, k, v, kvs, heads, nq, nkv, dim_head=64):
+        ch = heads * dim_head
+        out = self._act(1, nq, ch).view(self.B, 1, nq, ch)
         lse = self._f32(self.B, heads, nq) if self.train else None
-        a = L.AttnD64Args(dtype=self.code, B=self.B, heads=heads, Nq=nq, Nkv=nkv, q=q, q_stride=qs, k=k, v=v, kv_stride=kvs,
-                          out=out.data_ptr(), out_stride=heads * 64, lse=L.ptr(lse))
-        self.ops.append(_Op(self.lib.pd_attn_d64, a, "attn_d64", 4.0 * self.B * heads * nq * nkv * 64,
-                            (2.0 * self.B * nq + 2.0 * self.B * nkv) * heads * 64 * self._esz()))
+        common = dict(dtype=self.code, B=self.B, heads=heads, Nq=nq, Nkv=nkv, q=q, q_stride=qs, k=k, v=v, kv_stride=kvs,
+                      out=out.data_ptr(), out_stride=ch, lse=L.ptr(lse))
+        if dim_head == 64:
+            fn, a, what = self.lib.pd_attn_d64, L.AttnD64Args(**common), "attn_d64"
+        else:                           # SD 1.x head dimensions (40 / 80 / 160); anything else is refused by the entry point
+            fn, a, what = self.lib.pd_attn_hd, L.AttnHdArgs(D=dim_head, scale=float(dim_head) ** -0.5, **common), "attn_hd"
+        self.ops.append(_Op(fn, a, what, 4.0 * self.B * heads * nq * nkv * dim_head,
+                            (2.0 * self.B * nq + 2.0 * self.B * nkv) * ch * self._esz()))
         return out, lse
 
     def _transformer(self, name, x):
@@ -394,7 +420,7 @@ class SDUNetPlan(UNetPlan):
         y1 = self._layernorm(h0, e.ln1)
         qkv = lin(y1, e.wqkv1, zb, 3 * ch)
         p = qkv.data_ptr()
-        a1, lse1 = self._attention(p, 3 * ch, p + ch * esz, p + 2 * ch * esz, 3 * ch, e.heads, N, N)
+        a1, lse1 = self._attention(p, 3 * ch, p + ch * esz, p + 2 * ch * esz, 3 * ch, e.heads, N, N, e.dim_head)
         a1 = a1.view(B, h, w, ch)
         h1 = lin(a1, e.wo1, e.bo1, ch, residual=h0)
         # cross attention over the encoder_hidden_states tokens
@@ -404,7 +430,7 @@ class SDUNetPlan(UNetPlan):
         # k / v of the cross attention depend on the class context only -- not on the latents, not on the timestep: a sampling loop
         # projects them ONCE per context (`run(..., context=False)` skips these ops; 16 launches, 1.6 % of a forward at B = 32) -- round 6
         self.ops[-1].ctx = not self.train
-        a2, lse2 = self._attention(q2.data_ptr(), ch, kv.data_ptr(), kv.data_ptr() + ch * esz, 2 * ch, e.heads, N, self.tokens)
+        a2, lse2 = self._attention(q2.data_ptr(), ch, kv.data_ptr(), kv.data_ptr() + ch * esz, 2 * ch, e.heads, N, self.tokens, e.dim_head)
         a2 = a2.view(B, h, w, ch)
         h2 = lin(a2, e.wo2, e.bo2, ch, residual=h1)
         # GEGLU feed-forward

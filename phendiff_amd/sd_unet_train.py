@@ -103,6 +103,7 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
                  input_grad: bool = False):
         """``input_grad``: also produce d loss / d latents (fp32 NCHW, ``self.dsample``) -- the gradient-guided transfer's
         ``torch.autograd.grad(losses_seq, images)`` through the UNet (utils_Img2Img.py:718-745, latent-diffusion branch)."""
+        m.require_attention_backward("SDUNetTrainPlan")
         self.train = True
         SDUNetPlan.__init__(self, m, w, B, H, W, tokens, device)
         self._init_train(tw, params, grads, input_grad, frozen)
@@ -457,6 +458,7 @@ class SDUNetTrainer(UNetTrainer):
         least one of its parameters does (:func:`sd_training_layout`); :meth:`step_images` then encodes inside the step and sends
         the loss gradient back through ``quant_conv`` and the encoder.  ``_vae_chunk``: tests force the encoder's chunk size."""
         from .training import DiffusionLoss, FlatAdamWEMA, broadcast_from_rank0_
+        model.require_attention_backward("SDUNetTrainer (SD fine-tuning)")
         self.model, self.class_embedding, self.scheduler, self.vae = model, class_embedding, scheduler, vae
         dev = device or model.device
         if torch.device(dev).type != "cuda":
