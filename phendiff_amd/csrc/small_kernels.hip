@@ -364,7 +364,8 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const pd_ddim_step_args 
   for (int j = 0; j < 4; ++j) {
     float out = o[j];
     if (a.uncond_out) {
-      const float w = a.w_per_sample ? a.w[(i0 + j) / a.per_sample] : a.w[0];
+      // (lanes past numel in the tail vector take element i0's weight: (i0 + j) / per_sample would index one past w[B - 1])
+      const float w = a.w_per_sample ? a.w[(i0 + (j < cnt ? j : 0)) / a.per_sample] : a.w[0];
       out = a.guidance_cfg ? (o[j] + w * (o[j] - u[j])) : (u[j] + w * (o[j] - u[j]));
     }
     float x0, eps;
@@ -499,7 +500,9 @@ extern "C" int pd_ddim_step(const pd_ddim_step_args* a, void* stream) {
   PD_CHECK(a->numel > 0 && a->sample && a->model_out && a->prev_sample, PD_ERR_ARG, "pd_ddim_step: bad args");
   PD_CHECK(a->pred_type >= 0 && a->pred_type <= 2, PD_ERR_ARG, "pd_ddim_step: bad prediction type");
   PD_CHECK(!a->uncond_out || a->w, PD_ERR_ARG, "pd_ddim_step: guidance without weights");
-  PD_CHECK(((uintptr_t)a->sample % 16 == 0) && ((uintptr_t)a->model_out % 16 == 0) && ((uintptr_t)a->prev_sample % 16 == 0),
+  // uncond_out and pred_x0 go through the same f32x4 loads / stores as the other three (NULL passes: 0 % 16 == 0)
+  PD_CHECK(((uintptr_t)a->sample % 16 == 0) && ((uintptr_t)a->model_out % 16 == 0) && ((uintptr_t)a->prev_sample % 16 == 0) &&
+           ((uintptr_t)a->uncond_out % 16 == 0) && ((uintptr_t)a->pred_x0 % 16 == 0),
            PD_ERR_ARG, "pd_ddim_step: tensors must be 16-byte aligned");
   const unsigned grid = (unsigned)((a->numel + 1023) / 1024);
   hipLaunchKernelGGL(ddim_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);

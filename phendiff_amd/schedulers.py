@@ -131,14 +131,15 @@ class _SchedulerBase:
         prev = torch.empty_like(x) if out is None else out
         x0 = torch.empty_like(x) if want_x0 else None
         c = self.config
-        wt = None
+        wt = uo = None
         if uncond_output is not None:
+            uo = uncond_output.contiguous().float()      # the kernel reads dense fp32, as it does model_output
             wt = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
         a = L.DdimStepArgs(numel=x.numel(), per_sample=x[0].numel(), pred_type=_PRED[c.prediction_type],
                            clip=int(bool(c.clip_sample)), clip_range=float(c.clip_sample_range),
                            use_clipped_model_output=int(bool(use_clipped_model_output)),
                            sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=x.data_ptr(), model_out=mo.data_ptr(),
-                           uncond_out=L.ptr(uncond_output), w=L.ptr(wt), w_per_sample=int(wt is not None and wt.numel() > 1),
+                           uncond_out=L.ptr(uo), w=L.ptr(wt), w_per_sample=int(wt is not None and wt.numel() > 1),
                            guidance_cfg=int(guidance_cfg), prev_sample=prev.data_ptr(), pred_x0=L.ptr(x0))
         st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
         L.check(lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")

@@ -67,6 +67,13 @@ def test_argument_validation_without_gpu():
     assert lib.pd_conv(C.byref(a), None) == -2 and b"multiples of 32" in lib.pd_last_error()
     assert lib.pd_attn_d8(C.byref(L.AttnArgs(dtype=1, B=0)), None) == -2
     assert lib.pd_ddim_step(C.byref(L.DdimStepArgs(numel=0)), None) == -1
+    # every tensor of pd_ddim_step goes through 16-byte loads / stores: each of the five pointers in turn at 16k + 4, the others
+    # aligned, is refused before any launch (the addresses are never dereferenced)
+    base = dict(sample=0x10000, model_out=0x20000, uncond_out=0x30000, prev_sample=0x40000, pred_x0=0x50000)
+    for name in base:
+        p = dict(base, **{name: base[name] + 4})
+        assert lib.pd_ddim_step(C.byref(L.DdimStepArgs(numel=8, per_sample=8, pred_type=2, w=0x60000, **p)), None) == -1, name
+        assert b"16-byte aligned" in lib.pd_last_error(), name
     assert lib.pd_conv_stat_tiles(256, 256, 3, 1) == 256 and lib.pd_conv_stat_tiles(64, 64, 3, 2) == 32
     assert lib.pd_attn_wide(C.byref(L.AttnWideArgs(dtype=1, B=1, heads=1, D=512, Nq=0, Nkv=4)), None) == -2
     assert lib.pd_attn_d64_bwd(C.byref(L.AttnD64BwdArgs(dtype=1, B=1, heads=1, Nq=4, Nkv=4)), None) == -1
