@@ -36,7 +36,7 @@ extern "C" {
  * pd_resize_tf1, pd_conv_rect, pd_pool2d, pd_fc_f32 (the evaluation metrics' feature extractor); pd_pack_weight_args.dst2 / dst2_ct_stride;
  * 8 = pd_geglu_bwd_args.sums / sum_splits / B, pd_layernorm_bwd_args.dxsum (bias gradients without a pass over dY), pd_upsample_phase_weights,
  * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
- * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess. */
+ * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd. */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -577,13 +577,14 @@ typedef struct {
 } pd_attn_wide_args;
 int pd_attn_wide(const pd_attn_wide_args* a, void* stream);
 
-/* pd_attn_hd: softmax(q k^T * scale) v per (batch, head) for the head dimensions of the Stable-Diffusion 1.x denoisers,
- * D in {40, 80, 160} (attention_head_dim = 8: eight heads on 320 / 640 / 1280 channels; BasicTransformerBlock.attn1 / .attn2 of
+/* pd_attn_hd: softmax(q k^T * scale) v per (batch, head) for the head dimensions between the dedicated kernels:
+ * D in {16, 32} (attention_head_dim 16 / 32 of CustomCondUNet2DModel, cond_unet_2d.py:60,100) and D in {40, 80, 160} (the
+ * Stable-Diffusion 1.x denoisers, attention_head_dim = 8: eight heads on 320 / 640 / 1280 channels; BasicTransformerBlock.attn1 / .attn2 of
  * the CompVis/stable-diffusion-v1-* and runwayml/stable-diffusion-v1-5 UNets that custom_pipeline_stable_diffusion_img2img.py:108-130
  * names).  Operand addressing as pd_attn_d64 (token-major with element strides, multiples of 8; channel = head*D + d), so q/k/v may
  * be slices of one fused projection output.  scale = D^-1/2 for diffusers' Attention.  Any other D: PD_ERR_SHAPE.  D is padded to
  * the MFMA step in LDS / registers only, with zeros; nothing beyond a head's D channels or a sample's Nkv rows is used.
- * No backward yet: lse is what it will recompute P from. */
+ * lse is what pd_attn_hd_bwd (D in {16, 32}) recomputes P from; D in {40, 80, 160} has no backward yet. */
 typedef struct {
   int dtype;
   int B, heads, D, Nq, Nkv;
@@ -594,6 +595,24 @@ typedef struct {
   float* lse;   /* optional out [B][heads][Nq]: log2-domain log-sum-exp of the scaled scores (as pd_attn_d64_args.lse), or NULL */
 } pd_attn_hd_args;
 int pd_attn_hd(const pd_attn_hd_args* a, void* stream);
+
+/* pd_attn_hd_bwd: gradient of pd_attn_hd (autograd of F.scaled_dot_product_attention over heads of D channels), D in {16, 32}; any
+ * other D: PD_ERR_SHAPE.  P is recomputed from the forward's lse; a delta pre-pass, a dQ kernel and a dK / dV kernel, no atomics: the
+ * result is bitwise reproducible.  Fields and addressing as pd_attn_wide_bwd_args (token-major, element strides that are multiples of
+ * 8, channel = head*D + d), so dq | dk | dv may be slices of one fused projection's output gradient.
+ *   o / dout: the forward's output and the gradient w.r.t. it, [B][Nq][o_stride];  delta: workspace [B][heads][Nq];
+ *   dq: [B][Nq][dq_stride];  dk, dv: [B][Nkv][dkv_stride].  fp32 / bf16 / fp16 (fp16 under the trainer's loss scale).
+ * Nothing beyond a head's D channels or a sample's Nq / Nkv rows is read, and nothing else is written. */
+typedef struct {
+  int dtype, B, heads, D, Nq, Nkv; float scale;
+  const void* q; int q_stride;
+  const void* k; const void* v; int kv_stride;
+  const void* o; const void* dout; int o_stride;
+  const float* lse; float* delta;
+  void* dq; int dq_stride;
+  void* dk; void* dv; int dkv_stride;
+} pd_attn_hd_bwd_args;
+int pd_attn_hd_bwd(const pd_attn_hd_bwd_args* a, void* stream);
 
 /* pd_attn_wide_bwd: gradient of pd_attn_wide (autograd of F.scaled_dot_product_attention, one wide head per D channels): what
  * accelerator.backward(loss) (utils_training.py:436) runs for the attention blocks of orig_google_ddpm_model_denoiser.json

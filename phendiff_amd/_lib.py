@@ -176,6 +176,13 @@ class AttnHdArgs(C.Structure):
                 ("out_stride", C.c_int), ("lse", vp)]
 
 
+class AttnHdBwdArgs(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("heads", C.c_int), ("D", C.c_int), ("Nq", C.c_int), ("Nkv", C.c_int),
+                ("scale", C.c_float), ("q", vp), ("q_stride", C.c_int), ("k", vp), ("v", vp), ("kv_stride", C.c_int), ("o", vp),
+                ("dout", vp), ("o_stride", C.c_int), ("lse", vp), ("delta", vp), ("dq", vp), ("dq_stride", C.c_int), ("dk", vp),
+                ("dv", vp), ("dkv_stride", C.c_int)]
+
+
 class CommId(C.Structure):
     _fields_ = [("bytes", C.c_char * 128)]
 
@@ -348,6 +355,7 @@ SYMBOLS = {
     "pd_linear_fold_workspace": (C.c_size_t, [C.POINTER(LinearArgs)]),
     "pd_attn_wide": (C.c_int, [C.POINTER(AttnWideArgs), vp]),
     "pd_attn_hd": (C.c_int, [C.POINTER(AttnHdArgs), vp]),
+    "pd_attn_hd_bwd": (C.c_int, [C.POINTER(AttnHdBwdArgs), vp]),
     "pd_attn_wide_bwd": (C.c_int, [C.POINTER(AttnWideBwdArgs), vp]),
     "pd_comm_unique_id": (C.c_int, [C.POINTER(CommId)]),
     "pd_comm_init": (C.c_int, [C.POINTER(CommId), C.c_int, C.c_int, C.POINTER(vp)]),

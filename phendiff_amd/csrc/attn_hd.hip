@@ -1,10 +1,11 @@
-// pd_attn_hd: softmax(q k^T * scale) v for the head dimensions of the Stable-Diffusion 1.x denoisers, D = 40 / 80 / 160
-// (attention_head_dim = 8 heads on 320 / 640 / 1280 channels).  The structure is attn_d64_kernel's one-fragment form (sd_kernels.hip):
+// pd_attn_hd: softmax(q k^T * scale) v for the head dimensions between the dedicated kernels: D = 16 / 32 (attention_head_dim 16 / 32 of the
+// pixel UNet) and D = 40 / 80 / 160 (the Stable-Diffusion 1.x denoisers: 8 heads on 320 / 640 / 1280 channels).  The structure is attn_d64_kernel's one-fragment form (sd_kernels.hip):
 // workgroup = 4 waves = 128 queries of one (batch, head), keys / values stream through LDS in double-buffered tiles, per wave and
 // 32-key sub-tile
 //   S^T[key][query] = K[32 x DK] . Q^T[DK x 32]       DK / 16 MFMA k-steps, DK = D rounded up to 16 (40 -> 48: 3 steps, not the 4 of a 64-padded head)
 //   deferred-rescale online softmax, P in registers
 //   O^T[d][query] += V^T[DV x 32 keys] . P^T          DV / 32 row tiles, DV = D rounded up to 32 (80 -> 96: 3 tiles, not the 4 of a 128-padded head)
+// D = 32 has no padding at all; D = 16 has one k-step and one row tile whose upper half is padding (never stored).
 // The padding of D exists in LDS and registers only, as zeros: the pad columns of the K / V tiles are zeroed once per workgroup (the staging
 // never writes them), the pad elements of the Q fragments are selected to zero.  Nothing is read from HBM for them (the channels behind a head
 // belong to the next head, or to nobody).
@@ -13,43 +14,9 @@
 #include <stdlib.h>
 #include "pd_common.h"
 #include "pd_stage.h"
-#include "pd_d64.h"
+#include "pd_hd.h"
 
 namespace pd {
-
-template <typename T, int D> struct HD {
-  typedef Elem<T> E;
-  typedef typename E::Frag Frag;
-  static constexpr int ES = E::BYTES;
-  static constexpr int DK = (D + 15) / 16 * 16, DV = (D + 31) / 32 * 32;
-  static constexpr int KS = DK / 16, NT = DV / 32, PPR = D / 8;           // k-steps of QK^T, row tiles of O^T, 8-element pieces per row
-  // row pitches as D64's: K rows read as ds_read_b128 rows (odd multiple of 16 B), V rows as transposed 4-row blocks (odd multiple of 64 B)
-  static constexpr int KP = DK * ES + 16;
-  static constexpr int VP = ES == 2 ? (((DV * 2 + 63) / 64) | 1) * 64 : DV * 4 + 16;
-  // keys per tile: 64; 32 at D = 160 (64 would take 83 968 B of LDS: one workgroup per CU, where the registers allow two) and in the
-  // fp32 parity engine.  The file is built with the MFMA accumulators in VGPRs (build.sh): O, S and the softmax share one register class.
-  static constexpr int KT = (ES == 2 && D <= 80) ? 64 : 32;
-  static constexpr int KBYTES = KT * KP, VBYTES = KT * VP, LDS = 2 * (KBYTES + VBYTES);
-  static constexpr int NP = KT * PPR, PIECES = (NP + 255) / 256;           // staging pieces per tensor and tile / per thread
-  static __device__ __forceinline__ int vt_lane_off(int lane) {            // (D64::vt_lane_off with this pitch)
-    if constexpr (ES == 2) {
-      const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-      return (4 * (g >> 1) + q) * VP + (16 * (g & 1) + 4 * pp) * 2;
-    } else {
-      return (4 * (lane >> 5)) * VP + (lane & 31) * 4;
-    }
-  }
-  static __device__ __forceinline__ Frag load_vt(const unsigned char* base) {
-    if constexpr (ES == 2) {
-      return D64<T>::load_vt2(base, base + 8 * VP);
-    } else {
-      Frag f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { f.lo[j] = *(const float*)(base + j * VP); f.hi[j] = *(const float*)(base + (8 + j) * VP); }
-      return f;
-    }
-  }
-};
 
 template <typename T, int D>
 __global__ __launch_bounds__(256) void attn_hd_kernel(const pd_attn_hd_args a) {
@@ -234,6 +201,8 @@ static int launch_attn_hd(const pd_attn_hd_args* a, hipStream_t st) {
 
 template <typename T>
 static int dispatch_attn_hd(const pd_attn_hd_args* a, hipStream_t st) {
+  if (a->D == 16) return launch_attn_hd<T, 16>(a, st);
+  if (a->D == 32) return launch_attn_hd<T, 32>(a, st);
   if (a->D == 40) return launch_attn_hd<T, 40>(a, st);
   if (a->D == 80) return launch_attn_hd<T, 80>(a, st);
   return launch_attn_hd<T, 160>(a, st);
@@ -245,7 +214,8 @@ using namespace pd;
 
 extern "C" int pd_attn_hd(const pd_attn_hd_args* a, void* stream) {
   PD_CHECK(a != nullptr, PD_ERR_ARG, "pd_attn_hd: null args");
-  PD_CHECK(a->D == 40 || a->D == 80 || a->D == 160, PD_ERR_SHAPE, "pd_attn_hd: head dimension %d not built (40, 80, 160)", a->D);
+  PD_CHECK(a->D == 16 || a->D == 32 || a->D == 40 || a->D == 80 || a->D == 160, PD_ERR_SHAPE,
+           "pd_attn_hd: head dimension %d not built (16, 32, 40, 80, 160)", a->D);
   PD_CHECK(a->B > 0 && a->heads > 0 && a->Nq > 0 && a->Nkv > 0, PD_ERR_SHAPE, "pd_attn_hd: bad shape");
   PD_CHECK(a->q && a->k && a->v && a->out, PD_ERR_ARG, "pd_attn_hd: null pointer");
   PD_CHECK(a->scale == a->scale && a->scale != 0.f && a->scale - a->scale == 0.f, PD_ERR_ARG, "pd_attn_hd: scale must be finite and non-zero");

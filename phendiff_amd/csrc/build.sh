@@ -9,13 +9,13 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 if [ "$1" = "--clean" ]; then rm -rf "$HERE/build"; rm -f "$OUT" "$OUT.manifest.json"; fi
 mkdir -p "$HERE/build"
 pids=()
-SRCS="conv_igemm attn_d8 small_kernels train_kernels backward_kernels wgrad sd_kernels attn_hd vae_kernels sd_bwd_kernels linear_gemm linear_p8 metric_kernels data_kernels comm_rccl"
+SRCS="conv_igemm attn_d8 small_kernels train_kernels backward_kernels wgrad sd_kernels attn_hd attn_hd_bwd vae_kernels sd_bwd_kernels linear_gemm linear_p8 metric_kernels data_kernels comm_rccl"
 for f in $SRCS; do
   X=""
-  # attention (forward d = 8, backward d = 64, forward d = 40 / 80 / 160): keep MFMA accumulators in VGPRs (the softmax / its derivative
+  # attention (forward d = 8, backward d = 64, forward and backward of the templated head dimensions): keep MFMA accumulators in VGPRs (the softmax / its derivative
   # work on them; AGPR form costs a copy per register -- d64 backward: 20.3 -> 17.8 ms per SD training step, dq kernel 2 -> 3 waves/SIMD;
   # attn_hd, 16-bit engines: 112+48 / 144+64 / 196+96 -> 120 / 166 / 220 registers, 3 / 2 / 1 -> 4 / 3 / 2 waves/SIMD)
-  if [ "$f" = "attn_d8" ] || [ "$f" = "sd_bwd_kernels" ] || [ "$f" = "attn_hd" ]; then X="-mllvm -amdgpu-mfma-vgpr-form"; fi
+  if [ "$f" = "attn_d8" ] || [ "$f" = "sd_bwd_kernels" ] || [ "$f" = "attn_hd" ] || [ "$f" = "attn_hd_bwd" ]; then X="-mllvm -amdgpu-mfma-vgpr-form"; fi
   # an object is current when the hash of everything it depends on (its .hip, EVERY header, this script, the flags) equals the
   # one recorded beside it -- no hand-kept header list, no timestamps
   want="$(python3 "$HERE/source_hash.py" "$f" "$FLAGS $X $EXTRA_HIPCC_FLAGS")"

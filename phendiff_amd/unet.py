@@ -739,24 +739,28 @@ class UNetPlan:
         return out
 
     def _attn_nhwc(self, name, x):
-        """GroupNorm -> fused q|k|v Linear (NHWC, no head-major copy) -> attention with head_dim 64 (``pd_attn_d64``) or one wide
-        head of 128 / 256 / 512 channels (``pd_attn_wide``) -> out Linear + residual: diffusers ``Attention`` with
+        """GroupNorm -> fused q|k|v Linear (NHWC, no head-major copy) -> attention with head_dim 16 / 32 (``pd_attn_hd``), 64
+        (``pd_attn_d64``) or one wide head of 128 / 256 / 512 channels (``pd_attn_wide``) -> out Linear + residual: diffusers ``Attention`` with
         ``residual_connection=True`` for every head_dim other than 8 (the VAE mid block; ``attention_head_dim = None``)."""
         e = self.w.attns[name]
         B, h, w, ch = x.shape
         N, esz = h * w, (4 if self.code == L.PD_F32 else 2)
         d = ch // e.heads
-        if d != 64 and d not in (128, 256, 512):
-            raise NotImplementedError(f"attention head_dim {d}: implemented are 8, 64 and one wide head of 128 / 256 / 512 channels")
+        if d not in (16, 32, 64, 128, 256, 512):
+            raise NotImplementedError(f"attention head_dim {d}: implemented are 8, 16, 32, 64 and one wide head of 128 / 256 / 512 channels")
         gn = self._gn(x, None, e.g, e.be, e.eps)
         qkv, _ = self._conv(x, None, e.wqkv, e.bqkv, 3 * ch, ksize=1, pad=0, gn=gn, stats=False)
         o = self._act(h, w, ch)
         p = qkv.data_ptr()
-        lse = self._f32(B, e.heads, N) if self.train else None        # kept for the backward (pd_attn_d64_bwd / pd_attn_wide_bwd)
+        lse = self._f32(B, e.heads, N) if self.train else None        # kept for the backward (pd_attn_d64_bwd / pd_attn_hd_bwd / pd_attn_wide_bwd)
         if d == 64:
             a = L.AttnD64Args(dtype=self.code, B=B, heads=e.heads, Nq=N, Nkv=N, q=p, q_stride=3 * ch, k=p + ch * esz,
                               v=p + 2 * ch * esz, kv_stride=3 * ch, out=o.data_ptr(), out_stride=ch, lse=L.ptr(lse))
             fn, what = self.lib.pd_attn_d64, "attn_d64"
+        elif d in (16, 32):
+            a = L.AttnHdArgs(dtype=self.code, B=B, heads=e.heads, D=d, Nq=N, Nkv=N, scale=float(d) ** -0.5, q=p, q_stride=3 * ch,
+                             k=p + ch * esz, v=p + 2 * ch * esz, kv_stride=3 * ch, out=o.data_ptr(), out_stride=ch, lse=L.ptr(lse))
+            fn, what = self.lib.pd_attn_hd, "attn_hd"
         else:
             a = L.AttnWideArgs(dtype=self.code, B=B, heads=e.heads, D=d, Nq=N, Nkv=N, scale=float(d) ** -0.5, q=p, q_stride=3 * ch,
                                k=p + ch * esz, v=p + 2 * ch * esz, kv_stride=3 * ch, out=o.data_ptr(), out_stride=ch, lse=L.ptr(lse))

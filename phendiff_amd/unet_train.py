@@ -626,7 +626,7 @@ class UNetTrainPlan(UNetPlan):
         self._gn_bwd(rec.gn, dz, 0, res=dout, wname=n + ".group_norm")
 
     def _attn_nhwc_bwd(self, rec):
-        """Backward of ``UNetPlan._attn_nhwc`` (head_dim 64, or one wide head of 128 / 256 / 512 channels: ``attention_head_dim``
+        """Backward of ``UNetPlan._attn_nhwc`` (head_dim 16 / 32 / 64, or one wide head of 128 / 256 / 512 channels: ``attention_head_dim``
         null of orig_google_ddpm_model_denoiser.json): q | k | v live NHWC in one [B][N][3C] tensor, so the attention gradient
         is written straight into the fused projection's output gradient [dq | dk | dv]."""
         e, te, n = rec.e, self.tw.attns[rec.name], rec.name
@@ -645,6 +645,9 @@ class UNetTrainPlan(UNetPlan):
                       delta=delta.data_ptr(), dq=dp, dq_stride=3 * ch, dk=dp + ch * esz, dv=dp + 2 * ch * esz, dkv_stride=3 * ch)
         if d == 64:
             self._b(self.lib.pd_attn_d64_bwd, L.AttnD64BwdArgs(**common), "attn_d64_bwd", 10.0 * B * N * N * ch, 8.0 * B * N * ch * esz)
+        elif d in (16, 32):
+            self._b(self.lib.pd_attn_hd_bwd, L.AttnHdBwdArgs(D=d, scale=float(d) ** -0.5, **common), "attn_hd_bwd",
+                    10.0 * B * N * N * ch, 8.0 * B * N * ch * esz)
         else:
             self._b(self.lib.pd_attn_wide_bwd, L.AttnWideBwdArgs(D=d, scale=float(d) ** -0.5, **common), "attn_wide_bwd",
                     10.0 * B * N * N * ch, 8.0 * B * N * ch * esz)

@@ -12,7 +12,7 @@ git -C "$ROOT" show "$REV:include/phendiff_hip.h" > "$TMP/include/phendiff_hip.h
 cd "$TMP/phendiff_amd/csrc"
 OBJS=""
 for f in $(ls *.hip | sed "s/\.hip$//"); do
-  X=""; { [ "$f" = "attn_d8" ] || [ "$f" = "sd_bwd_kernels" ] || [ "$f" = "attn_hd" ]; } && X="-mllvm -amdgpu-mfma-vgpr-form"
+  X=""; { [ "$f" = "attn_d8" ] || [ "$f" = "sd_bwd_kernels" ] || [ "$f" = "attn_hd" ] || [ "$f" = "attn_hd_bwd" ]; } && X="-mllvm -amdgpu-mfma-vgpr-form"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function $X "$@" -c $f.hip -o $f.o 2>/dev/null &
   OBJS="$OBJS $f.o"
 done; wait

@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "phendiff_amd", "csrc")
 srcs = sorted(f for f in os.listdir(CS) if f.endswith(".hip"))
 def run(f):
-    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if f in ("attn_d8.hip", "sd_bwd_kernels.hip", "attn_hd.hip") else []
+    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if f in ("attn_d8.hip", "sd_bwd_kernels.hip", "attn_hd.hip", "attn_hd_bwd.hip") else []
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
                         *extra, os.path.join(CS, f), "-o", os.devnull], stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True)
     return r.stderr

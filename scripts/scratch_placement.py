@@ -10,7 +10,7 @@ SRC = os.path.join(ROOT, "phendiff_amd", "csrc")
 names = sys.argv[1:] or ["conv_igemm", "wgrad"]
 print("# kernel | MFMAs | scratch stores / loads before the first MFMA | between MFMAs | after the last MFMA")
 for n in names:
-    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if n in ("attn_d8", "sd_bwd_kernels", "attn_hd") else []
+    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if n in ("attn_d8", "sd_bwd_kernels", "attn_hd", "attn_hd_bwd") else []
     with tempfile.NamedTemporaryFile(suffix=".s") as t:
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S"] + extra +
                        [os.path.join(SRC, n + ".hip"), "-o", t.name], check=True, stderr=subprocess.DEVNULL)
