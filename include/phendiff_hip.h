@@ -36,7 +36,7 @@ extern "C" {
  * pd_resize_tf1, pd_conv_rect, pd_pool2d, pd_fc_f32 (the evaluation metrics' feature extractor); pd_pack_weight_args.dst2 / dst2_ct_stride;
  * 8 = pd_geglu_bwd_args.sums / sum_splits / B, pd_layernorm_bwd_args.dxsum (bias gradients without a pass over dY), pd_upsample_phase_weights,
  * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
- * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd. */
+ * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample. */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -802,6 +802,47 @@ typedef struct {
   float* y_f32; unsigned char* y_u8;
 } pd_image_preprocess_args;
 int pd_image_preprocess(const pd_image_preprocess_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_train_sample (added under ABI 8): the per-step sampling of perform_training_epoch (utils_training.py:244-256) on the device, one launch:
+ * Gaussian noise, timesteps and noisy = sqrt_acp[t] * clean + sqrt_1m_acp[t] * noise in a single pass over `clean`.  csrc/sample_kernels.hip;
+ * host side phendiff_amd.training.DeviceTrainingSampler.  The values depend only on (seed, step, rank, purpose, element index) -- not on the
+ * launch geometry, the batch split or the pointers -- so a run resumes from (seed, rank, step) alone.  It is NOT torch's CPU stream and NOT
+ * torch's device Philox layout.
+ *
+ * The stream (the contract): Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; ten rounds) with
+ *     key     = (seed low 32 bits, seed high 32 bits)
+ *     counter = (q low 32 bits, q high 32 bits, step low 32 bits, (step bits 32..47 << 16) | (rank << 4) | purpose)
+ *   rank < 4096, step < 2^48; purpose 0 = training noise, 1 = timesteps (never a noise purpose), 2 = posterior noise / a plain randn.
+ *   noise: flat element e = elem_base + i (i = index into this launch's buffers) takes word e & 3 of counter q = e >> 2.  Words (0, 1) are
+ *     one Box-Muller pair, words (2, 3) the other: with u = (x >> 8) * 2^-24 + 2^-25 in (0, 1) (evaluated exactly: 25 significant bits, more
+ *     than one fp32 holds, so the kernel takes ln u as log1p(u - 1) and the angle as 2 u - 2 in the upper half of the interval),
+ *     r = sqrt(-2 ln u_a), z_even = r * cospi(2 u_b), z_odd = r * sinpi(2 u_b); precise logf / log1pf / sqrtf / sincospif, fp32.
+ *   timesteps: t_b = ((uint64)x * N) >> 32 with x = word 0 of counter q = b (b = i / per_sample, the sample index within this launch)
+ *     under purpose 1; written as int64 by the thread that holds sample b's first element.
+ *   noisy: sqrt_acp[t_b] * clean + sqrt_1m_acp[t_b] * noise, two products and one sum without contraction: bit-identical to pd_add_noise on
+ *     the same noise and t.  The tables are fp32 [N] on the device (the host-computed ones DiffusionLoss / add_noise gather from).
+ * One thread per Philox counter = four consecutive elements: 16-byte loads / stores where the quad lies whole inside one sample and the
+ * buffers are aligned there, element by element where it straddles two samples (per_sample % 4 != 0), is cut by the end of the tensor or
+ * by an elem_base that is no multiple of 4.  B, per_sample and their product are arbitrary positive sizes.
+ *   clean == NULL: a pure randn fill of noise[B * per_sample] (noisy must be NULL); timesteps are drawn only when timesteps_out is given.
+ *   timesteps_in (optional, int64 [B], values in [0, N); the table index is clamped to that range): used instead of drawing, never written.
+ * Refused before any launch: null args / noise, N <= 0 where timesteps are needed, rank / step / purpose out of range, clean without tables or
+ * noisy or a source of timesteps, noisy without clean (PD_ERR_ARG); B, per_sample <= 0, a product or elem_base + product beyond 2^62, more
+ * than 2^31 - 1 blocks (PD_ERR_SHAPE). */
+typedef struct {
+  uint64_t seed, step;
+  int rank, purpose;
+  int64_t B, per_sample;
+  uint64_t elem_base;
+  int N;
+  const float* clean;
+  const float* sqrt_acp; const float* sqrt_1m_acp;
+  const int64_t* timesteps_in;
+  int64_t* timesteps_out;
+  float* noise; float* noisy;
+} pd_train_sample_args;
+int pd_train_sample(const pd_train_sample_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_comm_*: the data-parallel gradient exchange -- DistributedDataParallel's bucketed all-reduce under accelerator.backward(loss)

@@ -17,6 +17,7 @@ from . import configs  # noqa: F401
 from . import diagnostics  # noqa: F401
 from .comm import NativeComm  # noqa: F401
 from . import training  # noqa: F401
+from .training import DeviceTrainingSampler  # noqa: F401
 from .unet_train import UNetTrainer, UNetTrainPlan, training_param_order  # noqa: F401
 from . import train_state  # noqa: F401
 from . import eval_generation  # noqa: F401

@@ -317,6 +317,12 @@ class ImagePreprocessArgs(C.Structure):
                 ("std0", C.c_float), ("std1", C.c_float), ("std2", C.c_float), ("y_f32", vp), ("y_u8", vp)]
 
 
+class TrainSampleArgs(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("rank", C.c_int), ("purpose", C.c_int), ("B", C.c_int64),
+                ("per_sample", C.c_int64), ("elem_base", C.c_uint64), ("N", C.c_int), ("clean", vp), ("sqrt_acp", vp),
+                ("sqrt_1m_acp", vp), ("timesteps_in", vp), ("timesteps_out", vp), ("noise", vp), ("noisy", vp)]
+
+
 # every symbol include/phendiff_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pd_abi_version": (C.c_int, []),
@@ -381,6 +387,7 @@ SYMBOLS = {
     "pd_pool2d": (C.c_int, [C.POINTER(Pool2dArgs), vp]),
     "pd_fc_f32": (C.c_int, [C.POINTER(FcF32Args), vp]),
     "pd_image_preprocess": (C.c_int, [C.POINTER(ImagePreprocessArgs), vp]),
+    "pd_train_sample": (C.c_int, [C.POINTER(TrainSampleArgs), vp]),
     "pd_graph_begin": (C.c_int, [vp]),
     "pd_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
     "pd_graph_launch": (C.c_int, [vp, vp]),

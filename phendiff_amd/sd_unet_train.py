@@ -569,6 +569,11 @@ class SDUNetTrainer(UNetTrainer):
         return super().step(noisy, timesteps, clean, noise, class_labels=class_labels, class_emb=None, lr=lr, group=group,
                             overlap=overlap, bucket_bytes=bucket_bytes)
 
+    def step_clean(self, clean, class_labels, **step_kwargs):
+        """:meth:`step` from the clean LATENTS alone: the attached sampler draws (noise, timesteps, noisy) on the device."""
+        noise, timesteps, noisy = self._require_sampler("step_clean").sample(clean)
+        return self.step(noisy, timesteps, clean, noise, class_labels, **step_kwargs)
+
     # ---- components_to_train autoencoder: the step starts from images --------------------------------------------------------
     def _bind_vae_weights(self):
         """The VAE's kernel-layout weights the trainer's encoder plans, gradient-layout set and re-packer are bound to: rebuilt
@@ -664,16 +669,35 @@ class SDUNetTrainer(UNetTrainer):
         self._keep_images = (x, moments, pn, nz, latents, noisy, out, dout, sa, sb, ts, labels, ehs)
         return loss, latents
 
-    def step_images(self, images, timesteps, noise, class_labels, posterior_noise=None, unconditional: bool = False,
+    def step_images(self, images, timesteps=None, noise=None, class_labels=None, posterior_noise=None, unconditional: bool = False,
                     lr: Optional[float] = None, group=None, overlap: bool = True, bucket_bytes: int = 64 << 20):
         """One optimisation step from IMAGES (``utils_training.py:237-256``: the batch is encoded inside the step): with a training
         autoencoder, :meth:`images_forward_backward`, then the bucketed gradient all-reduce over the trainable runs of the flat buffer
         (VAE segments included; never-graded ones, like frozen ones, are not exchanged), the joint clip over all trained parameters,
         AdamW + EMA and the in-place re-pack of the UNet's and the encoder's kernel-layout weights.  With a frozen autoencoder
         (``pipeline.vae.requires_grad_(False)``): encode -> sample -> add_noise -> :meth:`step`, i.e. today's step.
-        ``noise`` / ``posterior_noise``: (B, latent, H/8, W/8); the posterior noise is drawn on the device when None."""
+        ``noise`` / ``posterior_noise``: (B, latent, H/8, W/8); the posterior noise is drawn on the device when None.
+        With an attached sampler (``attach_sampler``) ``timesteps``, ``noise`` and ``posterior_noise`` may be None: the sampler draws the
+        posterior noise first (``randn``), then noise and timesteps, each consuming one of its steps."""
         check_training_images(getattr(self, "vae", None), images)
         vae = self.vae
+        sampler = getattr(self, "sampler", None)
+        if sampler is not None and (timesteps is None or noise is None):
+            nlev = len(vae.config.block_out_channels)
+            shape = (images.shape[0], vae.config.latent_channels, images.shape[2] >> (nlev - 1), images.shape[3] >> (nlev - 1))
+            if posterior_noise is None:
+                posterior_noise = sampler.randn(shape)
+            if not self._vae_trains:
+                latents = vae.encode(images).latent_dist.sample(noise=posterior_noise, scale=float(vae.config.scaling_factor))
+                nz, timesteps, noisy = sampler.sample(latents, timesteps=timesteps)
+                if noise is not None:       # the caller's noise with drawn timesteps
+                    nz = noise.to(device=latents.device, dtype=torch.float32)
+                    noisy = self.scheduler.add_noise(latents, nz, timesteps)
+                return self.step(noisy, timesteps, latents, nz, class_labels, unconditional=unconditional, lr=lr, group=group,
+                                 overlap=overlap, bucket_bytes=bucket_bytes)
+            nz, ts = sampler.sample_noise(shape)
+            noise = nz if noise is None else noise
+            timesteps = ts if timesteps is None else timesteps
         if not self._vae_trains:
             sf = float(vae.config.scaling_factor)
             latents = vae.encode(images).latent_dist.sample(noise=posterior_noise, scale=sf)

@@ -5,7 +5,8 @@ writes under ``<run>/checkpoints/step_<n>`` (``utils_misc.py:322-347``) and read
     step_<n>/pytorch_model.bin        unet.state_dict()                     (diffusers parameter names)
     step_<n>/optimizer.bin            torch.optim.AdamW.state_dict()        (parameters indexed in unet.parameters() order)
     step_<n>/scheduler.bin            LambdaLR.state_dict()                 (cosine schedule with warm-up, train.py:298-303)
-    step_<n>/random_states_<rank>.pkl python / numpy / torch / torch.cuda RNG states
+    step_<n>/random_states_<rank>.pkl python / numpy / torch / torch.cuda RNG states (+ the device sampler's seed / rank / step when a
+                                      trainer has one attached: an extra key accelerate's loader ignores)
     step_<n>/pytorch_model_2.bin      class_embedding.state_dict()          (StableDiffusion runs: accelerate numbers the prepared
                                       models unet, vae, class_embedding -- train.py:318-326; the frozen VAE is not the trainer's)
     step_<n>/custom_checkpoint_<k>.pkl diffusers EMAModel.state_dict() per trained module (accelerate's slot for registered objects; the
@@ -27,6 +28,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+DEVICE_SAMPLER_KEY = "phendiff_device_sampler"      # entry of random_states_<rank>.pkl: DeviceTrainingSampler.state_dict()
 ADAMW_GROUP_DEFAULTS = dict(amsgrad=False, foreach=None, maximize=False, capturable=False, differentiable=False, fused=None)
 
 
@@ -168,8 +170,11 @@ def save_state(trainer, output_dir: str, rank: int = 0, base_lr: Optional[float]
                                        current_lr if current_lr is not None else opt.lr), os.path.join(output_dir, "scheduler.bin"))
     if getattr(opt, "scaler", None) is not None:          # --mixed_precision fp16: accelerate writes the GradScaler's state_dict as scaler.pt
         torch.save(opt.scaler.state_dict(), os.path.join(output_dir, "scaler.pt"))
+    states = random_states()
+    if getattr(trainer, "sampler", None) is not None:     # the device sampler's (seed, rank, step): an extra entry, only when one is attached
+        states[DEVICE_SAMPLER_KEY] = trainer.sampler.state_dict()
     with open(os.path.join(output_dir, f"random_states_{rank}.pkl"), "wb") as f:
-        pickle.dump(random_states(), f)
+        pickle.dump(states, f)
     if opt.ema is not None:
         for slot, (_, mod, prefix) in enumerate(mods):       # one EMAModel per trained module (train.py:224-241)
             mnames = [prefix + n for n, _ in mod.named_parameters() if prefix + n in trainer.params]
@@ -233,7 +238,10 @@ def load_state(trainer, input_dir: str, rank: int = 0) -> dict:
     rs = os.path.join(input_dir, f"random_states_{rank}.pkl")
     if os.path.exists(rs):
         with open(rs, "rb") as f:
-            restore_random_states(pickle.load(f))
+            states = pickle.load(f)
+        restore_random_states(states)
+        if getattr(trainer, "sampler", None) is not None and DEVICE_SAMPLER_KEY in states:      # (older checkpoints lack the entry)
+            trainer.sampler.load_state_dict(states[DEVICE_SAMPLER_KEY])
     trainer.refresh_weights()
     sched = os.path.join(input_dir, "scheduler.bin")
     return torch.load(sched, map_location="cpu") if os.path.exists(sched) else {}

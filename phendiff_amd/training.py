@@ -56,11 +56,118 @@ class UnconditionalStepFlags:
         return bool(torch.rand(1, generator=self.g).item() < self.p)
 
 
+class DeviceTrainingSampler:
+    """The per-step sampling of ``perform_training_epoch`` (utils_training.py:244-256) drawn ON the device by one ``pd_train_sample``
+    launch: no host ``randn``, no H2D copy, no separate ``randint`` / ``pd_add_noise``.  A counter-based stream (Philox4x32-10, defined in
+    ``include/phendiff_hip.h``): every value depends only on (seed, step, rank, element index), so a run is reproducible across batch
+    splits, launch geometry, data-parallel ranks and checkpoint resume (``state_dict``: seed, rank, step).  It is NOT torch's CPU stream
+    and NOT torch's device Philox layout -- a run that must reproduce the reference's draws keeps :func:`sample_training_inputs`' default.
+
+    ``rank``: None = "not chosen" (0 until a trainer's ``attach_sampler`` sets its group rank); an int pins it.  Every draw (``sample``,
+    ``sample_noise``, ``randn``) consumes one step."""
+
+    PURPOSE_NOISE, PURPOSE_RANDN = 0, 2
+
+    def __init__(self, scheduler, seed: int, device, rank: Optional[int] = None):
+        if torch.device(device).type != "cuda":
+            raise L.PhenDiffHipError("DeviceTrainingSampler draws on MI355X only (no CPU fallback)")
+        self.scheduler, self.device = scheduler, torch.device(device)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.rank_pinned = rank is not None
+        self.rank = int(rank or 0)
+        if not 0 <= self.rank < 4096:
+            raise ValueError(f"DeviceTrainingSampler: rank {self.rank} outside [0, 4096)")
+        self._step = 0
+        self._acp = None
+        self._tables = None
+
+    @property
+    def step(self) -> int:
+        return self._step
+
+    def bind_rank(self, rank: int):
+        """A trainer's group rank, unless the sampler was built with one."""
+        if not self.rank_pinned:
+            if not 0 <= int(rank) < 4096:
+                raise ValueError(f"DeviceTrainingSampler: rank {rank} outside [0, 4096)")
+            self.rank = int(rank)
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "rank": self.rank, "step": self._step}
+
+    def load_state_dict(self, sd: dict):
+        self.seed, self.rank, self._step = int(sd["seed"]), int(sd["rank"]), int(sd["step"])
+
+    def tables(self):
+        """sqrt(alpha_bar), sqrt(1 - alpha_bar): host-computed fp32 (the arithmetic of ``add_noise`` / ``DiffusionLoss``), device resident;
+        rebuilt when the scheduler's ``alphas_cumprod`` object changes."""
+        acp = self.scheduler.alphas_cumprod
+        if self._tables is None or self._acp is not acp:
+            a = acp.detach().float().cpu()
+            self._tables = ((a ** 0.5).contiguous().to(self.device), ((1 - a) ** 0.5).contiguous().to(self.device))
+            self._acp = acp
+        return self._tables
+
+    def _launch(self, purpose, B, per_sample, noise, clean=None, noisy=None, timesteps_in=None, timesteps_out=None, elem_base=0):
+        sa, sb = self.tables() if (clean is not None or timesteps_out is not None) else (None, None)
+        a = L.TrainSampleArgs(seed=self.seed, step=self._step, rank=self.rank, purpose=purpose, B=B, per_sample=per_sample,
+                              elem_base=elem_base, N=int(self.scheduler.config.num_train_timesteps), clean=L.ptr(clean),
+                              sqrt_acp=L.ptr(sa), sqrt_1m_acp=L.ptr(sb), timesteps_in=L.ptr(timesteps_in),
+                              timesteps_out=L.ptr(timesteps_out), noise=noise.data_ptr(), noisy=L.ptr(noisy))
+        L.check(L.lib().pd_train_sample(C.byref(a), torch.cuda.current_stream(self.device).cuda_stream), "pd_train_sample")
+        self._step += 1
+
+    def _on_device(self, t, what):
+        if not t.is_cuda or t.device != self.device:
+            raise L.PhenDiffHipError(f"DeviceTrainingSampler: {what} must live on {self.device} (no CPU fallback)")
+
+    @torch.no_grad()
+    def sample(self, clean: torch.Tensor, timesteps: Optional[torch.Tensor] = None):
+        """(noise, timesteps, noisy) for one batch of clean samples: the tuple :func:`sample_training_inputs` returns.  One launch, then
+        ``step += 1``.  ``timesteps`` (int64 [B]): use these instead of drawing."""
+        self._on_device(clean, "clean")
+        x = clean.contiguous().float()
+        B = x.shape[0]
+        noise, noisy = torch.empty_like(x), torch.empty_like(x)
+        if timesteps is not None:
+            ts = timesteps.to(device=self.device, dtype=torch.long).contiguous()
+            self._launch(self.PURPOSE_NOISE, B, x[0].numel(), noise, clean=x, noisy=noisy, timesteps_in=ts)
+        else:
+            ts = torch.empty(B, dtype=torch.long, device=self.device)
+            self._launch(self.PURPOSE_NOISE, B, x[0].numel(), noise, clean=x, noisy=noisy, timesteps_out=ts)
+        return noise, ts, noisy
+
+    @torch.no_grad()
+    def sample_noise(self, shape):
+        """(noise, timesteps) of the step :meth:`sample` would draw for a batch of this shape, without the clean samples (they do not
+        exist yet when the autoencoder trains: the latents are encoded inside the step)."""
+        shape = tuple(int(v) for v in shape)
+        noise = torch.empty(shape, dtype=torch.float32, device=self.device)
+        ts = torch.empty(shape[0], dtype=torch.long, device=self.device)
+        self._launch(self.PURPOSE_NOISE, shape[0], noise[0].numel(), noise, timesteps_out=ts)
+        return noise, ts
+
+    @torch.no_grad()
+    def randn(self, shape):
+        """Standard normals of ``shape`` (fp32) from the ``posterior_noise`` / plain-randn purpose of the stream; consumes a step."""
+        shape = tuple(int(v) for v in shape)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if out.numel():
+            self._launch(self.PURPOSE_RANDN, 1, out.numel(), out)
+        return out
+
+    def randn_like(self, t: torch.Tensor):
+        return self.randn(t.shape)
+
+
 @torch.no_grad()
 def sample_training_inputs(clean_images: torch.Tensor, scheduler, cpu_generator: Optional[torch.Generator] = None,
-                           device_generator: Optional[torch.Generator] = None):
+                           device_generator: Optional[torch.Generator] = None, sampler: Optional[DeviceTrainingSampler] = None):
     """perform_training_epoch's per-step sampling: noise on the CPU RNG then H2D (utils_training.py:244), timesteps
-    ``randint(0, N, (B,))`` on the device (:247-252), ``noisy = add_noise(clean, noise, t)`` (:256, ``pd_add_noise``)."""
+    ``randint(0, N, (B,))`` on the device (:247-252), ``noisy = add_noise(clean, noise, t)`` (:256, ``pd_add_noise``).
+    ``sampler``: a :class:`DeviceTrainingSampler` draws all three in one launch instead (its own stream: not the generators')."""
+    if sampler is not None:
+        return sampler.sample(clean_images)
     B = clean_images.shape[0]
     noise = torch.randn(clean_images.shape, generator=cpu_generator).to(clean_images.device)
     timesteps = torch.randint(0, scheduler.config.num_train_timesteps, (B,), device=clean_images.device,

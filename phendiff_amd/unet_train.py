@@ -1080,6 +1080,29 @@ class UNetTrainer:
         self.refresh_weights()
         return loss
 
+    def attach_sampler(self, sampler, group=None):
+        """Draw the step's noise and timesteps on the device (:class:`phendiff_amd.training.DeviceTrainingSampler`, one
+        ``pd_train_sample`` launch): :meth:`step_clean` then starts from the clean batch alone.  The sampler takes this process's rank
+        in ``group`` unless it was built with one, so data-parallel ranks see distinct noise and timesteps (as in the reference, where
+        every rank's generator differs).  ``save_state`` / ``load_state`` carry its (seed, rank, step).  ``None`` detaches."""
+        if sampler is not None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                sampler.bind_rank(dist.get_rank(group))
+        self.sampler = sampler
+        return sampler
+
+    def _require_sampler(self, what):
+        sampler = getattr(self, "sampler", None)
+        if sampler is None:
+            raise L.PhenDiffHipError(f"{what} needs a DeviceTrainingSampler (attach_sampler)")
+        return sampler
+
+    def step_clean(self, clean, class_labels=None, class_emb=None, **step_kwargs):
+        """:meth:`step` from the clean batch alone: the attached sampler draws (noise, timesteps, noisy) on the device."""
+        noise, timesteps, noisy = self._require_sampler("step_clean").sample(clean)
+        return self.step(noisy, timesteps, clean, noise, class_labels=class_labels, class_emb=class_emb, **step_kwargs)
+
     def _optimizer_step(self, lr):
         # unconditional step (class_emb = zeros, utils_training.py:510-516): the class table's .grad stays None in the
         # reference, torch's AdamW skips it (no decay, no moment update, no step count) -- EMA still steps
