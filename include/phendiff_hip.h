@@ -36,7 +36,8 @@ extern "C" {
  * pd_resize_tf1, pd_conv_rect, pd_pool2d, pd_fc_f32 (the evaluation metrics' feature extractor); pd_pack_weight_args.dst2 / dst2_ct_stride;
  * 8 = pd_geglu_bwd_args.sums / sum_splits / B, pd_layernorm_bwd_args.dxsum (bias gradients without a pass over dY), pd_upsample_phase_weights,
  * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
- * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample. */
+ * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample, pd_sample_stats
+ * (+ pd_sample_stats_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -843,6 +844,54 @@ typedef struct {
   float* noise; float* noisy;
 } pd_train_sample_args;
 int pd_train_sample(const pd_train_sample_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_sample_stats (added under ABI 8): per-sample diagnostics of a batch that stays on the device -- what check_Gaussianity
+ * (utils_Img2Img.py:79-93: mean, std, a 100-bin histogram on (-3, 3), scipy's normaltest) and Lp_loss (:245-270) need from an inverted batch
+ * or a regenerated one, reduced to B x (PD_SAMPLE_STATS_FIELDS + bins) numbers.  csrc/sample_stats.hip; host side phendiff_amd.diagnostics
+ * (check_gaussianity, sample_distances; normaltest_from_moments turns n, m2, m3, m4 into K^2 and its p-value).
+ *   x: contiguous [B][n] of `dtype` (PD_F32 / PD_BF16 / PD_F16); sample b starts at element b * n, whatever its alignment.  Every element is
+ *      widened to fp64 (exactly) before any arithmetic.
+ *   y (may be null): same dtype; y_sample_stride = n for one y per sample, 0 for one y[n] shared by all samples (Lp_loss's (N,C,H,W) / (C,H,W)).
+ *   bins > 0: edges = bins + 1 ascending fp64 values on the device (np.linspace(lo, hi, bins + 1) for np.histogram's uniform bins) and hist
+ *      [B][bins] uint32.  Element v falls in bin k when edges[k] <= v < edges[k + 1]; the last bin also takes v == edges[bins]; anything else
+ *      (a NaN, an infinity, a value outside) falls in no bin.  The bin is guessed as (int)((v - edges[0]) * bins / (edges[bins] - edges[0])) in
+ *      fp64 and then moved until the comparisons with edges[k] / edges[k + 1] hold (the guess alone is one off at some edges), so with linspace
+ *      edges the counts equal np.histogram(x64, bins, (lo, hi)) count for count.  bins <= PD_SAMPLE_STATS_MAX_BINS = 4096 (edges and counts of
+ *      one workgroup live in LDS: 12 * bins + 8 bytes); n < 2^32 (the counts are uint32).  hist is zeroed by a launch of the call's own.
+ *   stats [B][PD_SAMPLE_STATS_FIELDS] fp64, every field written by every call:
+ *      PD_SS_SUM, PD_SS_MIN, PD_SS_MAX, PD_SS_NONFINITE: sum of the elements (mean = sum / n), smallest and largest element (a NaN is passed
+ *        over; +inf / -inf when every element is a NaN), number of NaN / infinite elements.
+ *      PD_SS_M2, PD_SS_M3, PD_SS_M4: central moments sum(d^k) / n with d = x - sum / n in fp64 (two passes: no cancellation for a shifted
+ *        sample).  They, and the sum, are NaN / infinite when PD_SS_NONFINITE > 0 -- the IEEE result, as numpy's would be.
+ *      PD_SS_ERR_L1, PD_SS_ERR_SQ, PD_SS_ERR_MAX: sum |e|, sum e^2, max |e| with e = x - y in fp64; 0 when y is null.
+ *   workspace: pd_sample_stats_workspace(B, n, bins) bytes (the per-chunk partials: 80 bytes per PD_SAMPLE_STATS_CHUNK elements of a sample;
+ *      0 for sizes the call refuses), 8-byte aligned, contents irrelevant before and after; workspace_bytes states what the caller allocated.
+ * Launches: [zero hist], pass A (per-chunk sum / min / max / non-finite), a fold per sample, pass B (per-chunk sums of d^2 d^3 d^4, the error
+ * sums, the histogram in LDS integer atomics flushed with global integer atomic adds), a fold per sample; no host synchronisation, capturable.
+ * Every floating-point reduction runs in a fixed order (lane, wave, workgroup, chunk index) and the element -> lane map depends on the index
+ * within the sample only (16-byte loads where a slot is aligned and whole, element loads elsewhere, same values to the same lane): a
+ * sample's stats and hist are bitwise reproducible and do not depend on B, on its row in the batch or on the pointers' alignment.
+ * Refused before any launch: null args / x / stats / workspace, a dtype outside the three, bins < 0, bins > 0 without edges or hist, a
+ * workspace_bytes below the query's (PD_ERR_ARG); B, n <= 0, bins > PD_SAMPLE_STATS_MAX_BINS, y_sample_stride outside {0, n}, B * n >= 2^62,
+ * n >= 2^32 with bins > 0, more than 2^31 - 1 blocks (PD_ERR_SHAPE). */
+#define PD_SAMPLE_STATS_FIELDS 10
+#define PD_SAMPLE_STATS_CHUNK 8192
+#define PD_SAMPLE_STATS_MAX_BINS 4096
+enum { PD_SS_SUM = 0, PD_SS_MIN = 1, PD_SS_MAX = 2, PD_SS_NONFINITE = 3, PD_SS_M2 = 4, PD_SS_M3 = 5, PD_SS_M4 = 6,
+       PD_SS_ERR_L1 = 7, PD_SS_ERR_SQ = 8, PD_SS_ERR_MAX = 9 };
+typedef struct {
+  int dtype, bins;
+  int64_t B, n;
+  int64_t y_sample_stride;
+  const void* x; const void* y;
+  const double* edges;
+  double* stats;
+  uint32_t* hist;
+  void* workspace; size_t workspace_bytes;
+} pd_sample_stats_args;
+size_t pd_sample_stats_workspace(int64_t B, int64_t n, int bins);
+int pd_sample_stats(const pd_sample_stats_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_comm_*: the data-parallel gradient exchange -- DistributedDataParallel's bucketed all-reduce under accelerator.backward(loss)

@@ -15,6 +15,7 @@ from .img2img import (inversion, ddib, inverted_regeneration, classifier_free_gu
 from .configs import UNET_CONFIGS, SCHEDULER_CONFIGS, SD15_UNET_CONFIG  # noqa: F401
 from . import configs  # noqa: F401
 from . import diagnostics  # noqa: F401
+from .diagnostics import check_gaussianity, sample_distances, normaltest_from_moments, GaussianityReport  # noqa: F401
 from .comm import NativeComm  # noqa: F401
 from . import training  # noqa: F401
 from .training import DeviceTrainingSampler  # noqa: F401

@@ -323,6 +323,17 @@ class TrainSampleArgs(C.Structure):
                 ("sqrt_1m_acp", vp), ("timesteps_in", vp), ("timesteps_out", vp), ("noise", vp), ("noisy", vp)]
 
 
+class SampleStatsArgs(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("bins", C.c_int), ("B", C.c_int64), ("n", C.c_int64), ("y_sample_stride", C.c_int64),
+                ("x", vp), ("y", vp), ("edges", vp), ("stats", vp), ("hist", vp), ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+# pd_sample_stats: the stats row (PD_SS_*), the chunk a workgroup takes and the LDS histogram's limit, as the header defines them
+SAMPLE_STATS_FIELDS = ("sum", "min", "max", "nonfinite", "m2", "m3", "m4", "err_l1", "err_sq", "err_max")
+SAMPLE_STATS_CHUNK = 8192
+SAMPLE_STATS_MAX_BINS = 4096
+
+
 # every symbol include/phendiff_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pd_abi_version": (C.c_int, []),
@@ -388,6 +399,8 @@ SYMBOLS = {
     "pd_fc_f32": (C.c_int, [C.POINTER(FcF32Args), vp]),
     "pd_image_preprocess": (C.c_int, [C.POINTER(ImagePreprocessArgs), vp]),
     "pd_train_sample": (C.c_int, [C.POINTER(TrainSampleArgs), vp]),
+    "pd_sample_stats": (C.c_int, [C.POINTER(SampleStatsArgs), vp]),
+    "pd_sample_stats_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "pd_graph_begin": (C.c_int, [vp]),
     "pd_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
     "pd_graph_launch": (C.c_int, [vp, vp]),
