@@ -21,9 +21,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .packing import pack_conv_weight, upsample_phase_weights_stacked
 from .training import mark_requires_grad_calls
 from .unet import UNet2DOutput, UNetPlan, _Block, _DT, _Op, _Resnet, _Sampler, _TimestepEmbedding
+from .weight_layout import WeightSet
 
 ATTN_HEAD_DIMS = (40, 64, 80, 160)      # pd_attn_d64 for 64, pd_attn_hd for the SD 1.x widths
 
@@ -296,80 +296,48 @@ class SDUNet2DConditionModel(nn.Module):
 
 
 # ---- kernel-layout weights ----------------------------------------------------------------------------------------------
-class _SDPackedWeights:
+class _SDPackedWeights(WeightSet):
     def __init__(self, m: SDUNet2DConditionModel, device):
-        self.code, self.tdt = _DT[m.compute_dtype]
-        dev = device
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        pk = lambda w, cp=None: pack_conv_weight(w.detach().to(device=dev, dtype=torch.float32), self.tdt, cp)
-        lin = lambda w: w.detach() if w.ndim == 4 else w.detach()[:, :, None, None]      # (proj_in / proj_out of SD 1.x are 1x1 convs already)
-        c = m.config
+        self.code, tdt = _DT[m.compute_dtype]
+        super().__init__(device, tdt)
+        f32, pk = self.f32, self.pack
         # conv_in over the latents padded to 32 NHWC channels (zero weights on the padding)
-        wi = torch.zeros((c.block_out_channels[0], 32, 3, 3), dtype=torch.float32, device=dev)
-        wi[:, :c.in_channels] = f32(m.conv_in.weight)
-        self.conv_in_w, self.conv_in_b = pk(wi), f32(m.conv_in.bias)
-        te = m.time_embedding
-        self.w1T, self.b1 = f32(te.linear_1.weight.t()), f32(te.linear_1.bias)
-        self.w2T, self.b2 = f32(te.linear_2.weight.t()), f32(te.linear_2.bias)
+        self.conv_in_w, self.conv_in_b = self.padded(m.conv_in, m.config.block_out_channels[0], 32)
+        self.time_mlp_and_conv_out(m)
         self.class_table = None
         self.resnets, self.transformers, self.samplers = {}, {}, {}
-        proj_w, proj_b, off = [], [], 0
-        maxc = 0
+        res, maxc = [], 0
         for name, r in m.named_modules():
             if isinstance(r, _Resnet):
-                e = SimpleNamespace(cin=r.in_channels, cout=r.out_channels, eps=r.norm1.eps)
-                e.g1, e.be1, e.g2, e.be2 = f32(r.norm1.weight), f32(r.norm1.bias), f32(r.norm2.weight), f32(r.norm2.bias)
-                e.w1, e.b1, e.w2, e.b2 = pk(r.conv1.weight), f32(r.conv1.bias), pk(r.conv2.weight), f32(r.conv2.bias)
-                e.fused_shortcut = r.conv_shortcut is not None
-                if e.fused_shortcut:
-                    ws = pk(r.conv_shortcut.weight)
-                    ct = e.w2.shape[0]
-                    e.w2 = torch.cat([e.w2.reshape(ct, -1, 64, 8), ws.reshape(ct, -1, 64, 8)], 1).contiguous()
-                    e.b2 = e.b2 + f32(r.conv_shortcut.bias)
-                e.temb_off = off
-                off += e.cout
-                proj_w.append(r.time_emb_proj.weight.detach())
-                proj_b.append(r.time_emb_proj.bias.detach())
-                self.resnets[name] = e
+                self.resnets[name] = self.resnet(r)
+                res.append((r, self.resnets[name]))
             elif isinstance(r, _Transformer2D):
                 blk = r.transformer_blocks[0]
                 ch = r.proj_in.weight.shape[0]
                 e = SimpleNamespace(heads=r.heads, dim_head=r.dim_head, ch=ch, g=f32(r.norm.weight), be=f32(r.norm.bias), eps=r.norm.eps)
-                e.w_in, e.b_in = pk(lin(r.proj_in.weight)), f32(r.proj_in.bias)
-                e.w_out, e.b_out = pk(lin(r.proj_out.weight)), f32(r.proj_out.bias)
+                e.w_in, e.b_in = pk(r.proj_in.weight), f32(r.proj_in.bias)        # (proj_in / proj_out of SD 1.x are 1x1 convs already)
+                e.w_out, e.b_out = pk(r.proj_out.weight), f32(r.proj_out.bias)
                 for i, nrm in enumerate((blk.norm1, blk.norm2, blk.norm3), 1):
                     setattr(e, f"ln{i}", (f32(nrm.weight), f32(nrm.bias), nrm.eps))
                 a1, a2 = blk.attn1, blk.attn2
-                e.wqkv1 = pk(lin(torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0)))
-                e.wo1, e.bo1 = pk(lin(a1.to_out[0].weight)), f32(a1.to_out[0].bias)
-                e.wq2 = pk(lin(a2.to_q.weight))
-                e.wkv2 = pk(lin(torch.cat([a2.to_k.weight, a2.to_v.weight], 0)))
-                e.wo2, e.bo2 = pk(lin(a2.to_out[0].weight)), f32(a2.to_out[0].bias)
-                e.wff1, e.bff1 = pk(lin(blk.ff.net[0].proj.weight)), f32(blk.ff.net[0].proj.bias)
+                e.wqkv1 = pk(torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0))
+                e.wo1, e.bo1 = pk(a1.to_out[0].weight), f32(a1.to_out[0].bias)
+                e.wq2 = pk(a2.to_q.weight)
+                e.wkv2 = pk(torch.cat([a2.to_k.weight, a2.to_v.weight], 0))
+                e.wo2, e.bo2 = pk(a2.to_out[0].weight), f32(a2.to_out[0].bias)
+                e.wff1, e.bff1 = pk(blk.ff.net[0].proj.weight), f32(blk.ff.net[0].proj.bias)
                 # inference copy for the fused GEGLU epilogue of pd_linear: value rows in the even, gate rows in the odd 32-row tiles
                 wf = blk.ff.net[0].proj.weight
-                pv, pg = pk(lin(wf[:4 * ch])), pk(lin(wf[4 * ch:]))
+                pv, pg = pk(wf[:4 * ch]), pk(wf[4 * ch:])
                 e.wff1_glu = torch.stack([pv, pg], 1).reshape(2 * pv.shape[0], *pv.shape[1:]).contiguous()
-                e.wff2, e.bff2 = pk(lin(blk.ff.net[2].weight)), f32(blk.ff.net[2].bias)
+                e.wff2, e.bff2 = pk(blk.ff.net[2].weight), f32(blk.ff.net[2].bias)
                 maxc = max(maxc, 8 * ch)
                 self.transformers[name] = e
             elif isinstance(r, _Sampler):
-                self.samplers[name] = SimpleNamespace(w=pk(r.conv.weight), b=f32(r.conv.bias), padding=r.padding)
-                if ".upsamplers." in name:      # Upsample2D as four 2x2 phase convolutions (UNetPlan._upconv_subpixel; inference plans)
-                    # (w4_src: the four fp32 phase kernels stacked on the device; the fine-tuning re-pack refreshes them every step)
-                    self.samplers[name].w4_src = upsample_phase_weights_stacked(r.conv.weight.detach().to(device=dev, dtype=torch.float32))
-                    self.samplers[name].w4 = tuple(pk(self.samplers[name].w4_src[p]) for p in range(4))
-        self.proj_dim = off
-        self.wpT = f32(torch.cat(proj_w, 0).t())
-        self.bp = f32(torch.cat(proj_b, 0))
-        self.zero_bias = torch.zeros(max(maxc, 64) + 64, dtype=torch.float32, device=dev)
-        self.gn_out = (f32(m.conv_norm_out.weight), f32(m.conv_norm_out.bias), m.conv_norm_out.eps)
-        co = m.conv_out.weight.shape[0]
-        self.conv_out_pad = ((co + 31) // 32) * 32
-        self.conv_out_w = pk(m.conv_out.weight, self.conv_out_pad)
-        b = torch.zeros(self.conv_out_pad, dtype=torch.float32, device=dev)
-        b[:co] = f32(m.conv_out.bias)
-        self.conv_out_b = b
+                # Upsample2D as four 2x2 phase convolutions (UNetPlan._upconv_subpixel); the fine-tuning re-pack refreshes them every step
+                self.samplers[name] = self.sampler(r, phases=".upsamplers." in name)
+        self.stack_time_emb_proj(res)
+        self.zero_bias = torch.zeros(max(maxc, 64) + 64, dtype=torch.float32, device=device)
 
 
 class SDUNetPlan(UNetPlan):
@@ -380,9 +348,6 @@ class SDUNetPlan(UNetPlan):
         super().__init__(m, w, B, H, W, device)
 
     # ---- emitters for the Transformer2DModel additions ---------------------------------------------------------------
-    def _esz(self):
-        return 4 if self.code == L.PD_F32 else 2
-
     def _layernorm(self, x, ln):
         gamma, beta, eps = ln
         B, h, w, ch = x.shape

@@ -18,11 +18,11 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib as L
-from .packing import dgrad_weight, pack_conv_weight, upsample_phase_weights_stacked
 from .sd_unet import (CustomEmbedding, SDUNet2DConditionModel, SDUNetPlan, _SDPackedWeights, _Transformer2D,
                       class_emb_to_encoder_hidden_states)
-from .unet import _Resnet, _Sampler, _copy_into
-from .unet_train import UNetTrainer, UNetTrainPlan, _contiguous_after, run_pack_jobs
+from .unet import _Resnet, _Sampler
+from .unet_train import UNetTrainer, UNetTrainPlan
+from .weight_layout import Repacker, WeightSet, contiguous_after as _contiguous_after, pad32, require_adjacent, require_alias
 
 
 EMB_NAME = "class_embedding.inner_module.weight"
@@ -56,41 +56,32 @@ def sd_training_param_order(m: SDUNet2DConditionModel) -> List[Tuple[str, torch.
     return out
 
 
-class SDTrainWeights:
+class SDTrainWeights(WeightSet):
     """Input-gradient weights in ``pd_conv``'s packed layout (W'[ci][co][ky][kx] = W[co][ci][K-1-ky][K-1-kx])."""
 
     def __init__(self, m: SDUNet2DConditionModel, device, tdt):
         # fp16 (round 5): `--mixed_precision fp16` fine-tuning (args_parser.py:381-390) under training.LossScaler, set up by SDUNetTrainer
-        self.tdt, self.device = tdt, device
-        pk = lambda w, cp=None: pack_conv_weight(dgrad_weight(w.detach().to(device=device, dtype=torch.float32)), tdt, cp)
-        lin = lambda w: w.detach()[:, :, None, None]
+        super().__init__(device, tdt, dgrad=True)
+        pk = self.pack
         self.resnets, self.transformers, self.samplers = {}, {}, {}
         for name, mod in m.named_modules():
             if isinstance(mod, _Resnet):
-                e = SimpleNamespace(w1d=pk(mod.conv1.weight), w2d=pk(mod.conv2.weight))
-                if mod.conv_shortcut is not None:
-                    e.wsd = pk(mod.conv_shortcut.weight)
-                self.resnets[name] = e
+                self.resnets[name] = self.resnet(mod)
             elif isinstance(mod, _Transformer2D):
                 blk = mod.transformer_blocks[0]
                 a1, a2 = blk.attn1, blk.attn2
                 self.transformers[name] = SimpleNamespace(
-                    w_in_d=pk(lin(mod.proj_in.weight)), w_out_d=pk(lin(mod.proj_out.weight)),
-                    wqkv1_d=pk(lin(torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0))),
-                    wo1_d=pk(lin(a1.to_out[0].weight)), wq2_d=pk(lin(a2.to_q.weight)),
-                    wkv2_d=pk(lin(torch.cat([a2.to_k.weight, a2.to_v.weight], 0))), wo2_d=pk(lin(a2.to_out[0].weight)),
-                    wff1_d=pk(lin(blk.ff.net[0].proj.weight)), wff2_d=pk(lin(blk.ff.net[2].weight)))
+                    w_in_d=pk(mod.proj_in.weight), w_out_d=pk(mod.proj_out.weight),
+                    wqkv1_d=pk(torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0)),
+                    wo1_d=pk(a1.to_out[0].weight), wq2_d=pk(a2.to_q.weight),
+                    wkv2_d=pk(torch.cat([a2.to_k.weight, a2.to_v.weight], 0)), wo2_d=pk(a2.to_out[0].weight),
+                    wff1_d=pk(blk.ff.net[0].proj.weight), wff2_d=pk(blk.ff.net[2].weight))
             elif isinstance(mod, _Sampler):
-                self.samplers[name] = SimpleNamespace(wd=pk(mod.conv.weight))
-                if ".upsamplers." in name:      # input-gradient weights of the four sub-pixel phases (UNetTrainPlan's "up" backward, pd_conv phase_in)
-                    k4 = upsample_phase_weights_stacked(mod.conv.weight.detach().to(device=device, dtype=torch.float32))
-                    self.samplers[name].wd4 = tuple(pk(k4[p]) for p in range(4))
-        co = m.conv_out.weight.shape[0]
-        wo = torch.zeros((((co + 31) // 32) * 32,) + tuple(m.conv_out.weight.shape[1:]), dtype=torch.float32, device=device)
-        wo[:co] = m.conv_out.weight.detach().to(device=device, dtype=torch.float32)
-        self.conv_out_d = pk(wo)
+                self.samplers[name] = self.sampler(mod, phases=".upsamplers." in name)
+        co, cc = m.conv_out.weight.shape[:2]
+        self.conv_out_d = self.padded(m.conv_out, pad32(co), cc)
         # conv_in's input gradient (the latent gradient of the gradient-guided transfer): block_out_channels[0] -> 4 channels (pad 32)
-        self.conv_in_d = pk(m.conv_in.weight, 32)
+        self.conv_in_d = self.padded(m.conv_in, m.conv_in.weight.shape[0], 32)
 
 
 class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
@@ -339,106 +330,51 @@ def check_training_images(vae, images):
         raise L.PhenDiffHipError("phendiff_amd trains on MI355X only (no CPU fallback): move the images to 'cuda'")
 
 
-class _SDRepacker:
-    """After an optimizer step: fp32 master parameters -> every kernel-layout copy the plans read, IN PLACE
-    (``pd_pack_weight`` launches + a few small fp32 copies).  fp32 vectors the kernels read directly (norm affines, biases)
-    alias the flat master buffer."""
+class _SDRepacker(Repacker):
+    """The SD UNet's re-pack: the ``_SDPackedWeights`` and ``SDTrainWeights`` tensors."""
 
     def __init__(self, m: SDUNet2DConditionModel, w: _SDPackedWeights, tw: SDTrainWeights):
-        self.lib = L.lib()
-        self.jobs, self.small, self.pre = [], [], []
-        self.jobs_device = m.conv_in.weight.device
+        super().__init__(w.code, m.conv_in.weight.device)
         self.w = w
-        code = w.code
-
-        def job(dst, src, cout, cin, k, *, dgrad=0, cout_pad=None, cin_pad=None, ct_stride=None, dst_off=0):
-            cp = cout_pad or ((cout + 31) // 32) * 32
-            ip = cin_pad or ((cin + 31) // 32) * 32
-            per_ct = (ip // 32) * k * k * 2 * 64 * 8
-            self.jobs.append(L.PackWeightArgs(dtype=code, cout=cout, cin=cin, cout_pad=cp, cin_pad=ip, ksize=k,
-                                              src_in=(cout if dgrad else cin), dgrad=dgrad, src=src.data_ptr(),
-                                              dst=dst.data_ptr() + dst_off * dst.element_size(), dst_ct_stride=ct_stride or per_ct))
-
-        def both(dst, dstd, weight, cout, cin, k=1):
-            job(dst, weight, cout, cin, k)
-            job(dstd, weight, cin, cout, k, dgrad=1)
-
-        ci, c0 = m.conv_in.weight.shape[1], m.conv_in.weight.shape[0]
-        job(w.conv_in_w, m.conv_in.weight, c0, ci, 3, cin_pad=32)
-        job(tw.conv_in_d, m.conv_in.weight, ci, c0, 3, dgrad=1, cout_pad=32)
+        pair = self.pair
+        c0, ci = m.conv_in.weight.shape[:2]
+        co, cc = m.conv_out.weight.shape[:2]
+        pair(w.conv_in_w, tw.conv_in_d, m.conv_in.weight, c0, ci, 3, cin_pad=32)
+        res, blk0 = [], None
         for name, mod in m.named_modules():
             if isinstance(mod, _Resnet):
-                e, t = w.resnets[name], tw.resnets[name]
-                cin, cout = mod.in_channels, mod.out_channels
-                job(e.w1, mod.conv1.weight, cout, cin, 3)
-                stride = e.w2[0].numel()
-                job(e.w2, mod.conv2.weight, cout, cout, 3, ct_stride=stride)
-                job(t.w1d, mod.conv1.weight, cin, cout, 3, dgrad=1)
-                job(t.w2d, mod.conv2.weight, cout, cout, 3, dgrad=1)
-                if mod.conv_shortcut is not None:
-                    job(e.w2, mod.conv_shortcut.weight, cout, cin, 1, ct_stride=stride, dst_off=(cout // 32) * 9 * 2 * 512)
-                    job(t.wsd, mod.conv_shortcut.weight, cin, cout, 1, dgrad=1)
-                    b2, bs, dst = mod.conv2.bias, mod.conv_shortcut.bias, e.b2
-                    self.small.append(lambda b2=b2, bs=bs, dst=dst: torch.add(b2.data, bs.data, out=dst))
+                self.resnet(mod, w.resnets[name], tw.resnets[name])
+                res.append(mod)
             elif isinstance(mod, _Transformer2D):
                 e, t = w.transformers[name], tw.transformers[name]
                 blk = mod.transformer_blocks[0]
+                blk0 = blk0 or (e, blk)
                 a1, a2 = blk.attn1, blk.attn2
                 ch, D = e.ch, a2.to_k.weight.shape[1]
-                if not (_contiguous_after(a1.to_q.weight.data, a1.to_k.weight.data) and _contiguous_after(a1.to_k.weight.data, a1.to_v.weight.data)
-                        and _contiguous_after(a2.to_k.weight.data, a2.to_v.weight.data)):
-                    raise ValueError("fused projection weights must be adjacent (use sd_training_param_order)")
-                both(e.w_in, t.w_in_d, mod.proj_in.weight, ch, ch)
-                both(e.w_out, t.w_out_d, mod.proj_out.weight, ch, ch)
-                both(e.wqkv1, t.wqkv1_d, a1.to_q.weight, 3 * ch, ch)
-                both(e.wo1, t.wo1_d, a1.to_out[0].weight, ch, ch)
-                both(e.wq2, t.wq2_d, a2.to_q.weight, ch, ch)
-                both(e.wkv2, t.wkv2_d, a2.to_k.weight, 2 * ch, D)
-                both(e.wo2, t.wo2_d, a2.to_out[0].weight, ch, ch)
-                both(e.wff1, t.wff1_d, blk.ff.net[0].proj.weight, 8 * ch, ch)
+                require_adjacent("fused projection weights must be adjacent (use sd_training_param_order)",
+                                 (a1.to_q.weight, a1.to_k.weight, a1.to_v.weight), (a2.to_k.weight, a2.to_v.weight))
+                pair(e.w_in, t.w_in_d, mod.proj_in.weight, ch, ch)
+                pair(e.w_out, t.w_out_d, mod.proj_out.weight, ch, ch)
+                pair(e.wqkv1, t.wqkv1_d, a1.to_q.weight, 3 * ch, ch)
+                pair(e.wo1, t.wo1_d, a1.to_out[0].weight, ch, ch)
+                pair(e.wq2, t.wq2_d, a2.to_q.weight, ch, ch)
+                pair(e.wkv2, t.wkv2_d, a2.to_k.weight, 2 * ch, D)
+                pair(e.wo2, t.wo2_d, a2.to_out[0].weight, ch, ch)
+                pair(e.wff1, t.wff1_d, blk.ff.net[0].proj.weight, 8 * ch, ch)
                 wf = blk.ff.net[0].proj.weight                       # inference copy: value / gate tiles interleaved
-                tile = (ch // 32) * 2 * 512
-                job(e.wff1_glu, wf.data[:4 * ch], 4 * ch, ch, 1, ct_stride=2 * tile)
-                job(e.wff1_glu, wf.data[4 * ch:], 4 * ch, ch, 1, ct_stride=2 * tile, dst_off=tile)
-                both(e.wff2, t.wff2_d, blk.ff.net[2].weight, ch, 4 * ch)
-            elif isinstance(mod, _Sampler):
-                ch = mod.conv.weight.shape[0]
-                both(w.samplers[name].w, tw.samplers[name].wd, mod.conv.weight, ch, ch, 3)
-                if getattr(w.samplers[name], "w4_src", None) is not None:      # the inference plans' sub-pixel phase kernels follow the weights too
-                    src4, wt = w.samplers[name].w4_src, mod.conv.weight
-                    self.pre.append(lambda src4=src4, wt=wt: upsample_phase_weights_stacked(wt.data, out=src4))
-                    for p in range(4):
-                        job(w.samplers[name].w4[p], src4[p], ch, ch, 2)
-                        job(tw.samplers[name].wd4[p], src4[p], ch, ch, 2, dgrad=1)
-        co, cc = m.conv_out.weight.shape[0], m.conv_out.weight.shape[1]
-        job(w.conv_out_w, m.conv_out.weight, co, cc, 3, cout_pad=w.conv_out_pad)
-        job(tw.conv_out_d, m.conv_out.weight, cc, co, 3, dgrad=1, cin_pad=w.conv_out_pad)
-        te = m.time_embedding
-        res = [mod for _, mod in m.named_modules() if isinstance(mod, _Resnet)]
-        pd_, tdim = w.proj_dim, m.time_embed_dim
-        first = res[0].time_emb_proj
-        self.small += [
-            lambda: w.w1T.copy_(te.linear_1.weight.data.t()),
-            lambda: w.w2T.copy_(te.linear_2.weight.data.t()),
-            lambda: w.wpT.copy_(torch.as_strided(first.weight.data, (pd_, tdim), (tdim, 1)).t()),
-            lambda: w.bp.copy_(torch.as_strided(first.bias.data, (pd_,), (1,))),
-            lambda: w.conv_out_b[:co].copy_(m.conv_out.bias.data),
-        ]
-        tf0 = next(iter(w.transformers.values()))
-        for a, b in ((w.b1, te.linear_1.bias), (w.conv_in_b, m.conv_in.bias), (w.gn_out[0], m.conv_norm_out.weight),
-                     (tf0.ln1[0], next(mod for mod in m.modules() if isinstance(mod, _Transformer2D)).transformer_blocks[0].norm1.weight)):
-            if a.data_ptr() != b.data_ptr():
-                raise RuntimeError("kernel-side fp32 vectors must alias the master parameters (build the packed weights "
-                                   "after the parameters were moved into the flat training buffer)")
+                tile = e.wff1_glu[0].numel()
+                self.job(e.wff1_glu, wf.data[:4 * ch], 4 * ch, ch, 1, ct_stride=2 * tile)
+                self.job(e.wff1_glu, wf.data[4 * ch:], 4 * ch, ch, 1, ct_stride=2 * tile, dst_off=tile)
+                pair(e.wff2, t.wff2_d, blk.ff.net[2].weight, ch, 4 * ch)
+            elif isinstance(mod, _Sampler):      # (the inference plans' sub-pixel phase kernels follow the weights too)
+                self.sampler(mod, w.samplers[name], tw.samplers[name])
+        pair(w.conv_out_w, tw.conv_out_d, m.conv_out.weight, co, cc, 3, cout_pad=w.conv_out_pad)
+        self.time_mlp_and_conv_out(m, w, res[0].time_emb_proj)
+        require_alias([(w.b1, m.time_embedding.linear_1.bias), (w.conv_in_b, m.conv_in.bias), (w.gn_out[0], m.conv_norm_out.weight),
+                       (blk0[0].ln1[0], blk0[1].norm1.weight)])
 
     def run(self, stream):
-        with torch.no_grad():
-            for f in self.pre:
-                f()
-        run_pack_jobs(self.lib, self.jobs, stream, self.__dict__.setdefault("_batch", {}), self.jobs_device)
-        with torch.no_grad():
-            for f in self.small:
-                f()
+        super().run(stream)
         self.w.version = getattr(self.w, "version", 0) + 1      # inference plans drop what they cached of the old weights (cross-attention k / v)
 
 

@@ -19,8 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .packing import pack_conv_weight, upsample_phase_weights, upsample_phase_weights_stacked
 from .training import mark_requires_grad_calls
+from .weight_layout import WeightSet
 
 # compute_dtype -> (pd_dtype, storage dtype).  "fp16": the reference's `--mixed_precision fp16` (args_parser.py:381-390; img2img_comparison.py:57):
 # fp16 storage + MFMA, fp32 accumulate / statistics / softmax; since round 5 it trains too (unet_train.UNetTrainer under training.LossScaler)
@@ -346,24 +346,16 @@ class CustomCondUNet2DModel(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------
-class _PackedWeights:
+class _PackedWeights(WeightSet):
     """Weights in kernel layouts (device).  Built once per model / device / dtype."""
 
     def __init__(self, m: CustomCondUNet2DModel, device):
-        self.code, self.tdt = _DT[m.compute_dtype]
-        dev = device
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.code, tdt = _DT[m.compute_dtype]
+        super().__init__(device, tdt)
+        f32 = self.f32
         self.conv_in_w, self.conv_in_b = f32(m.conv_in.weight), f32(m.conv_in.bias)
-        cin = m.conv_in.weight.shape[1]
-        if cin > 3:
-            raise NotImplementedError("conv_in on the HIP path takes <= 3 input channels (pixel-space UNet)")
-        # conv_in as a 1x1 conv over 32 virtual channels k = ci*9 + ky*3 + kx (pd_conv im2col3 mode)
-        wv = torch.zeros((m.conv_in.weight.shape[0], 32, 1, 1), dtype=torch.float32, device=dev)
-        wv[:, :cin * 9, 0, 0] = f32(m.conv_in.weight).reshape(-1, cin * 9)
-        self.conv_in_wv = pack_conv_weight(wv, self.tdt)
-        te = m.time_embedding
-        self.w1T, self.b1 = f32(te.linear_1.weight.t()), f32(te.linear_1.bias)
-        self.w2T, self.b2 = f32(te.linear_2.weight.t()), f32(te.linear_2.bias)
+        self.conv_in_wv = self.im2col_conv_in(m.conv_in)
+        self.time_mlp_and_conv_out(m)
         self.class_table = f32(m.class_embedding.weight) if isinstance(m.class_embedding, nn.Embedding) else None
         # class_embed_type: "timestep" = a second TimestepEmbedding over the sinusoid of the labels; "identity" = rows given as is
         self.class_mode = m.config.class_embed_type
@@ -371,91 +363,20 @@ class _PackedWeights:
             ce = m.class_embedding
             self.cw1T, self.cb1 = f32(ce.linear_1.weight.t()), f32(ce.linear_1.bias)
             self.cw2T, self.cb2 = f32(ce.linear_2.weight.t()), f32(ce.linear_2.bias)
-        self.resnets = {}
-        self.attns = {}
-        self.samplers = {}
-        proj_w, proj_b, off = [], [], 0
-        for name, r in self._iter(m, _Resnet):
-            e = SimpleNamespace()
-            e.cin, e.cout = r.in_channels, r.out_channels
-            e.g1, e.be1 = f32(r.norm1.weight), f32(r.norm1.bias)
-            e.g2, e.be2 = f32(r.norm2.weight), f32(r.norm2.bias)
-            e.w1, e.b1 = self._pack(r.conv1.weight), f32(r.conv1.bias)
-            e.w2, e.b2 = self._pack(r.conv2.weight), f32(r.conv2.bias)
-            if r.conv_shortcut is not None:
-                # conv_shortcut is folded into conv2 (pd_conv tail): per 32-co tile the tail's fragments follow conv2's
-                ws = self._pack(r.conv_shortcut.weight)
-                ct = e.w2.shape[0]
-                e.w2 = torch.cat([e.w2.reshape(ct, -1, 64, 8), ws.reshape(ct, -1, 64, 8)], 1).contiguous()
-                e.b2 = e.b2 + f32(r.conv_shortcut.bias)
-                e.fused_shortcut = True
-            else:
-                e.fused_shortcut = False
-            e.eps = r.norm1.eps
-            e.temb_off = off
-            e.scale_shift = r.scale_shift
-            off += r.time_emb_proj.weight.shape[0]
-            proj_w.append(r.time_emb_proj.weight.detach())
-            proj_b.append(r.time_emb_proj.bias.detach())
-            self.resnets[name] = e
-        self.proj_dim = off
-        self.wpT = f32(torch.cat(proj_w, 0).t())
-        self.bp = f32(torch.cat(proj_b, 0))
-        for name, a in self._iter(m, _Attention):
-            e = SimpleNamespace()
-            e.heads = a.heads
-            e.g, e.be, e.eps = f32(a.group_norm.weight), f32(a.group_norm.bias), a.group_norm.eps
-            wqkv = torch.cat([a.to_q.weight, a.to_k.weight, a.to_v.weight], 0).detach()
-            e.wqkv = self._pack(wqkv[:, :, None, None])
-            e.bqkv = f32(torch.cat([a.to_q.bias, a.to_k.bias, a.to_v.bias], 0))
-            e.wo, e.bo = self._pack(a.to_out[0].weight.detach()[:, :, None, None]), f32(a.to_out[0].bias)
-            self.attns[name] = e
-        for name, s in self._iter(m, _Sampler):
-            e = SimpleNamespace()
-            e.w, e.b, e.padding = self._pack(s.conv.weight), f32(s.conv.bias), s.padding
-            if ".upsamplers." in name:
-                # Upsample2D as four 2x2 convolutions over the low-resolution tensor (pd_conv phase 1..4): 4 / 9 of the FLOPs of the 3x3
-                # convolution over the nearest-upsampled tensor (round 4: the training plans too -- their input gradient runs the four phases backwards, pd_conv phase_in; the weight gradient stays on the 3x3 form)
-                # (w4_src: the four fp32 phase kernels stacked, on the device -- the training re-pack refreshes it and re-packs w4 every step)
-                e.w4_src = upsample_phase_weights_stacked(s.conv.weight.detach().to(device=device, dtype=torch.float32))
-                e.w4 = tuple(self._pack(e.w4_src[p]) for p in range(4))      # (a tuple: _copy_into refreshes tuples of tensors in place)
-            self.samplers[name] = e
-        self.gn_out = (f32(m.conv_norm_out.weight), f32(m.conv_norm_out.bias), m.conv_norm_out.eps)
-        co = m.conv_out.weight.shape[0]
-        self.conv_out_pad = ((co + 31) // 32) * 32
-        self.conv_out_w = self._pack(m.conv_out.weight, self.conv_out_pad)
-        b = torch.zeros(self.conv_out_pad, dtype=torch.float32, device=dev)
-        b[:co] = f32(m.conv_out.bias)
-        self.conv_out_b = b
-
-    @staticmethod
-    def _iter(m, cls):
+        self.resnets, self.attns, self.samplers = {}, {}, {}
+        res = []
         for name, mod in m.named_modules():
-            if isinstance(mod, cls):
-                yield name, mod
-
-    def _pack(self, w, cout_pad=None):
-        # packed on the device the plan runs on (a training step re-packs after every optimizer update)
-        return pack_conv_weight(w.detach().to(device=self.conv_in_w.device, dtype=torch.float32), self.tdt, cout_pad)
-
-    def refresh(self, m):
-        """Re-derive every kernel-layout tensor from ``m``'s current parameters IN PLACE (device pointers held by launch
-        plans stay valid).  Called after each optimizer step of a training run."""
-        _copy_into(self, type(self)(m, self.conv_in_w.device))
-
-
-def _copy_into(dst, src):
-    items = src.items() if isinstance(src, dict) else vars(src).items()
-    for k, v in items:
-        d = dst[k] if isinstance(dst, dict) else getattr(dst, k)
-        if torch.is_tensor(v):
-            d.copy_(v)
-        elif isinstance(v, (dict, SimpleNamespace)):
-            _copy_into(d, v)
-        elif isinstance(v, tuple):
-            for dd, vv in zip(d, v):
-                if torch.is_tensor(vv):
-                    dd.copy_(vv)
+            if isinstance(mod, _Resnet):
+                e = self.resnets[name] = self.resnet(mod)
+                e.scale_shift = mod.scale_shift
+                res.append((mod, e))
+            elif isinstance(mod, _Attention):
+                self.attns[name] = self.attention(mod)
+            elif isinstance(mod, _Sampler):
+                # Upsample2D as four 2x2 convolutions over the low-resolution tensor, in the training plans too: their input gradient
+                # runs the four phases backwards (pd_conv phase_in); the weight gradient stays on the 3x3 form
+                self.samplers[name] = self.sampler(mod, phases=".upsamplers." in name)
+        self.stack_time_emb_proj(res)
 
 
 class _Op:
@@ -494,6 +415,10 @@ class UNetPlan:
         self._in_args = None
         self._out_args = None
         self._build()
+
+    def _esz(self):
+        """Bytes per element of the compute dtype."""
+        return 4 if self.code == L.PD_F32 else 2
 
     # ---- buffers ---------------------------------------------------------------------------------
     def _act(self, h, w, ch):
@@ -561,7 +486,7 @@ class UNetPlan:
                        tail_C1=(tail[1].shape[3] if (tail and tail[1] is not None) else 0))
         if temb_off is not None:
             self._temb_ptr_fields.append((a, temb_off))
-        esz = 4 if self.code == L.PD_F32 else 2
+        esz = self._esz()
         cin = c0 + c1
         flops = 2.0 * B * hout * wout * cout * cin * ksize * ksize
         tail_c = (tail[0].shape[3] + (tail[1].shape[3] if tail[1] is not None else 0)) if tail else 0
@@ -580,7 +505,7 @@ class UNetPlan:
 
     def _subpixel_up_ok(self, x):
         B, h, w, ch = x.shape
-        esz = 4 if self.code == L.PD_F32 else 2
+        esz = self._esz()
         return (self.SUBPIXEL_UP and (not getattr(self, "train", False) or getattr(self, "subpixel_in_training", False)) and w >= 16 and ch % 32 == 0
                 and B * 4 * h * w * ch * esz < (1 << 31))
 
@@ -593,7 +518,7 @@ class UNetPlan:
         T = self.lib.pd_conv_stat_tiles(h, w, 2, 1)
         st = self._f32(B, 4 * T, ch, 2)
         self.stats[id(y)] = (st, 4 * T)
-        esz = 4 if self.code == L.PD_F32 else 2
+        esz = self._esz()
         for ph in range(4):
             a = L.ConvArgs(dtype=self.code, B=B, Hin=h, Win=w, Hout=h, Wout=w, C0=ch, C1=0, Cout=ch, Cout_pad=ch, ksize=2, stride=1, pad=0,
                            upsample=0, silu=0, out_mode=L.PD_OUT_NHWC, heads=0, x0=x.data_ptr(), x1=None, scale=None, shift=None,
@@ -614,7 +539,7 @@ class UNetPlan:
         y = self._act(h, w, c0 + c1)
         a = L.GnApplyArgs(dtype=self.code, B=B, HW=h * w, C0=c0, C1=c1, silu=silu, x0=x0.data_ptr(), x1=L.ptr(x1),
                           scale=gn[0].data_ptr(), shift=gn[1].data_ptr(), y=y.data_ptr())
-        self.ops.append(_Op(self.lib.pd_gn_apply, a, "gn_apply", 0.0, 2.0 * y.numel() * (4 if self.code == L.PD_F32 else 2)))
+        self.ops.append(_Op(self.lib.pd_gn_apply, a, "gn_apply", 0.0, 2.0 * y.numel() * self._esz()))
         return y
 
     def _linear(self, x, wpk, bias, cout, residual=None, y=None, gn=None, stats=False, what="linear", glu=False):
@@ -625,7 +550,7 @@ class UNetPlan:
         B, h, w, K = x.shape
         if y is None:
             y = self._act(h, w, cout // 2 if glu else cout)
-        M, esz = B * h * w, (4 if self.code == L.PD_F32 else 2)
+        M, esz = B * h * w, self._esz()
         st = None
         if stats:
             T = (h * w) // 128
@@ -718,7 +643,7 @@ class UNetPlan:
                     self._fold_ws = ws
                     self.bufs.append(ws)
                 a.fold_ws, a.fold_ws_bytes = ws.data_ptr(), need
-            esz_ = 4 if self.code == L.PD_F32 else 2
+            esz_ = self._esz()
             self.ops.append(_Op(self.lib.pd_linear, a, "conv1x1", 2.0 * M * ch * 3 * ch, (M * ch * 4 + 3 * ch * ch) * esz_))
         else:
             kmax2 = None
@@ -728,7 +653,7 @@ class UNetPlan:
         lse = self._f32(B, e.heads, h * w) if self.train else None
         a = L.AttnArgs(dtype=self.code, B=B, heads=e.heads, N=h * w, q=qkv[0].data_ptr(), k=qkv[1].data_ptr(),
                        v=qkv[2].data_ptr(), out=o.data_ptr(), lse=L.ptr(lse), kmax2=kmax2)
-        esz = 4 if self.code == L.PD_F32 else 2
+        esz = self._esz()
         N = h * w
         self.ops.append(_Op(self.lib.pd_attn_d8, a, "attn_d8", 4.0 * B * e.heads * N * N * 8, 4.0 * B * N * ch * esz))
         if self._linear_ok(o):
@@ -744,7 +669,7 @@ class UNetPlan:
         ``residual_connection=True`` for every head_dim other than 8 (the VAE mid block; ``attention_head_dim = None``)."""
         e = self.w.attns[name]
         B, h, w, ch = x.shape
-        N, esz = h * w, (4 if self.code == L.PD_F32 else 2)
+        N, esz = h * w, self._esz()
         d = ch // e.heads
         if d not in (16, 32, 64, 128, 256, 512):
             raise NotImplementedError(f"attention head_dim {d}: implemented are 8, 16, 32, 64 and one wide head of 128 / 256 / 512 channels")
@@ -805,7 +730,7 @@ class UNetPlan:
             self._in_args = conv_in_args
         self.ops[-1].what = "conv_in"
         self.ops[-1].flops = 2.0 * B * H * W * boc[0] * c.in_channels * 9
-        self.ops[-1].bytes = B * H * W * (c.in_channels * 4 + boc[0] * (4 if self.code == L.PD_F32 else 2))
+        self.ops[-1].bytes = B * H * W * (c.in_channels * 4 + boc[0] * self._esz())
         self.tape.append(SimpleNamespace(kind="conv_in", out=a0))
         h = a0
         skips = [a0]

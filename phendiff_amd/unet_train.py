@@ -20,14 +20,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib as L
-from .packing import dgrad_weight, pack_conv_weight, upsample_phase_weights_stacked
-from .unet import CustomCondUNet2DModel, UNetPlan, _Attention, _Op, _PackedWeights, _Resnet, _Sampler, _copy_into
+from .unet import CustomCondUNet2DModel, UNetPlan, _Attention, _Op, _PackedWeights, _Resnet, _Sampler
+from .weight_layout import (Repacker, WeightSet, contiguous_after as _contiguous_after, fuse_pack_jobs,  # noqa: F401 (re-exported)
+                            pad32, require_alias, run_pack_jobs)
 
 
 # diagnostic (same-box A/B): route the 1x1 gradients through pd_conv / pd_conv_wgrad as the 3x3 ones
@@ -72,43 +72,25 @@ def training_param_order(m: CustomCondUNet2DModel) -> List[Tuple[str, torch.nn.P
     return out
 
 
-def _contiguous_after(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return b.data_ptr() == a.data_ptr() + a.numel() * a.element_size()
-
-
-class TrainWeights:
+class TrainWeights(WeightSet):
     """Input-gradient ("dgrad") weights in ``pd_conv``'s packed layout: W'[ci][co][ky][kx] = W[co][ci][K-1-ky][K-1-kx]."""
 
     def __init__(self, m: CustomCondUNet2DModel, device, tdt):
         # fp16 (round 5): the reference's `--mixed_precision fp16` training (launch_script_DDIM.sh:56) -- fp16 activations and activation
         # gradients on the f16 MFMA, fp32 master weights / parameter gradients, a loss scale (training.LossScaler) set up by UNetTrainer
-        self.tdt, self.device = tdt, device
-        pk = lambda w: pack_conv_weight(dgrad_weight(w.detach().to(device=device, dtype=torch.float32)), tdt)
-        lin = lambda w: w.detach()[:, :, None, None]
+        super().__init__(device, tdt, dgrad=True)
         self.resnets, self.attns, self.samplers = {}, {}, {}
         for name, mod in m.named_modules():
             if isinstance(mod, _Resnet):
-                e = SimpleNamespace(w1d=pk(mod.conv1.weight), w2d=pk(mod.conv2.weight))
-                if mod.conv_shortcut is not None:
-                    e.wsd = pk(mod.conv_shortcut.weight)
-                self.resnets[name] = e
+                self.resnets[name] = self.resnet(mod)
             elif isinstance(mod, _Attention):
-                wqkv = torch.cat([mod.to_q.weight, mod.to_k.weight, mod.to_v.weight], 0)
-                self.attns[name] = SimpleNamespace(wqkvd=pk(lin(wqkv)), wod=pk(lin(mod.to_out[0].weight)))
+                self.attns[name] = self.attention(mod)
             elif isinstance(mod, _Sampler):
-                self.samplers[name] = SimpleNamespace(wd=pk(mod.conv.weight))
-                if ".upsamplers." in name:      # input-gradient weights of the four sub-pixel phases (pd_conv phase_in): transposed, taps flipped
-                    k4 = upsample_phase_weights_stacked(mod.conv.weight.detach().to(device=device, dtype=torch.float32))
-                    self.samplers[name].wd4 = tuple(pk(k4[p]) for p in range(4))
-        co = m.conv_out.weight.shape[0]
-        wo = torch.zeros((((co + 31) // 32) * 32,) + tuple(m.conv_out.weight.shape[1:]), dtype=torch.float32, device=device)
-        wo[:co] = m.conv_out.weight.detach().to(device=device, dtype=torch.float32)
-        self.conv_out_d = pk(wo)           # 32 (3 real) output-gradient channels -> block_out_channels[0]
+                self.samplers[name] = self.sampler(mod, phases=".upsamplers." in name)
+        co, c0, ci = m.conv_out.weight.shape[0], m.conv_out.weight.shape[1], m.conv_in.weight.shape[1]
+        self.conv_out_d = self.padded(m.conv_out, pad32(co), c0)      # 32 (3 real) output-gradient channels -> block_out_channels[0]
         # conv_in's input gradient (the image gradient of the guided transfer): block_out_channels[0] -> 3 channels (pad 32)
-        self.conv_in_d = pack_conv_weight(dgrad_weight(m.conv_in.weight.detach().to(device=device, dtype=torch.float32)), tdt, 32)
-
-    def refresh(self, m):
-        _copy_into(self, TrainWeights(m, self.device, self.tdt))
+        self.conv_in_d = self.padded(m.conv_in, m.conv_in.weight.shape[0], pad32(ci))
 
 
 class UNetTrainPlan(UNetPlan):
@@ -276,9 +258,6 @@ class UNetTrainPlan(UNetPlan):
             if n not in self.frozen:
                 self.grad_ready[n] = len(self.bwd_ops)
         return self.grads[wname], self.grads[bname]
-
-    def _esz(self):
-        return 4 if self.code == L.PD_F32 else 2
 
     def _bias_grad(self, dy, total, valid=None, per_sample=None, per_stride=None):
         if not self.param_grads:
@@ -796,155 +775,32 @@ def plan_grad_buckets(sizes: List[int], ready: List[int], bucket_elems: int) -> 
     return sorted(out, key=lambda b: b[2])
 
 
-def fuse_pack_jobs(jobs):
-    """A weight is re-packed twice after every optimizer step -- the forward layout and the input-gradient layout (transposed, taps
-    flipped) -- from the same fp32 master tensor.  Pairs whose 32 x 32 blocks coincide become ONE job with ``dst2`` (ABI 7): the master
-    weights are read once (the re-pack of the SD-2.1 UNet: 6.9 -> 3.5 GB of reads per step).  Jobs without a partner stay as they are."""
-    fwd = {}
-    for a in jobs:
-        if not a.dgrad and not a.dst2:
-            fwd.setdefault((a.src, a.ksize, a.cout, a.cin, a.cout_pad, a.cin_pad, a.src_in), []).append(a)
-    out, used = [], set()
-    for a in jobs:
-        if a.dgrad:
-            cands = fwd.get((a.src, a.ksize, a.cin, a.cout, a.cin_pad, a.cout_pad, a.src_in), [])
-            partner = next((f for f in cands if id(f) not in used), None)
-            if partner is not None:
-                used.add(id(partner))
-                partner.dst2, partner.dst2_ct_stride = a.dst, a.dst_ct_stride
-                continue
-        out.append(a)
-    return out
-
-
-def run_pack_jobs(lib, jobs, stream, cache, device):
-    """All ``pd_pack_weight`` jobs of an optimizer step as ONE ``pd_pack_weight_batch`` launch: the descriptors are uploaded
-    once (``cache``: a dict owned by the re-packer) next to the block-range table the kernel searches."""
-    if not jobs:
-        return
-    st = cache.get("batch")
-    if st is None:
-        jobs = fuse_pack_jobs(jobs)
-        for a in jobs:     # what pd_pack_weight would refuse
-            if a.cout_pad % 32 or a.cin_pad % 32 or a.cout_pad < a.cout or a.cin_pad < a.cin or a.dtype != jobs[0].dtype:
-                raise L.PhenDiffHipError("pd_pack_weight_batch: inconsistent job descriptors")
-        dev = torch.device(device)
-        st = []
-        # one launch per kernel size: the workgroup's LDS tile is sized by the launch's largest kernel (37 KB for 3x3 against 4 KB for the
-        # Linear / 1x1 blocks, which are most of the latent-diffusion UNet's blocks and would run at a quarter of the occupancy beside them)
-        for ks in sorted({a.ksize for a in jobs}):
-            sel = [a for a in jobs if a.ksize == ks]
-            raw = (L.PackWeightArgs * len(sel))(*sel)
-            table = torch.frombuffer(bytearray(bytes(raw)), dtype=torch.uint8).to(dev)
-            starts, tot = [0], 0
-            for a in sel:
-                tot += (a.cout_pad // 32) * (a.cin_pad // 32)
-                starts.append(tot)
-            starts_t = torch.tensor(starts, dtype=torch.int32, device=dev)
-            args = L.PackWeightBatchArgs(dtype=sel[0].dtype, n=len(sel), jobs=table.data_ptr(), starts=starts_t.data_ptr(), total_blocks=tot,
-                                         max_ksize=ks)
-            st.append((args, table, starts_t))
-        cache["batch"] = st
-    for args, _, _ in st:
-        L.check(lib.pd_pack_weight_batch(C.byref(args), stream), "pd_pack_weight_batch")
-
-
-class _Repacker:
-    """After an optimizer step: fp32 master parameters -> every kernel-layout copy the plans read (``_PackedWeights`` and
-    ``TrainWeights`` tensors, IN PLACE), as ``pd_pack_weight`` launches plus a handful of small fp32 copies.  Parameters
-    that the kernels read as plain fp32 vectors (GroupNorm affine, most biases, the class table) alias the flat master
-    buffer and need nothing."""
+class _Repacker(Repacker):
+    """The pixel UNet's re-pack: the ``_PackedWeights`` and ``TrainWeights`` tensors."""
 
     def __init__(self, m: CustomCondUNet2DModel, w: _PackedWeights, tw: TrainWeights):
-        self.lib = L.lib()
-        self.jobs, self.small, self.pre = [], [], []      # pre: torch-side preparations the pack jobs read (run first)
-        self.jobs_device = m.conv_in.weight.device
-        code = w.code
-
-        def job(dst, src, cout, cin, k, *, dgrad=0, cout_pad=None, cin_pad=None, src_in=None, ct_stride=None, dst_off=0):
-            cp = cout_pad or ((cout + 31) // 32) * 32
-            ip = cin_pad or ((cin + 31) // 32) * 32
-            per_ct = (ip // 32) * k * k * 2 * 64 * 8
-            esz = dst.element_size()
-            self.jobs.append(L.PackWeightArgs(dtype=code, cout=cout, cin=cin, cout_pad=cp, cin_pad=ip, ksize=k,
-                                              src_in=src_in or (cout if dgrad else cin), dgrad=dgrad, src=src.data_ptr(),
-                                              dst=dst.data_ptr() + dst_off * esz, dst_ct_stride=ct_stride or per_ct))
-
-        ci = m.conv_in.weight.shape[1]
-        job(w.conv_in_wv, m.conv_in.weight, m.conv_in.weight.shape[0], ci * 9, 1, cin_pad=32)
+        super().__init__(w.code, m.conv_in.weight.device)
+        c0, ci = m.conv_in.weight.shape[:2]
+        co, cc = m.conv_out.weight.shape[:2]
+        self.job(w.conv_in_wv, m.conv_in.weight, c0, ci * 9, 1, cin_pad=32)
+        res = []
         for name, mod in m.named_modules():
             if isinstance(mod, _Resnet):
-                e, t = w.resnets[name], tw.resnets[name]
-                cin, cout = mod.in_channels, mod.out_channels
-                job(e.w1, mod.conv1.weight, cout, cin, 3)
-                stride = e.w2[0].numel()
-                job(e.w2, mod.conv2.weight, cout, cout, 3, ct_stride=stride)
-                job(t.w1d, mod.conv1.weight, cin, cout, 3, dgrad=1)
-                job(t.w2d, mod.conv2.weight, cout, cout, 3, dgrad=1)
-                if mod.conv_shortcut is not None:
-                    job(e.w2, mod.conv_shortcut.weight, cout, cin, 1, ct_stride=stride, dst_off=(cout // 32) * 9 * 2 * 512)
-                    job(t.wsd, mod.conv_shortcut.weight, cin, cout, 1, dgrad=1)
-                    b2, bs, dst = mod.conv2.bias, mod.conv_shortcut.bias, e.b2
-                    self.small.append(lambda b2=b2, bs=bs, dst=dst: torch.add(b2.data, bs.data, out=dst))
+                self.resnet(mod, w.resnets[name], tw.resnets[name])
+                res.append(mod)
             elif isinstance(mod, _Attention):
-                e, t = w.attns[name], tw.attns[name]
-                ch = mod.to_q.weight.shape[0]
-                if not (_contiguous_after(mod.to_q.weight.data, mod.to_k.weight.data)
-                        and _contiguous_after(mod.to_k.weight.data, mod.to_v.weight.data)
-                        and _contiguous_after(mod.to_q.bias.data, mod.to_k.bias.data)
-                        and _contiguous_after(mod.to_k.bias.data, mod.to_v.bias.data)):
-                    raise ValueError("to_q/to_k/to_v parameters must be adjacent (use training_param_order)")
-                job(e.wqkv, mod.to_q.weight, 3 * ch, ch, 1)
-                job(e.wo, mod.to_out[0].weight, ch, ch, 1)
-                job(t.wqkvd, mod.to_q.weight, ch, 3 * ch, 1, dgrad=1)
-                job(t.wod, mod.to_out[0].weight, ch, ch, 1, dgrad=1)
-                qb, dst = mod.to_q.bias, e.bqkv
-                self.small.append(lambda qb=qb, dst=dst, ch=ch: dst.copy_(torch.as_strided(qb.data, (3 * ch,), (1,))))
+                self.attention(mod, w.attns[name], tw.attns[name], "training_param_order")
             elif isinstance(mod, _Sampler):
-                ch = mod.conv.weight.shape[0]
-                job(w.samplers[name].w, mod.conv.weight, ch, ch, 3)
-                job(tw.samplers[name].wd, mod.conv.weight, ch, ch, 3, dgrad=1)
-                if ".upsamplers." in name:      # the sub-pixel phase kernels: pre-summed taps first (one contraction), then packed like any weight
-                    src4, wt = w.samplers[name].w4_src, mod.conv.weight
-                    self.pre.append(lambda src4=src4, wt=wt: upsample_phase_weights_stacked(wt.data, out=src4))
-                    for p in range(4):
-                        job(w.samplers[name].w4[p], src4[p], ch, ch, 2)
-                        job(tw.samplers[name].wd4[p], src4[p], ch, ch, 2, dgrad=1)
-        co, c0 = m.conv_out.weight.shape[0], m.conv_out.weight.shape[1]
-        job(w.conv_out_w, m.conv_out.weight, co, c0, 3, cout_pad=w.conv_out_pad)
-        job(tw.conv_out_d, m.conv_out.weight, c0, co, 3, dgrad=1, cin_pad=w.conv_out_pad)
-        job(tw.conv_in_d, m.conv_in.weight, ci, m.conv_in.weight.shape[0], 3, dgrad=1, cout_pad=32)
+                self.sampler(mod, w.samplers[name], tw.samplers[name])
+        self.pair(w.conv_out_w, tw.conv_out_d, m.conv_out.weight, co, cc, 3, cout_pad=w.conv_out_pad)
+        self.job(tw.conv_in_d, m.conv_in.weight, ci, c0, 3, dgrad=1, cout_pad=32)
+        self.time_mlp_and_conv_out(m, w, res[0].time_emb_proj)
         te = m.time_embedding
-        res = [mod for _, mod in m.named_modules() if isinstance(mod, _Resnet)]
-        pd_, tdim = w.proj_dim, m.time_embed_dim
-        first = res[0].time_emb_proj
-        self.small += [
-            lambda: w.w1T.copy_(te.linear_1.weight.data.t()),
-            lambda: w.w2T.copy_(te.linear_2.weight.data.t()),
-            lambda: w.wpT.copy_(torch.as_strided(first.weight.data, (pd_, tdim), (tdim, 1)).t()),
-            lambda: w.bp.copy_(torch.as_strided(first.bias.data, (pd_,), (1,))),
-            lambda: w.conv_out_b[:co].copy_(m.conv_out.bias.data),
-        ]
         if getattr(w, "class_mode", None) == "timestep":      # the class MLP's transposed weights (its biases alias the parameters)
             ce = m.class_embedding
             self.small += [lambda: w.cw1T.copy_(ce.linear_1.weight.data.t()), lambda: w.cw2T.copy_(ce.linear_2.weight.data.t())]
-        for t in (w.b1, w.b2, w.conv_in_b):
-            pass  # alias the master parameters (fp32, contiguous, same device): nothing to refresh
-        self._alias_check = [(w.b1, te.linear_1.bias), (w.b2, te.linear_2.bias), (w.conv_in_b, m.conv_in.bias),
-                             (w.gn_out[0], m.conv_norm_out.weight)]
-        for a, b in self._alias_check:
-            if a.data_ptr() != b.data_ptr():
-                raise RuntimeError("kernel-side fp32 vectors must alias the master parameters (build the packed weights "
-                                   "after the parameters were moved into the flat training buffer)")
-
-    def run(self, stream):
-        with torch.no_grad():
-            for f in self.pre:
-                f()
-        run_pack_jobs(self.lib, self.jobs, stream, self.__dict__.setdefault("_batch", {}), self.jobs_device)
-        with torch.no_grad():
-            for f in self.small:
-                f()
+        require_alias([(w.b1, te.linear_1.bias), (w.b2, te.linear_2.bias), (w.conv_in_b, m.conv_in.bias),
+                       (w.gn_out[0], m.conv_norm_out.weight)])
 
 
 class UNetTrainer:

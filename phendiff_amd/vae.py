@@ -20,9 +20,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .packing import pack_conv_weight, upsample_phase_weights
 from .training import mark_requires_grad_calls
 from .unet import UNetPlan, _Attention, _Block, _DT, _Op, _Sampler
+from .weight_layout import WeightSet
 
 SD_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512),
                      layers_per_block=2, norm_num_groups=32, scaling_factor=0.18215, sample_size=512,
@@ -279,60 +279,31 @@ class AutoencoderKL(nn.Module):
 
 
 # ---- kernel-layout weights ----------------------------------------------------------------------------------------------
-class _VaeWeights:
+class _VaeWeights(WeightSet):
     def __init__(self, m: AutoencoderKL, device):
-        self.code, self.tdt = _DT[m.compute_dtype]
+        self.code, tdt = _DT[m.compute_dtype]
+        super().__init__(device, tdt)
         self.proj_dim = 0
-        dev, c = device, m.config
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        pk = lambda w, cp=None: pack_conv_weight(w.detach().to(device=dev, dtype=torch.float32), self.tdt, cp)
-
-        def padded(conv, cin_pad, cout_pad):
-            """conv weight / bias zero-padded to (cout_pad, cin_pad) channels."""
-            co, ci, k, _ = conv.weight.shape
-            w = torch.zeros((cout_pad, cin_pad, k, k), dtype=torch.float32, device=dev)
-            w[:co, :ci] = f32(conv.weight)
-            b = torch.zeros(cout_pad, dtype=torch.float32, device=dev)
-            b[:co] = f32(conv.bias)
-            return pk(w), b
-
+        f32, padded = self.f32, self.padded
         enc, dec = m.encoder, m.decoder
-        # encoder conv_in: 3x3 over <= 3 NCHW planes = a 1x1 conv over 32 im2col channels k = ci*9 + ky*3 + kx
-        cin = enc.conv_in.weight.shape[1]
-        wv = torch.zeros((enc.conv_in.weight.shape[0], 32, 1, 1), dtype=torch.float32, device=dev)
-        wv[:, :cin * 9, 0, 0] = f32(enc.conv_in.weight).reshape(-1, cin * 9)
-        self.enc_in_w, self.enc_in_b = pk(wv), f32(enc.conv_in.bias)
-        self.enc_out_w, self.enc_out_b = padded(enc.conv_out, enc.conv_out.weight.shape[1], 32)     # 2*latent -> 32 channels (zeros)
+        self.enc_in_w, self.enc_in_b = self.im2col_conv_in(enc.conv_in), f32(enc.conv_in.bias)
+        self.enc_out_w, self.enc_out_b = padded(enc.conv_out, 32, enc.conv_out.weight.shape[1])     # 2*latent -> 32 channels (zeros)
         self.quant_w, self.quant_b = padded(m.quant_conv, 32, 32)
         self.post_quant_w, self.post_quant_b = padded(m.post_quant_conv, 32, 32)
-        self.dec_in_w, self.dec_in_b = padded(dec.conv_in, 32, dec.conv_in.weight.shape[0])
-        self.dec_out_w, self.dec_out_b = padded(dec.conv_out, dec.conv_out.weight.shape[1], 32)
+        self.dec_in_w, self.dec_in_b = padded(dec.conv_in, dec.conv_in.weight.shape[0], 32)
+        self.dec_out_w, self.dec_out_b = padded(dec.conv_out, 32, dec.conv_out.weight.shape[1])
         self.enc_gn = (f32(enc.conv_norm_out.weight), f32(enc.conv_norm_out.bias), enc.conv_norm_out.eps)
         self.dec_gn = (f32(dec.conv_norm_out.weight), f32(dec.conv_norm_out.bias), dec.conv_norm_out.eps)
         self.resnets, self.attns, self.samplers = {}, {}, {}
         for name, r in m.named_modules():
             if isinstance(r, _VaeResnet):
-                e = SimpleNamespace(cin=r.in_channels, cout=r.out_channels, eps=r.norm1.eps, temb_off=None)
-                e.g1, e.be1, e.g2, e.be2 = f32(r.norm1.weight), f32(r.norm1.bias), f32(r.norm2.weight), f32(r.norm2.bias)
-                e.w1, e.b1, e.w2, e.b2 = pk(r.conv1.weight), f32(r.conv1.bias), pk(r.conv2.weight), f32(r.conv2.bias)
-                e.fused_shortcut = r.conv_shortcut is not None
-                if e.fused_shortcut:                          # conv_shortcut folded into conv2 (pd_conv tail chunks)
-                    ws = pk(r.conv_shortcut.weight)
-                    ct = e.w2.shape[0]
-                    e.w2 = torch.cat([e.w2.reshape(ct, -1, 64, 8), ws.reshape(ct, -1, 64, 8)], 1).contiguous()
-                    e.b2 = e.b2 + f32(r.conv_shortcut.bias)
-                self.resnets[name] = e
+                self.resnets[name] = self.resnet(r)
+                self.resnets[name].temb_off = None
             elif isinstance(r, _Attention):
-                e = SimpleNamespace(heads=r.heads, g=f32(r.group_norm.weight), be=f32(r.group_norm.bias), eps=r.group_norm.eps)
-                wqkv = torch.cat([r.to_q.weight, r.to_k.weight, r.to_v.weight], 0).detach()
-                e.wqkv = pk(wqkv[:, :, None, None])
-                e.bqkv = f32(torch.cat([r.to_q.bias, r.to_k.bias, r.to_v.bias], 0))
-                e.wo, e.bo = pk(r.to_out[0].weight.detach()[:, :, None, None]), f32(r.to_out[0].bias)
-                self.attns[name] = e
+                self.attns[name] = self.attention(r)
             elif isinstance(r, _Sampler):
-                self.samplers[name] = SimpleNamespace(w=pk(r.conv.weight), b=f32(r.conv.bias), padding=r.padding)
-                if ".upsamplers." in name:      # Upsample2D as four 2x2 phase convolutions (UNetPlan._upconv_subpixel; inference plans)
-                    self.samplers[name].w4 = tuple(pk(k) for k in upsample_phase_weights(r.conv.weight))
+                # Upsample2D as four 2x2 phase convolutions (UNetPlan._upconv_subpixel; inference plans): the decoder never trains
+                self.samplers[name] = self.sampler(r, phases=".upsamplers." in name, keep_src=False)
 
 
 class _VaePlan(UNetPlan):

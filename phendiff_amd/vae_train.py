@@ -17,9 +17,9 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib as L
-from .packing import dgrad_weight, pack_conv_weight
 from .unet import _Attention, _Sampler
-from .unet_train import UNetTrainPlan, _contiguous_after, run_pack_jobs
+from .unet_train import UNetTrainPlan
+from .weight_layout import Repacker, WeightSet, contiguous_after as _contiguous_after, require_alias
 from .vae import AutoencoderKL, VaeEncodePlan, _VaePlan, _VaeResnet, _VaeWeights
 
 VAE_PREFIX = "vae."
@@ -48,36 +48,22 @@ def vae_never_graded(vae: AutoencoderKL) -> frozenset:
     return frozenset(n for n, _ in vae.named_parameters() if not (n.startswith("encoder.") or n.startswith("quant_conv.")))
 
 
-class VaeTrainWeights:
+class VaeTrainWeights(WeightSet):
     """Input-gradient weights of the encoder and ``quant_conv`` in ``pd_conv``'s packed layout (transposed, taps flipped)."""
 
     def __init__(self, vae: AutoencoderKL, device, tdt):
-        self.tdt, self.device = tdt, device
-        f32 = lambda w: w.detach().to(device=device, dtype=torch.float32)
-        pk = lambda w, cp=None: pack_conv_weight(dgrad_weight(f32(w)), tdt, cp)
-        lin = lambda w: w.detach()[:, :, None, None]
+        super().__init__(device, tdt, dgrad=True)
         self.resnets, self.attns, self.samplers = {}, {}, {}
         for name, mod in vae.encoder.named_modules(prefix="encoder"):
             if isinstance(mod, _VaeResnet):
-                e = SimpleNamespace(w1d=pk(mod.conv1.weight), w2d=pk(mod.conv2.weight))
-                if mod.conv_shortcut is not None:
-                    e.wsd = pk(mod.conv_shortcut.weight)
-                self.resnets[name] = e
+                self.resnets[name] = self.resnet(mod)
             elif isinstance(mod, _Attention):
-                wqkv = torch.cat([mod.to_q.weight, mod.to_k.weight, mod.to_v.weight], 0)
-                self.attns[name] = SimpleNamespace(wqkvd=pk(lin(wqkv)), wod=pk(lin(mod.to_out[0].weight)))
+                self.attns[name] = self.attention(mod)
             elif isinstance(mod, _Sampler):
-                self.samplers[name] = SimpleNamespace(wd=pk(mod.conv.weight))
-
-        def padded(conv, cout_pad, cin_pad):
-            co, ci, k, _ = conv.weight.shape
-            w = torch.zeros((cout_pad, cin_pad, k, k), dtype=torch.float32, device=device)
-            w[:co, :ci] = f32(conv.weight)
-            return pk(w)
-
+                self.samplers[name] = self.sampler(mod)
         co = vae.encoder.conv_out
-        self.enc_out_d = padded(co, 32, co.weight.shape[1])      # 32 (2 x latent real) output-gradient lanes -> block_out_channels[-1]
-        self.quant_d = padded(vae.quant_conv, 32, 32)
+        self.enc_out_d = self.padded(co, 32, co.weight.shape[1])      # 32 (2 x latent real) output-gradient lanes -> block_out_channels[-1]
+        self.quant_d = self.padded(vae.quant_conv, 32, 32)
 
 
 class VaeEncodeTrainPlan(UNetTrainPlan, VaeEncodePlan):
@@ -160,78 +146,28 @@ class VaeEncodeTrainPlan(UNetTrainPlan, VaeEncodePlan):
         super().backward(self.dmom, stream, after_op=after_op)
 
 
-class _VaeRepacker:
-    """After an optimizer step: the encoder's and ``quant_conv``'s fp32 master parameters -> the kernel-layout copies the encode
-    plans (inference and training) and the backward read, IN PLACE.  GroupNorm affines and plain biases alias the flat master
-    buffer; the decoder never changes."""
+class _VaeRepacker(Repacker):
+    """The re-pack of the encoder's and ``quant_conv``'s kernel-layout copies, which the encode plans (inference and training)
+    and the backward read.  The decoder never changes."""
 
     def __init__(self, vae: AutoencoderKL, w: _VaeWeights, tw: VaeTrainWeights):
-        self.lib = L.lib()
-        self.jobs, self.small = [], []
-        self.jobs_device = vae.quant_conv.weight.device
-        code = w.code
-
-        def job(dst, src, cout, cin, k, *, dgrad=0, cout_pad=None, cin_pad=None, ct_stride=None, dst_off=0):
-            cp = cout_pad or ((cout + 31) // 32) * 32
-            ip = cin_pad or ((cin + 31) // 32) * 32
-            per_ct = (ip // 32) * k * k * 2 * 64 * 8
-            self.jobs.append(L.PackWeightArgs(dtype=code, cout=cout, cin=cin, cout_pad=cp, cin_pad=ip, ksize=k,
-                                              src_in=(cout if dgrad else cin), dgrad=dgrad, src=src.data_ptr(),
-                                              dst=dst.data_ptr() + dst_off * dst.element_size(), dst_ct_stride=ct_stride or per_ct))
-
-        enc = vae.encoder
-        c0, ci = enc.conv_in.weight.shape[0], enc.conv_in.weight.shape[1]
-        job(w.enc_in_w, enc.conv_in.weight, c0, ci * 9, 1, cin_pad=32)
+        super().__init__(w.code, vae.quant_conv.weight.device)
+        enc, q = vae.encoder, vae.quant_conv
+        c0, ci = enc.conv_in.weight.shape[:2]
+        co, cc = enc.conv_out.weight.shape[:2]
+        qo, qi = q.weight.shape[:2]
+        self.job(w.enc_in_w, enc.conv_in.weight, c0, ci * 9, 1, cin_pad=32)
         for name, mod in enc.named_modules(prefix="encoder"):
             if isinstance(mod, _VaeResnet):
-                e, t = w.resnets[name], tw.resnets[name]
-                cin, cout = mod.in_channels, mod.out_channels
-                job(e.w1, mod.conv1.weight, cout, cin, 3)
-                stride = e.w2[0].numel()
-                job(e.w2, mod.conv2.weight, cout, cout, 3, ct_stride=stride)
-                job(t.w1d, mod.conv1.weight, cin, cout, 3, dgrad=1)
-                job(t.w2d, mod.conv2.weight, cout, cout, 3, dgrad=1)
-                if mod.conv_shortcut is not None:
-                    job(e.w2, mod.conv_shortcut.weight, cout, cin, 1, ct_stride=stride, dst_off=(cout // 32) * 9 * 2 * 512)
-                    job(t.wsd, mod.conv_shortcut.weight, cin, cout, 1, dgrad=1)
-                    b2, bs, dst = mod.conv2.bias, mod.conv_shortcut.bias, e.b2
-                    self.small.append(lambda b2=b2, bs=bs, dst=dst: torch.add(b2.data, bs.data, out=dst))
+                self.resnet(mod, w.resnets[name], tw.resnets[name])
             elif isinstance(mod, _Attention):
-                e, t = w.attns[name], tw.attns[name]
-                ch = mod.to_q.weight.shape[0]
-                if not (_contiguous_after(mod.to_q.weight.data, mod.to_k.weight.data)
-                        and _contiguous_after(mod.to_k.weight.data, mod.to_v.weight.data)
-                        and _contiguous_after(mod.to_q.bias.data, mod.to_k.bias.data)
-                        and _contiguous_after(mod.to_k.bias.data, mod.to_v.bias.data)):
-                    raise ValueError("to_q/to_k/to_v parameters must be adjacent (use vae_training_param_order)")
-                job(e.wqkv, mod.to_q.weight, 3 * ch, ch, 1)
-                job(e.wo, mod.to_out[0].weight, ch, ch, 1)
-                job(t.wqkvd, mod.to_q.weight, ch, 3 * ch, 1, dgrad=1)
-                job(t.wod, mod.to_out[0].weight, ch, ch, 1, dgrad=1)
-                qb, dst = mod.to_q.bias, e.bqkv
-                self.small.append(lambda qb=qb, dst=dst, ch=ch: dst.copy_(torch.as_strided(qb.data, (3 * ch,), (1,))))
+                self.attention(mod, w.attns[name], tw.attns[name], "vae_training_param_order")
             elif isinstance(mod, _Sampler):
-                ch = mod.conv.weight.shape[0]
-                job(w.samplers[name].w, mod.conv.weight, ch, ch, 3)
-                job(tw.samplers[name].wd, mod.conv.weight, ch, ch, 3, dgrad=1)
-        co, cc = enc.conv_out.weight.shape[0], enc.conv_out.weight.shape[1]
-        job(w.enc_out_w, enc.conv_out.weight, co, cc, 3, cout_pad=32)
-        job(tw.enc_out_d, enc.conv_out.weight, cc, co, 3, dgrad=1, cin_pad=32)
-        q = vae.quant_conv
-        qo, qi = q.weight.shape[0], q.weight.shape[1]
-        job(w.quant_w, q.weight, qo, qi, 1, cout_pad=32, cin_pad=32)
-        job(tw.quant_d, q.weight, qi, qo, 1, dgrad=1, cout_pad=32, cin_pad=32)
+                self.sampler(mod, w.samplers[name], tw.samplers[name])
+        self.pair(w.enc_out_w, tw.enc_out_d, enc.conv_out.weight, co, cc, 3, cout_pad=32)
+        self.pair(w.quant_w, tw.quant_d, q.weight, qo, qi, 1, cout_pad=32, cin_pad=32)
         self.small += [lambda: w.enc_out_b[:co].copy_(enc.conv_out.bias.data), lambda: w.quant_b[:qo].copy_(q.bias.data)]
-        for a, b in ((w.enc_in_b, enc.conv_in.bias), (w.enc_gn[0], enc.conv_norm_out.weight)):
-            if a.data_ptr() != b.data_ptr():
-                raise RuntimeError("kernel-side fp32 vectors must alias the master parameters (build the packed weights "
-                                   "after the parameters were moved into the flat training buffer)")
-
-    def run(self, stream):
-        run_pack_jobs(self.lib, self.jobs, stream, self.__dict__.setdefault("_batch", {}), self.jobs_device)
-        with torch.no_grad():
-            for f in self.small:
-                f()
+        require_alias([(w.enc_in_b, enc.conv_in.bias), (w.enc_gn[0], enc.conv_norm_out.weight)])
 
 
 def latent_chain_bwd(g_noisy, g_out, moments, eps, sa, sb, pred_type: str, scale: float, out, code, stream):

@@ -145,6 +145,30 @@ def test_sd_inference_after_training_steps_sees_the_updated_upsampler_phase_kern
     assert rel(got, ref_out) < 1e-4
 
 
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_sd_device_repack_equals_host_packing(mode):
+    """After an optimizer step the pd_pack_weight path must leave exactly what packing.py builds from the new parameters, in
+    every tensor of `_SDPackedWeights` and `SDTrainWeights` (the GEGLU-interleaved copy and the upsampler's phase kernels included)."""
+    import phendiff_amd as P
+    from phendiff_amd.sd_unet import _SDPackedWeights
+    from phendiff_amd.sd_unet_train import SDTrainWeights
+    from test_host_weight_layout import tensors
+    _, _, m, e2 = make_pair(TINY, mode)
+    sched, clean, noise, ts, labels, noisy, _ = batch(2, 16)
+    tr = P.SDUNetTrainer(m, e2, sched, lr=1e-3)
+    before = m.conv_in.weight.detach().clone()
+    tr.step(noisy.cuda(), ts.cuda(), clean.cuda(), noise.cuda(), labels.cuda())
+    torch.cuda.synchronize()
+    assert not torch.equal(m.conv_in.weight.detach(), before)
+    have = dict(list(tensors(m._weights, "w")) + list(tensors(tr._tw, "tw")))
+    fresh = dict(list(tensors(_SDPackedWeights(m, "cuda:0"), "w")) + list(tensors(SDTrainWeights(m, "cuda:0", m._weights.tdt), "tw")))
+    assert set(have) == set(fresh)
+    for kind in (".wff1_glu", ".w4[3]", ".wd4[3]", ".w4_src", ".wkv2", ".wff2_d", "w.conv_in_w", "tw.conv_in_d"):
+        assert any(path.endswith(kind) for path in have), kind
+    for path, t in have.items():
+        assert torch.equal(t, fresh[path]), path
+
+
 def test_sd_training_step_bf16_reduces_loss_and_overlapped_path():
     import phendiff_amd as P
     _, _, m, e2 = make_pair(TINY, "bf16")

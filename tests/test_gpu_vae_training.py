@@ -319,6 +319,33 @@ def test_step_images_follows_torch_adamw_f32():
     assert rel(got.mean, want.mean) < 1e-4 and rel(got.sample(noise=pn.cuda()), want.sample(noise=pn)) < 1e-4
 
 
+def test_vae_device_repack_equals_host_packing():
+    """After `step_images` the pd_pack_weight path must leave exactly what packing.py builds from the new parameters in the
+    `encoder.*` / `quant_conv` entries of `_VaeWeights` and in all of `VaeTrainWeights`; the decoder's entries are not touched."""
+    from phendiff_amd.vae import _VaeWeights
+    from phendiff_amd.vae_train import VaeTrainWeights
+    from test_host_weight_layout import tensors
+    sched, x, noise, pn, ts, labels = trainer_batch()
+    _, tr = make_trainer("f32", sched, lr=1e-3)
+    v = tr.vae
+    tr._bind_vae_weights()                   # (what the first encoder plan does: the sets the step and the re-pack are bound to)
+    w = v._weights
+    decoder = {path: t.clone() for path, t in tensors(w, "w") if ".decoder." in path or path.split(".")[1].startswith(("dec_", "post_quant_"))}
+    before = v.encoder.conv_in.weight.detach().clone()
+    tr.step_images(x.cuda(), ts.cuda(), noise.cuda(), labels.cuda(), posterior_noise=pn.cuda())
+    torch.cuda.synchronize()
+    assert v._weights is w and not torch.equal(v.encoder.conv_in.weight.detach(), before)
+    have = dict(list(tensors(w, "w")) + list(tensors(tr._vtw, "tw")))
+    fresh = dict(list(tensors(_VaeWeights(v, "cuda:0"), "w")) + list(tensors(VaeTrainWeights(v, "cuda:0", w.tdt), "tw")))
+    assert set(have) == set(fresh) and decoder and len(have) > len(decoder)
+    for kind in ("w.enc_in_w", "w.enc_out_w", "w.enc_out_b", "w.quant_w", "w.quant_b", "tw.enc_out_d", "tw.quant_d", ".wqkvd", ".wsd", ".wd"):
+        assert any(path.endswith(kind) for path in have), kind
+    for path, t in have.items():
+        assert torch.equal(t, fresh[path]), path
+    for path, t in decoder.items():
+        assert torch.equal(have[path], t), path
+
+
 def test_step_images_with_a_frozen_vae_is_todays_step():
     sched, x, noise, pn, ts, labels = trainer_batch()
     _, a = make_trainer("bf16", sched, freeze_vae=True)
