@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .training import mark_requires_grad_calls
-from .unet import UNet2DOutput, UNetPlan, _Block, _DT, _Op, _Resnet, _Sampler, _TimestepEmbedding
+from .unet import UNet2DOutput, UNetPlan, _Block, _DT, _Resnet, _Sampler, _TimestepEmbedding
 from .weight_layout import WeightSet
 
 ATTN_HEAD_DIMS = (40, 64, 80, 160)      # pd_attn_d64 for 64, pd_attn_hd for the SD 1.x widths
@@ -354,7 +354,7 @@ class SDUNetPlan(UNetPlan):
         y = self._act(h, w, ch)
         a = L.LayerNormArgs(dtype=self.code, rows=B * h * w, C=ch, eps=eps, x=x.data_ptr(), gamma=gamma.data_ptr(),
                             beta=beta.data_ptr(), y=y.data_ptr())
-        self.ops.append(_Op(self.lib.pd_layernorm, a, "layernorm", 0.0, 2.0 * x.numel() * self._esz()))
+        self._emit(self.lib.pd_layernorm, a, "layernorm", 0.0, 2.0 * x.numel() * self._esz())
         return y
 
     def _attention(self, q, qs, k, v, kvs, heads, nq, nkv, dim_head=64):
@@ -367,8 +367,7 @@ class SDUNetPlan(UNetPlan):
             fn, a, what = self.lib.pd_attn_d64, L.AttnD64Args(**common), "attn_d64"
         else:                           # SD 1.x head dimensions (40 / 80 / 160); anything else is refused by the entry point
             fn, a, what = self.lib.pd_attn_hd, L.AttnHdArgs(D=dim_head, scale=float(dim_head) ** -0.5, **common), "attn_hd"
-        self.ops.append(_Op(fn, a, what, 4.0 * self.B * heads * nq * nkv * dim_head,
-                            (2.0 * self.B * nq + 2.0 * self.B * nkv) * ch * self._esz()))
+        self._emit(fn, a, what, 4.0 * self.B * heads * nq * nkv * dim_head, (2.0 * self.B * nq + 2.0 * self.B * nkv) * ch * self._esz())
         return out, lse
 
     def _transformer(self, name, x):
@@ -404,7 +403,7 @@ class SDUNetPlan(UNetPlan):
             ff = lin(y3, e.wff1, e.bff1, 8 * ch)
             gg = self._act(h, w, 4 * ch)
             ga = L.GegluArgs(dtype=self.code, rows=B * N, inner=4 * ch, x=ff.data_ptr(), y=gg.data_ptr())
-            self.ops.append(_Op(self.lib.pd_geglu, ga, "geglu", 0.0, 3.0 * gg.numel() * esz))
+            self._emit(self.lib.pd_geglu, ga, "geglu", 0.0, 3.0 * gg.numel() * esz)
         else:                            # value * gelu(gate) in the GEMM's epilogue: the projection never reaches HBM
             ff, gg = None, self._linear(y3, e.wff1_glu, e.bff1, 8 * ch, glu=True)
         h3 = lin(gg, e.wff2, e.bff2, ch, residual=h2)
@@ -431,7 +430,7 @@ class SDUNetPlan(UNetPlan):
         # latents NCHW fp32 -> NHWC (32 channels, zero padded), then a plain 3x3 conv
         lat = self._act(H, W, 32)
         self._in_args = L.NchwToNhwcArgs(dtype=self.code, B=B, C=c.in_channels, HW=H * W, Cpad=32, x=None, out=lat.data_ptr())
-        self.ops.append(_Op(self.lib.pd_nchw_to_nhwc, self._in_args, "nchw_to_nhwc", 0.0, B * H * W * c.in_channels * 4.0))
+        self._emit(self.lib.pd_nchw_to_nhwc, self._in_args, "nchw_to_nhwc", 0.0, B * H * W * c.in_channels * 4.0)
         h, _ = self._conv(lat, None, w.conv_in_w, w.conv_in_b, boc[0])
         self.tape.append(SimpleNamespace(kind="sd_conv_in", x=lat, out=h))
         skips = [h]

@@ -21,8 +21,8 @@ from . import _lib as L
 from .sd_unet import (CustomEmbedding, SDUNet2DConditionModel, SDUNetPlan, _SDPackedWeights, _Transformer2D,
                       class_emb_to_encoder_hidden_states)
 from .unet import _Resnet, _Sampler
-from .unet_train import UNetTrainer, UNetTrainPlan
-from .weight_layout import Repacker, WeightSet, contiguous_after as _contiguous_after, pad32, require_adjacent, require_alias
+from .unet_train import UNetTrainer, UNetTrainPlan, _FusedSums
+from .weight_layout import Repacker, WeightSet, pad32, require_adjacent, require_alias
 
 
 EMB_NAME = "class_embedding.inner_module.weight"
@@ -100,23 +100,16 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         self._init_train(tw, params, grads, input_grad, frozen)
 
     # ---- layout checks -----------------------------------------------------------------------------------------------
-    def _check_layout(self):
-        for d in (self.params, self.grads):
-            res = [n for n, mod in self.m.named_modules() if isinstance(mod, _Resnet)]
-            for suffix in ("weight", "bias"):
-                for a, b in zip(res[:-1], res[1:]):
-                    if not _contiguous_after(d[f"{a}.time_emb_proj.{suffix}"], d[f"{b}.time_emb_proj.{suffix}"]):
-                        raise ValueError("time_emb_proj parameters must be stacked contiguously (use sd_training_param_order)")
-            for n, mod in self.m.named_modules():
-                if isinstance(mod, _Transformer2D):
-                    b = f"{n}.transformer_blocks.0"
-                    q, k, v = (d[f"{b}.attn1.{x}.weight"] for x in ("to_q", "to_k", "to_v"))
-                    k2, v2 = (d[f"{b}.attn2.{x}.weight"] for x in ("to_k", "to_v"))
-                    if not (_contiguous_after(q, k) and _contiguous_after(k, v) and _contiguous_after(k2, v2)):
-                        raise ValueError("attn1 to_q/to_k/to_v and attn2 to_k/to_v weights must be adjacent (use sd_training_param_order)")
-            for t in d.values():
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != torch.device(self.device):
-                    raise ValueError("training parameters / gradients must be contiguous fp32 tensors on the plan's device")
+    param_order_name = "sd_training_param_order"
+
+    def _fused_param_groups(self):
+        groups = self._time_emb_proj_groups()
+        for n, mod in self.m.named_modules():
+            if isinstance(mod, _Transformer2D):
+                b = f"{n}.transformer_blocks.0"
+                for attn, which in ((".attn1", ("to_q", "to_k", "to_v")), (".attn2", ("to_k", "to_v"))):
+                    groups.append(("attn1 to_q/to_k/to_v and attn2 to_k/to_v weights must be adjacent", [f"{b}{attn}.{x}.weight" for x in which]))
+        return groups
 
     def _zero_bias_len(self):
         return 8 * max(self.m.config.block_out_channels) + 64
@@ -149,10 +142,10 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         if self._want_ehs_grad():
             dehs, dt = self._dehs[0], self.grads[EMB_NAME]
             a = L.TokenEmbeddingGradArgs(dtype=self.code, rows=self.B, dim=dt.shape[1], num_classes=dt.shape[0],
-                                         row_stride=self.tokens * dt.shape[1], labels=None, d=dehs.data_ptr(),
-                                         dtable=self._G(EMB_NAME).data_ptr())
+                                         row_stride=self.tokens * dt.shape[1], labels=None, d=dehs.data_ptr(), dtable=dt.data_ptr())
             self._token_grad_args = a
-            self._b(self.lib.pd_token_embedding_grad, a, "token_embedding_grad")
+            self._emit(self.lib.pd_token_embedding_grad, a, "token_embedding_grad")
+            self._mark_ready(EMB_NAME)
 
     def _bwd_record(self, rec):
         if rec.kind == "transformer":
@@ -160,18 +153,13 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         elif rec.kind == "sd_conv_in":
             if self.input_grad:
                 dout = self._g(rec.out)[0]
-                ops, self.ops = self.ops, self.bwd_ops
-                try:
-                    self._conv(dout, None, self.tw.conv_in_d, self._zero_bias, self.m.config.in_channels, out_mode=L.PD_OUT_NCHW_F32,
-                               cout_pad=32, y=self.dsample, stats=False)
-                finally:
-                    self.ops = ops
-                self.bwd_ops[-1].what = "dgrad3x3"
+                self._conv(dout, None, self.tw.conv_in_d, self._zero_bias, self.m.config.in_channels, out_mode=L.PD_OUT_NCHW_F32,
+                           cout_pad=32, y=self.dsample, stats=False, what="dgrad3x3")
             if not self.param_grads:
                 return
             dout = self._g(rec.out)[0]
-            self._bias_grad(dout, self._G("conv_in.bias"))
-            self._wgrad(rec.x, None, None, 0, dout, self._G("conv_in.weight"), cin_valid=self.m.config.in_channels)
+            self._bias_grad(dout, "conv_in.bias")
+            self._wgrad(rec.x, None, None, 0, dout, "conv_in.weight", cin_valid=self.m.config.in_channels)
         else:
             super()._bwd_record(rec)
 
@@ -184,14 +172,17 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         rows = B * h * w
         dx = self._tmp((B, h, w, ch), tag)
         partial = None
-        dgam, dbet = self._G2(pname + ".weight", pname + ".bias")
+        affine = (pname + ".weight", pname + ".bias")
+        dgam, dbet = self._grad(affine), self._grad(affine[::-1])       # both, or neither when both are frozen (one launch writes the two)
         fuse = bias_name is not None and dgam is not None and ch <= 1536 and bias_name not in self.frozen
-        dxsum = self._G(bias_name) if fuse else None
+        dxsum = self._grad(bias_name) if fuse else None
         if dgam is not None:
             partial = self._tmp((self.lib.pd_layernorm_bwd_blocks(rows) * (3 if fuse else 2) * ch,), "lnpart3" if fuse else "lnpart", torch.float32)
         a = L.LayerNormBwdArgs(dtype=self.code, rows=rows, C=ch, eps=eps, x=x.data_ptr(), dy=dy.data_ptr(), gamma=gamma.data_ptr(),
                                res=L.ptr(res), dx=dx.data_ptr(), dgamma=L.ptr(dgam), dbeta=L.ptr(dbet), partial=L.ptr(partial), dxsum=L.ptr(dxsum))
-        self._b(self.lib.pd_layernorm_bwd, a, "layernorm_bwd", 0.0, (3 + (res is not None)) * x.numel() * self._esz())
+        self._emit(self.lib.pd_layernorm_bwd, a, "layernorm_bwd", 0.0, (3 + (res is not None)) * x.numel() * self._esz())
+        if dgam is not None:
+            self._mark_ready(affine + ((bias_name,) if fuse else ()))
         return dx, fuse
 
     def _attn_bwd64(self, q, qs, k, v, kvs, o, do, lse, heads, nq, nkv, dq, dqs, dk, dv, dkvs):
@@ -199,24 +190,22 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         a = L.AttnD64BwdArgs(dtype=self.code, B=self.B, heads=heads, Nq=nq, Nkv=nkv, q=q, q_stride=qs, k=k, v=v, kv_stride=kvs,
                              o=o.data_ptr(), dout=do.data_ptr(), o_stride=heads * 64, lse=lse.data_ptr(), delta=delta.data_ptr(),
                              dq=dq, dq_stride=dqs, dk=dk, dv=dv, dkv_stride=dkvs)
-        self._b(self.lib.pd_attn_d64_bwd, a, "attn_d64_bwd", 10.0 * self.B * heads * nq * nkv * 64,
+        self._emit(self.lib.pd_attn_d64_bwd, a, "attn_d64_bwd", 10.0 * self.B * heads * nq * nkv * 64,
                 (4.0 * nq + 4.0 * nkv) * self.B * heads * 64 * self._esz())
 
     def _transformer_bwd(self, rec):
         e, te, n = rec.e, self.tw.transformers[rec.name], rec.name
         blk = n + ".transformer_blocks.0"
-        G = self._G
         B, h, w, ch = rec.x.shape
         N, esz, T = h * w, self._esz(), self.tokens
-        lin_w = lambda x, dy, wname, gn=None: self._wgrad(x, None, gn, 0, dy, G(*wname) if isinstance(wname, tuple) else G(wname),
-                                                          ksize=1, pad=0)
+        lin_w = lambda x, dy, wname, gn=None: self._wgrad(x, None, gn, 0, dy, wname, ksize=1, pad=0)
         dout = self._g(rec.out)[0]
         # proj_out (+ residual x: folded into the GroupNorm backward at the end)
-        self._bias_grad(dout, G(n + ".proj_out.bias"))
+        self._bias_grad(dout, n + ".proj_out.bias")
         lin_w(rec.h3, dout, n + ".proj_out.weight")
         dh3 = self._dgrad(dout, te.w_out_d, ch, ksize=1, tag="t_dh3")
         # feed-forward: h3 = ff2(geglu(ff1(LN3(h2)))) + h2
-        self._bias_grad(dh3, G(blk + ".ff.net.2.bias"))
+        self._bias_grad(dh3, blk + ".ff.net.2.bias")
         lin_w(rec.gg, dh3, blk + ".ff.net.2.weight")
         dgg = self._dgrad(dh3, te.wff2_d, 4 * ch, ksize=1, tag="t_dgg")
         dff = self._tmp((B, h, w, 8 * ch), "t_dff")
@@ -228,16 +217,16 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
             gws = torch.empty((B * gs * 8 * ch,), dtype=torch.float32, device=self.device)      # this block's own (its fold may run on the second stream)
             self.bufs.append(gws)
             ga.sums, ga.sum_splits, ga.B = gws.data_ptr(), gs, B
-            self._fused_sums[id(dff)] = (gws, gs, True)
-        self._b(self.lib.pd_geglu_bwd, ga, "geglu_bwd", 0.0, 5.0 * dgg.numel() * esz)
-        self._bias_grad(dff, G(blk + ".ff.net.0.proj.bias"))
+            self._fused_sums[id(dff)] = _FusedSums(gws, gs, True)
+        self._emit(self.lib.pd_geglu_bwd, ga, "geglu_bwd", 0.0, 5.0 * dgg.numel() * esz)
+        self._bias_grad(dff, blk + ".ff.net.0.proj.bias")
         self._fused_sums.pop(id(dff), None)               # (dff is a scratch buffer other blocks reuse)
         lin_w(rec.y3, dff, blk + ".ff.net.0.proj.weight")
         dy3 = self._dgrad(dff, te.wff1_d, ch, ksize=1, tag="t_dy")
         dh2, fb = self._ln_bwd(rec.h2, e.ln3, blk + ".norm3", dy3, dh3, "t_dh2", bias_name=blk + ".attn2.to_out.0.bias")
         # cross attention: h2 = to_out(attn(to_q(LN2(h1)), to_k(ehs), to_v(ehs))) + h1
         if not fb:
-            self._bias_grad(dh2, G(blk + ".attn2.to_out.0.bias"))
+            self._bias_grad(dh2, blk + ".attn2.to_out.0.bias")
         lin_w(rec.a2, dh2, blk + ".attn2.to_out.0.weight")
         da2 = self._dgrad(dh2, te.wo2_d, ch, ksize=1, tag="t_da")
         dq2 = self._tmp((B, h, w, ch), "t_dq2")
@@ -246,26 +235,26 @@ class SDUNetTrainPlan(UNetTrainPlan, SDUNetPlan):
         self._attn_bwd64(rec.q2.data_ptr(), ch, kvp, kvp + ch * esz, 2 * ch, rec.a2, da2, rec.lse2, e.heads, N, T,
                          dq2.data_ptr(), ch, dkv.data_ptr(), dkv.data_ptr() + ch * esz, 2 * ch)
         lin_w(rec.y2, dq2, blk + ".attn2.to_q.weight")
-        lin_w(self.ehs, dkv, (blk + ".attn2.to_k.weight", (blk + ".attn2.to_v.weight",)))       # fused [2C][D] gradient
+        lin_w(self.ehs, dkv, (blk + ".attn2.to_k.weight", blk + ".attn2.to_v.weight"))       # fused [2C][D] gradient
         if self._want_ehs_grad():
             self._dgrad(dkv, te.wkv2_d, self.ehs.shape[3], ksize=1, into=self._dehs)
         dy2 = self._dgrad(dq2, te.wq2_d, ch, ksize=1, tag="t_dy")
         dh1, fb = self._ln_bwd(rec.h1, e.ln2, blk + ".norm2", dy2, dh2, "t_dh1", bias_name=blk + ".attn1.to_out.0.bias")
         # self attention: h1 = to_out(attn(qkv(LN1(h0)))) + h0
         if not fb:
-            self._bias_grad(dh1, G(blk + ".attn1.to_out.0.bias"))
+            self._bias_grad(dh1, blk + ".attn1.to_out.0.bias")
         lin_w(rec.a1, dh1, blk + ".attn1.to_out.0.weight")
         da1 = self._dgrad(dh1, te.wo1_d, ch, ksize=1, tag="t_da")
         dqkv = self._tmp((B, h, w, 3 * ch), "t_dqkv")
         p, dp = rec.qkv.data_ptr(), dqkv.data_ptr()
         self._attn_bwd64(p, 3 * ch, p + ch * esz, p + 2 * ch * esz, 3 * ch, rec.a1, da1, rec.lse1, e.heads, N, N,
                          dp, 3 * ch, dp + ch * esz, dp + 2 * ch * esz, 3 * ch)
-        lin_w(rec.y1, dqkv, (blk + ".attn1.to_q.weight", (blk + ".attn1.to_k.weight", blk + ".attn1.to_v.weight")))
+        lin_w(rec.y1, dqkv, tuple(f"{blk}.attn1.{x}.weight" for x in ("to_q", "to_k", "to_v")))
         dy1 = self._dgrad(dqkv, te.wqkv1_d, ch, ksize=1, tag="t_dy")
         dh0, fb = self._ln_bwd(rec.h0, e.ln1, blk + ".norm1", dy1, dh1, "t_dh0", bias_name=n + ".proj_in.bias")
         # proj_in over GroupNorm(x) (no SiLU)
         if not fb:
-            self._bias_grad(dh0, G(n + ".proj_in.bias"))
+            self._bias_grad(dh0, n + ".proj_in.bias")
         lin_w(rec.x, dh0, n + ".proj_in.weight", gn=rec.gn)
         dz = self._dgrad(dh0, te.w_in_d, ch, ksize=1, tag="t_dz")
         self._gn_bwd(rec.gn, dz, 0, res=dout, wname=n + ".norm")
@@ -393,33 +382,18 @@ class SDUNetTrainer(UNetTrainer):
         ``vae``: the pipeline's :class:`phendiff_amd.vae.AutoencoderKL` (``components_to_train autoencoder``): it trains when at
         least one of its parameters does (:func:`sd_training_layout`); :meth:`step_images` then encodes inside the step and sends
         the loss gradient back through ``quant_conv`` and the encoder.  ``_vae_chunk``: tests force the encoder's chunk size."""
-        from .training import DiffusionLoss, FlatAdamWEMA, broadcast_from_rank0_
         model.require_attention_backward("SDUNetTrainer (SD fine-tuning)")
         self.model, self.class_embedding, self.scheduler, self.vae = model, class_embedding, scheduler, vae
-        dev = device or model.device
-        if torch.device(dev).type != "cuda":
-            raise L.PhenDiffHipError("phendiff_amd trains on MI355X only (no CPU fallback): move the model to 'cuda'")
         order, flags, never, self._vae_trains = sd_training_layout(model, class_embedding, vae, train_class_embedding, trainable)
-        if not any(flags):
-            raise ValueError("SDUNetTrainer: no trainable parameter (every parameter is frozen)")
-        if self._vae_trains and torch.device(vae.device) != torch.device(dev):
+        if self._vae_trains and torch.device(vae.device) != torch.device(device or model.device):
             raise L.PhenDiffHipError("SDUNetTrainer: the autoencoder must live on the UNet's device")
         # parameters the loss never reaches get what torch.optim.AdamW gives `grad is None`: no update, no decay, no moments -- the
         # optimizer treats them as frozen (their EMA shadow is the parameter itself), and so do the all-reduce buckets
         self.trainable_flags, self.never_graded, self._vae_chunk = list(flags), never, _vae_chunk
         flags = [f and n not in never for (n, _), f in zip(order, flags)]
-        self.frozen = frozenset(n for (n, _), f in zip(order, flags) if not f)
-        self.opt = FlatAdamWEMA([p for _, p in order], lr, use_ema=use_ema, max_grad_norm=max_grad_norm, **adamw)
-        self.opt.set_trainable(flags)
-        if train_class_embedding and flags[-1]:
-            self.opt.set_tail(class_embedding.inner_module.weight.numel(), (EMB_NAME,))
-        # DDP's wrap-time broadcast (train.py:311-326): rank 0's parameters everywhere; the EMA shadow starts from them
-        broadcast_from_rank0_(self.opt.flat, group)
-        if self.opt.ema is not None:
-            self.opt.ema.copy_(self.opt.flat)
-        self.params = {n: p.data for n, p in order}
-        self.grads = {n: p.grad for n, p in order}
-        model.invalidate()
+        tail = (class_embedding.inner_module.weight.numel(), (EMB_NAME,)) if train_class_embedding and flags[-1] else None
+        self._uncond = False
+        self._init_state(order, flags, tail, lr, device, use_ema, max_grad_norm, group, adamw)
         if self._vae_trains:
             if vae.compute_dtype != model.compute_dtype:
                 raise ValueError("SDUNetTrainer: the autoencoder and the UNet must share one compute_dtype")
@@ -430,20 +404,11 @@ class SDUNetTrainer(UNetTrainer):
             self._vfrozen = frozenset(n[k:] for n in self.frozen if n.startswith(VAE_PREFIX))
             vae.invalidate()
         self._vplans, self._vtw, self._vrepack, self._bound_vw = {}, None, None, None
-        self.loss_fn = DiffusionLoss(scheduler, dev)
-        if getattr(model, "compute_dtype", None) == "fp16":      # --mixed_precision fp16: accelerate's GradScaler (training.LossScaler)
-            from .training import LossScaler
-            self.opt.scaler = LossScaler()
-        self.device = dev
-        self._plans = {}
-        self._tw = None
-        self._repack = None
-        self._uncond = False
 
     def checkpoint_modules(self):
         """accelerate's numbering of the prepared models (train.py:318-326): unet 0, vae 1 (only when it trains: a frozen one is not
         the trainer's), class embedding 2 -- flat names carry the ``vae.`` / ``class_embedding.`` prefixes."""
-        return sd_checkpoint_modules(self.model, self.class_embedding, getattr(self, "vae", None), self.params)
+        return sd_checkpoint_modules(self.model, self.class_embedding, self.vae, self.params)
 
     def _optimizer_step(self, lr):
         # an unconditional step leaves the CustomEmbedding without a gradient: torch's AdamW skips it (EMA still steps)
@@ -461,7 +426,7 @@ class SDUNetTrainer(UNetTrainer):
     def _make_plan(self, key):
         m = self.model
         return SDUNetTrainPlan(m, m._weights, self._tw, *key, self.device, self.params, self.grads, frozen=self.frozen,
-                               input_grad=getattr(self, "_vae_trains", False))      # d loss / d noisy latents feeds the encoder's backward
+                               input_grad=self._vae_trains)      # d loss / d noisy latents feeds the encoder's backward
 
     def plan_for(self, B, H, W, tokens=77):
         self._bind_weights()
@@ -482,7 +447,7 @@ class SDUNetTrainer(UNetTrainer):
 
     def forward_backward(self, noisy, timesteps, clean, noise, class_labels=None, class_emb=None, after_op=None, unconditional=None):
         if unconditional is None:
-            unconditional = getattr(self, "_uncond", False)
+            unconditional = self._uncond
         B, _, H, W = noisy.shape
         plan = self.plan_for(B, H, W)
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -499,7 +464,7 @@ class SDUNetTrainer(UNetTrainer):
     def step(self, noisy, timesteps, clean, noise, class_labels, unconditional: bool = False, lr: Optional[float] = None,
              group=None, overlap: bool = True, bucket_bytes: int = 64 << 20):
         """3.46 GB of fp32 gradients per step: 64 MB buckets (xGMI rings are per-link bound: few, large messages)."""
-        if getattr(self, "_vae_trains", False):
+        if self._vae_trains:
             raise ValueError("SDUNetTrainer: the autoencoder trains -- the step starts from images (step_images), not from latents")
         self._uncond = bool(unconditional)
         return super().step(noisy, timesteps, clean, noise, class_labels=class_labels, class_emb=None, lr=lr, group=group,
@@ -542,7 +507,7 @@ class SDUNetTrainer(UNetTrainer):
 
     def refresh_weights(self):
         super().refresh_weights()
-        if getattr(self, "_vae_trains", False) and not (self.vae._weights is None and self._bound_vw is None):
+        if self._vae_trains and not (self.vae._weights is None and self._bound_vw is None):
             from .vae_train import _VaeRepacker
             self._bind_vae_weights()
             if self._vrepack is None:
@@ -563,7 +528,7 @@ class SDUNetTrainer(UNetTrainer):
         from .vae import DiagonalGaussianDistribution
         from .vae_train import latent_chain_bwd
         if unconditional is None:
-            unconditional = getattr(self, "_uncond", False)
+            unconditional = self._uncond
         vae, c = self.vae, self.vae.config
         B, _, H, W = images.shape
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -615,9 +580,8 @@ class SDUNetTrainer(UNetTrainer):
         ``noise`` / ``posterior_noise``: (B, latent, H/8, W/8); the posterior noise is drawn on the device when None.
         With an attached sampler (``attach_sampler``) ``timesteps``, ``noise`` and ``posterior_noise`` may be None: the sampler draws the
         posterior noise first (``randn``), then noise and timesteps, each consuming one of its steps."""
-        check_training_images(getattr(self, "vae", None), images)
-        vae = self.vae
-        sampler = getattr(self, "sampler", None)
+        check_training_images(self.vae, images)
+        vae, sampler = self.vae, self.sampler
         if sampler is not None and (timesteps is None or noise is None):
             nlev = len(vae.config.block_out_channels)
             shape = (images.shape[0], vae.config.latent_channels, images.shape[2] >> (nlev - 1), images.shape[3] >> (nlev - 1))
@@ -645,7 +609,7 @@ class SDUNetTrainer(UNetTrainer):
         self._uncond = bool(unconditional)
         loss, _ = self.images_forward_backward(images, timesteps, noise, class_labels, posterior_noise)
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
-        if world > 1 or getattr(self, "force_collectives", False):
+        if world > 1 or self.force_collectives:
             # the buckets are exchanged once both backward plans have run (the overlapped schedule of `step` follows ONE plan's launches)
             from .training import allreduce_mean_ranges_
             allreduce_mean_ranges_(self.opt.grad, self.opt.trainable_ranges(), group, bucket_bytes=bucket_bytes)

@@ -414,6 +414,7 @@ class UNetPlan:
         self._temb_ptr_fields = []
         self._in_args = None
         self._out_args = None
+        self._centered = None   # center_input_sample: the 2 x - 1 tensor conv_in reads (set by _build)
         self._build()
 
     def _esz(self):
@@ -432,6 +433,14 @@ class UNetPlan:
         return t
 
     # ---- op emitters -----------------------------------------------------------------------------
+    _sink = None            # list the emitters append to: ``self.ops``, or ``bwd_ops`` once a training plan lays out its backward
+
+    def _emit(self, fn, args, what, flops=0.0, nbytes=0.0) -> _Op:
+        """The one place an op enters the plan."""
+        op = _Op(fn, args, what, flops, nbytes)
+        (self.ops if self._sink is None else self._sink).append(op)
+        return op
+
     def _gn(self, x0, x1, gamma, beta, eps, temb_off=None):
         """GroupNorm(32) of [x0 | x1] -> per-(sample, channel) scale/shift, from the statistics the producers of x0 / x1
         emitted in their epilogues (no pass over the tensors)."""
@@ -451,12 +460,12 @@ class UNetPlan:
             mean, rstd = self._f32(self.B, self.groups), self._f32(self.B, self.groups)
             a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
             self.gn_saved[id(scale)] = SimpleNamespace(mean=mean, rstd=rstd, gamma=gamma, beta=beta, x0=x0, x1=x1)
-        self.ops.append(_Op(self.lib.pd_gn_finalize, a, "gn_finalize", 0.0, self.B * (t0 * c0 + t1 * c1) * 8.0))
+        self._emit(self.lib.pd_gn_finalize, a, "gn_finalize", 0.0, self.B * (t0 * c0 + t1 * c1) * 8.0)
         return scale, shift
 
     def _conv(self, x0, x1, wpk, bias, cout, *, ksize=3, stride=1, pad=1, upsample=0, silu=0, gn=None, temb_off=None,
               residual=None, out_mode=L.PD_OUT_NHWC, heads=0, cout_pad=None, y=None, stats=True, im2col3=0, src_ptr=None,
-              src_shape=None, tail=None):
+              src_shape=None, tail=None, what=None):
         B, hin, win, c0 = src_shape if src_shape is not None else x0.shape
         c1 = x1.shape[3] if x1 is not None else 0
         hc, wc = (2 * hin, 2 * win) if upsample else (hin, win)
@@ -495,7 +504,7 @@ class UNetPlan:
             + cout * cin * ksize * ksize * esz + (B * hout * wout * tail_c + cout * tail_c) * esz
         if out_mode == L.PD_OUT_NCHW_F32:
             nbytes += B * hout * wout * cout * (4 - esz)
-        self.ops.append(_Op(self.lib.pd_conv, a, f"conv{ksize}x{ksize}", flops, nbytes))
+        self._emit(self.lib.pd_conv, a, what or f"conv{ksize}x{ksize}", flops, nbytes)
         return y, a
 
     @property
@@ -525,21 +534,21 @@ class UNetPlan:
                            w_packed=s.w4[ph].data_ptr(), bias=s.b.data_ptr(), temb=None, temb_stride=self.w.proj_dim, residual=None,
                            y=y.data_ptr(), stats_out=st.data_ptr(), im2col3=0, tail_x0=None, tail_x1=None, tail_C0=0, tail_C1=0, phase=1 + ph)
             # FLOPs / bytes of the LOGICAL layer (3x3 over the upsampled tensor: what the roofline accounting quotes) shared by the four launches
-            self.ops.append(_Op(self.lib.pd_conv, a, "conv3x3", 2.0 * B * 4 * h * w * ch * ch * 9 / 4.0,
-                                (B * h * w * ch + B * 4 * h * w * ch) * esz / 4.0 + ch * ch * 4 * esz))
+            self._emit(self.lib.pd_conv, a, "conv3x3", 2.0 * B * 4 * h * w * ch * ch * 9 / 4.0,
+                       (B * h * w * ch + B * 4 * h * w * ch) * esz / 4.0 + ch * ch * 4 * esz)
         return y
 
     # pd_conv applies GroupNorm + SiLU while staging, once per 64-channel output tile; from this many output channels on
     # the input is normalised ONCE by pd_gn_apply instead and the convolution (and its weight gradient) runs without a prologue
     PREAPPLY_MIN_COUT = int(__import__("os").environ.get("PD_PREAPPLY_MIN_COUT", 320))      # measured: a win from 5 output tiles on (SD UNet: 7.7 vs 9.4 ms of 3x3 convs per forward), neutral at 4
 
-    def _gn_apply(self, x0, x1, gn, silu):
+    def _gn_apply(self, x0, x1, gn, silu, what="gn_apply"):
         B, h, w, c0 = x0.shape
         c1 = x1.shape[3] if x1 is not None else 0
         y = self._act(h, w, c0 + c1)
         a = L.GnApplyArgs(dtype=self.code, B=B, HW=h * w, C0=c0, C1=c1, silu=silu, x0=x0.data_ptr(), x1=L.ptr(x1),
                           scale=gn[0].data_ptr(), shift=gn[1].data_ptr(), y=y.data_ptr())
-        self.ops.append(_Op(self.lib.pd_gn_apply, a, "gn_apply", 0.0, 2.0 * y.numel() * self._esz()))
+        self._emit(self.lib.pd_gn_apply, a, what, 0.0, 2.0 * y.numel() * self._esz())
         return y
 
     def _linear(self, x, wpk, bias, cout, residual=None, y=None, gn=None, stats=False, what="linear", glu=False):
@@ -560,8 +569,8 @@ class UNetPlan:
                          w_packed=wpk.data_ptr(), bias=bias.data_ptr(), residual=L.ptr(residual), y=y.data_ptr(),
                          scale=L.ptr(gn[0]) if gn else None, shift=L.ptr(gn[1]) if gn else None, rows_per_sample=h * w, qkv_heads=0,
                          stats_out=L.ptr(st), glu=int(glu))
-        self.ops.append(_Op(self.lib.pd_linear, a, what, 2.0 * M * K * cout,
-                            (M * K + M * (cout // 2 if glu else cout) * (2 if residual is not None else 1) + K * cout) * esz))
+        self._emit(self.lib.pd_linear, a, what, 2.0 * M * K * cout,
+                   (M * K + M * (cout // 2 if glu else cout) * (2 if residual is not None else 1) + K * cout) * esz)
         return y
 
     @staticmethod
@@ -607,7 +616,7 @@ class UNetPlan:
             self._kmax_arena = torch.zeros(ARENA, dtype=torch.float32, device=self.device)
             self._kmax_used = 0
             self.bufs.append(self._kmax_arena)
-            self.ops.append(_Op(self.lib.pd_zero, L.ZeroArgs(ptr=self._kmax_arena.data_ptr(), bytes=ARENA * 4), "zero", 0.0, ARENA * 4))
+            self._emit(self.lib.pd_zero, L.ZeroArgs(ptr=self._kmax_arena.data_ptr(), bytes=ARENA * 4), "zero", 0.0, ARENA * 4)
         ptr = self._kmax_arena.data_ptr() + 4 * self._kmax_used
         self._kmax_used += n
         return ptr
@@ -644,7 +653,7 @@ class UNetPlan:
                     self.bufs.append(ws)
                 a.fold_ws, a.fold_ws_bytes = ws.data_ptr(), need
             esz_ = self._esz()
-            self.ops.append(_Op(self.lib.pd_linear, a, "conv1x1", 2.0 * M * ch * 3 * ch, (M * ch * 4 + 3 * ch * ch) * esz_))
+            self._emit(self.lib.pd_linear, a, "conv1x1", 2.0 * M * ch * 3 * ch, (M * ch * 4 + 3 * ch * ch) * esz_)
         else:
             kmax2 = None
             qkv, _ = self._conv(x, None, e.wqkv, e.bqkv, 3 * ch, ksize=1, pad=0, gn=gn, out_mode=L.PD_OUT_QKV_HEADS,
@@ -655,7 +664,7 @@ class UNetPlan:
                        v=qkv[2].data_ptr(), out=o.data_ptr(), lse=L.ptr(lse), kmax2=kmax2)
         esz = self._esz()
         N = h * w
-        self.ops.append(_Op(self.lib.pd_attn_d8, a, "attn_d8", 4.0 * B * e.heads * N * N * 8, 4.0 * B * N * ch * esz))
+        self._emit(self.lib.pd_attn_d8, a, "attn_d8", 4.0 * B * e.heads * N * N * 8, 4.0 * B * N * ch * esz)
         if self._linear_ok(o):
             out = self._linear(o, e.wo, e.bo, ch, residual=x, stats=True, what="conv1x1")
         else:
@@ -690,7 +699,7 @@ class UNetPlan:
             a = L.AttnWideArgs(dtype=self.code, B=B, heads=e.heads, D=d, Nq=N, Nkv=N, scale=float(d) ** -0.5, q=p, q_stride=3 * ch,
                                k=p + ch * esz, v=p + 2 * ch * esz, kv_stride=3 * ch, out=o.data_ptr(), out_stride=ch, lse=L.ptr(lse))
             fn, what = self.lib.pd_attn_wide, "attn_wide"
-        self.ops.append(_Op(fn, a, what, 4.0 * B * N * N * ch, 4.0 * B * N * ch * esz))
+        self._emit(fn, a, what, 4.0 * B * N * N * ch, 4.0 * B * N * ch * esz)
         if self._linear_ok(o):
             out = self._linear(o, e.wo, e.bo, ch, residual=x, stats=True, what="conv1x1")
         else:
@@ -720,7 +729,7 @@ class UNetPlan:
             ones, two, neg = self._center_const
             ca = L.AddNoiseArgs(numel=centered.numel(), per_sample=centered[0].numel(), velocity=0, x=None, noise=ones.data_ptr(),
                                 sa=two.data_ptr(), sb=neg.data_ptr(), out=centered.data_ptr())
-            self.ops.append(_Op(self.lib.pd_add_noise, ca, "center", 0.0, 2.0 * centered.numel() * 4))
+            self._emit(self.lib.pd_add_noise, ca, "center", 0.0, 2.0 * centered.numel() * 4)
         a0, conv_in_args = self._conv(None, None, w.conv_in_wv, w.conv_in_b, boc[0], ksize=1, pad=0,
                                       im2col3=c.in_channels, src_shape=(B, H, W, 32))
         if centered is not None:

@@ -20,14 +20,15 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib as L
 from .unet import CustomCondUNet2DModel, UNetPlan, _Attention, _Op, _PackedWeights, _Resnet, _Sampler
-from .weight_layout import (Repacker, WeightSet, contiguous_after as _contiguous_after, fuse_pack_jobs,  # noqa: F401 (re-exported)
-                            pad32, require_alias, run_pack_jobs)
+from .weight_layout import (Repacker, WeightSet, fuse_pack_jobs, pad32, require_adjacent, require_alias,  # noqa: F401 (re-exported)
+                            run_pack_jobs)
 
 
 # diagnostic (same-box A/B): route the 1x1 gradients through pd_conv / pd_conv_wgrad as the 3x3 ones
@@ -38,6 +39,15 @@ _NO_LINEAR_GRADS = bool(os.environ.get("PD_NO_LINEAR_GRADS"))
 # diagnostic (same-box A/B): keep the GroupNorm-prologue 1x1 weight gradients on pd_conv_wgrad (round 3 routes them through
 # pd_gn_apply + pd_token_wgrad)
 _NO_PREAPPLY_WGRAD = bool(os.environ.get("PD_NO_PREAPPLY_WGRAD"))
+
+# per-split channel sums [B][splits][C] the last writer of a gradient buffer left; ``own_workspace``: no other launch reuses ``sums``
+_FusedSums = namedtuple("_FusedSums", "sums splits own_workspace")
+
+
+def _names(names) -> Tuple[str, ...]:
+    """A parameter name, or the names one fused launch writes (the first one's gradient is where the launch starts)."""
+    return (names,) if isinstance(names, str) else tuple(names)
+
 
 def training_param_order(m: CustomCondUNet2DModel) -> List[Tuple[str, torch.nn.Parameter]]:
     """(name, parameter) pairs in the order the flat training buffers use: all ``time_emb_proj`` weights (then biases)
@@ -126,6 +136,10 @@ class UNetTrainPlan(UNetPlan):
         # for the three gradient launches `_temb_bwd` adds (round 6).  "identity": the rows are an INPUT (nothing to differentiate)
         self._class_mlp = getattr(w, "class_mode", None) == "timestep"
         self._class_mlp_ran = False
+        self._class_mlp_ops = (0, 0)    # [start, end) of the class MLP's gradient launches in bwd_ops (skipped when the rows bypassed it)
+        self._labels = None             # the step's class ids, for the embedding-table gradient ...
+        self._emb_grad_at = -1          # ... launched in front of this backward op
+        self._side_state = None
         self.dsample = self._f32(B, m.config.in_channels, H, W) if input_grad else None
         if self.param_grads:
             self._check_layout()
@@ -136,9 +150,8 @@ class UNetTrainPlan(UNetPlan):
         self.temb_table = self._f32(B, w.proj_dim)
         self.bwd_ops: List[_Op] = []
         self.grad_ready: Dict[str, int] = {}   # parameter name -> index of the last backward op that writes its gradient
-        self._emb_grad_op = None
         self._gact = {}
-        self._fused_sums = {}      # id(gradient buffer) -> (per-split channel sums [B][splits][C], splits) left by its last writer
+        self._fused_sums = {}      # id(gradient buffer) -> _FusedSums left by its last writer
         self._sum_owner = {}       # id(activation) -> (GnBwdArgs, field) currently emitting those sums
         self._tmp_cache = {}
         self._wgrad_args = []
@@ -146,19 +159,24 @@ class UNetTrainPlan(UNetPlan):
         self._build_backward()
 
     # ---- layout checks ---------------------------------------------------------------------------
+    param_order_name = "training_param_order"
+
+    def _time_emb_proj_groups(self):
+        res = [n for n, mod in self.m.named_modules() if isinstance(mod, _Resnet)]
+        return [("time_emb_proj parameters must be stacked contiguously", [f"{n}.time_emb_proj.{suffix}" for n in res])
+                for suffix in ("weight", "bias")]
+
+    def _fused_param_groups(self):
+        """(what must hold, names) of every group of parameters one launch reads / writes as ONE matrix or vector."""
+        return self._time_emb_proj_groups() + [
+            ("to_q/to_k/to_v parameters must be adjacent", [f"{n}.{x}.{suffix}" for x in ("to_q", "to_k", "to_v")])
+            for n, mod in self.m.named_modules() if isinstance(mod, _Attention) for suffix in ("weight", "bias")]
+
     def _check_layout(self):
+        groups = self._fused_param_groups()
         for d in (self.params, self.grads):
-            res = [n for n, mod in self.m.named_modules() if isinstance(mod, _Resnet)]
-            for suffix in ("weight", "bias"):
-                for a, b in zip(res[:-1], res[1:]):
-                    if not _contiguous_after(d[f"{a}.time_emb_proj.{suffix}"], d[f"{b}.time_emb_proj.{suffix}"]):
-                        raise ValueError("time_emb_proj parameters must be stacked contiguously (use training_param_order)")
-            for n, mod in self.m.named_modules():
-                if isinstance(mod, _Attention):
-                    for suffix in ("weight", "bias"):
-                        q, k, v = (d[f"{n}.{x}.{suffix}"] for x in ("to_q", "to_k", "to_v"))
-                        if not (_contiguous_after(q, k) and _contiguous_after(k, v)):
-                            raise ValueError("to_q/to_k/to_v parameters must be adjacent (use training_param_order)")
+            for message, names in groups:
+                require_adjacent(f"{message} (use {self.param_order_name})", [d[n] for n in names])
             for t in d.values():
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.device != torch.device(self.device):
                     raise ValueError("training parameters / gradients must be contiguous fp32 tensors on the plan's device")
@@ -198,9 +216,9 @@ class UNetTrainPlan(UNetPlan):
         a.feat, a.z1 = None, None
         self.run(sample.data_ptr(), self.temb_table.data_ptr(), out.data_ptr(), stream)
         self._labels = labels
-        src = getattr(self, "_centered", None)        # center_input_sample: what conv_in multiplied is 2 x - 1
+        src = self._centered if self._centered is not None else sample        # center_input_sample: what conv_in multiplied is 2 x - 1
         for args in self._sample_ptr_args:
-            args.x = src.data_ptr() if src is not None else sample.data_ptr()
+            args.x = src.data_ptr()
         self.keepalive = (sample, timesteps, labels, class_emb, out)
 
     # ---- backward emitters -----------------------------------------------------------------------
@@ -231,37 +249,29 @@ class UNetTrainPlan(UNetPlan):
                     setattr(args, fld, None)
                     del self._sum_owner[key]
 
-    def _b(self, fn, args, what, flops=0.0, nbytes=0.0):
-        self.bwd_ops.append(_Op(fn, args, what, flops, nbytes))
-
-    def _G(self, name, span=()):
-        """Gradient tensor of a parameter, noting that the NEXT emitted op writes it (and the parameters fused behind it:
-        ``span``) -- the schedule the overlapped data-parallel all-reduce follows.  None when the parameter (and everything fused
-        behind it) is frozen: the emitters then skip the launch (a fused launch with one trainable member still runs and writes the
-        frozen members' segments too -- ``FlatAdamWEMA.step`` zeroes those before the norm)."""
-        if not self.param_grads:
+    def _grad(self, names):
+        """Gradient tensor of the first of ``names`` (a parameter and those fused behind it: one launch writes them all), without side
+        effects.  None when the plan has no parameter gradients or every one of them is frozen: the emitters then skip the launch (a
+        fused launch with one trainable member still runs and writes the frozen members' segments too -- ``FlatAdamWEMA.step`` zeroes
+        those before the norm)."""
+        names = _names(names)
+        if not self.param_grads or all(n in self.frozen for n in names):
             return None
-        names = (name,) + tuple(span)
-        if all(n in self.frozen for n in names):
-            return None
-        for n in names:
-            if n not in self.frozen:
-                self.grad_ready[n] = len(self.bwd_ops)
-        return self.grads[name]
+        return self.grads[names[0]]
 
-    def _G2(self, wname, bname):
-        """(weight, bias) gradient tensors of a normalisation layer: both, or neither when both are frozen (one launch writes the two;
-        a frozen member of a half-frozen pair is written too and zeroed by ``FlatAdamWEMA.step``)."""
-        if not self.param_grads or (wname in self.frozen and bname in self.frozen):
-            return None, None
-        for n in (wname, bname):
+    def _mark_ready(self, names, at=None):
+        """The op emitted last (or the op at ``at``) is the last writer of these parameters' gradients -- the schedule the overlapped
+        data-parallel all-reduce hands its buckets over on.  Every emitter that writes a parameter gradient ends with this call."""
+        at = len(self.bwd_ops) - 1 if at is None else at
+        for n in _names(names):
             if n not in self.frozen:
-                self.grad_ready[n] = len(self.bwd_ops)
-        return self.grads[wname], self.grads[bname]
+                self.grad_ready[n] = at
 
-    def _bias_grad(self, dy, total, valid=None, per_sample=None, per_stride=None):
+    def _bias_grad(self, dy, name, valid=None, per_sample=None, per_stride=None):
+        """Gradient of the bias ``name`` (or the fused biases: a tuple of names) = the channel sums of ``dy``."""
         if not self.param_grads:
             return
+        total = self._grad(name)
         if total is None:                       # a frozen bias
             if per_sample is None or not self._temb_trains:
                 return
@@ -271,48 +281,38 @@ class UNetTrainPlan(UNetPlan):
         fused = self._fused_sums.get(id(dy))
         if fused is not None:
             # the GroupNorm backward that stored the final value of this gradient also left its per-split channel sums
-            ws, splits = fused[0], fused[1]
             # (round 6) sums in a workspace no other launch reuses, no per-sample consumer: the fold may run on the second stream with the slab folds
-            side = per_sample is None and len(fused) > 2 and fused[2]
+            side = per_sample is None and fused.own_workspace
             if side:
                 out = self._tmp((B, ch), "chsum_side", torch.float32)
             a = L.ChannelSumArgs(dtype=self.code, B=B, HW=h * w, C=ch, x=None, out=out.data_ptr(), out_stride=per_stride or ch,
-                                 accumulate=0, total=total.data_ptr(), total_valid=valid or ch, workspace=ws.data_ptr(),
-                                 splits=splits)
-            self._b(self.lib.pd_channel_sum, a, "channel_sum_fused", 0.0, B * splits * ch * 4.0)
-            self.bwd_ops[-1].side = bool(side)
-            return
-        splits = max(1, min(64, (h * w) // 64))
-        ws = self._tmp((B * splits * ch,), "chsum_ws", torch.float32)
-        a = L.ChannelSumArgs(dtype=self.code, B=B, HW=h * w, C=ch, x=dy.data_ptr(), out=out.data_ptr(),
-                             out_stride=per_stride or ch, accumulate=0, total=total.data_ptr(), total_valid=valid or ch,
-                             workspace=ws.data_ptr(), splits=splits)
-        self._b(self.lib.pd_channel_sum, a, "channel_sum", 0.0, dy.numel() * self._esz())
+                                 accumulate=0, total=total.data_ptr(), total_valid=valid or ch, workspace=fused.sums.data_ptr(),
+                                 splits=fused.splits)
+            self._emit(self.lib.pd_channel_sum, a, "channel_sum_fused", 0.0, B * fused.splits * ch * 4.0).side = bool(side)
+        else:
+            splits = max(1, min(64, (h * w) // 64))
+            ws = self._tmp((B * splits * ch,), "chsum_ws", torch.float32)
+            a = L.ChannelSumArgs(dtype=self.code, B=B, HW=h * w, C=ch, x=dy.data_ptr(), out=out.data_ptr(),
+                                 out_stride=per_stride or ch, accumulate=0, total=total.data_ptr(), total_valid=valid or ch,
+                                 workspace=ws.data_ptr(), splits=splits)
+            self._emit(self.lib.pd_channel_sum, a, "channel_sum", 0.0, dy.numel() * self._esz())
+        self._mark_ready(name)        # (a frozen bias whose sums only feed the time-embedding chain marks nothing)
 
-    def _wgrad(self, x0, x1, gn, silu, dy, dw, *, ksize=3, stride=1, pad=1, upsample=0, cout_valid=0, cin_valid=0, phase=0):
-        """Weight gradient of a convolution (``pd_conv_wgrad``); plain Linear layers (1x1, one dense source, no fused GroupNorm)
-        go through the token-reduction GEMM ``pd_token_wgrad``."""
-        if not self.param_grads or dw is None:          # (dw None: a frozen weight)
+    def _wgrad(self, x0, x1, gn, silu, dy, name, *, ksize=3, stride=1, pad=1, upsample=0, cout_valid=0, cin_valid=0, phases=False):
+        """Gradient of the convolution weight ``name`` (or the fused weights: a tuple of names) through ``pd_conv_wgrad``; plain Linear
+        layers (1x1, one dense source, no fused GroupNorm) go through the token-reduction GEMM ``pd_token_wgrad``.  ``phases``: an
+        upsampler's weight gradient as its four sub-pixel phases, each adding its 2x2 tap gradients to the 3x3 taps they sum (4 / 9 of the
+        FLOPs).  The gradient is final after the fold of the last launch."""
+        dw = self._grad(name)
+        if dw is None:          # (no parameter gradients, or a frozen weight)
             return
         if (ksize == 1 and gn is not None and x1 is None and not cout_valid and not cin_valid and x0.shape[3] % 8 == 0 and dy.shape[3] % 8 == 0
                 and not _NO_LINEAR_GRADS and not _NO_PREAPPLY_WGRAD):
             # a 1x1 layer behind a GroupNorm (the attention's fused q/k/v projection, Transformer2DModel.proj_in): pd_conv_wgrad's 1x1
             # form rebuilds the normalised input while staging and runs at ~190 TF/s; materialising it once (pd_gn_apply: one
             # bandwidth-bound pass over a tensor 1/16 .. 1/64 of the image-resolution ones) lets the token-reduction GEMM take it
-            first = len(self.bwd_ops)
-            ops, self.ops = self.ops, self.bwd_ops
-            try:
-                x0 = self._gn_apply(x0, None, gn, silu)
-            finally:
-                self.ops = ops
-            self.bwd_ops[-1].what = "gn_apply_bwd"
+            x0 = self._gn_apply(x0, None, gn, silu, what="gn_apply_bwd")
             gn, silu = None, 0
-            # `dw` came from _G(): "the NEXT emitted op writes this gradient" -- that op is now the pd_token_wgrad below, not the
-            # pd_gn_apply just emitted (the overlapped all-reduce would hand the bucket over one launch early: with two real
-            # ranks the reduced stale values then overwrite the gradient -- tests/test_gpu_two_rank_overlap.py)
-            for n, r in self.grad_ready.items():
-                if r >= first:
-                    self.grad_ready[n] = len(self.bwd_ops)
         if (ksize == 1 and gn is None and x1 is None and not cout_valid and not cin_valid and x0.shape[3] % 8 == 0 and dy.shape[3] % 8 == 0
                 and not _NO_LINEAR_GRADS):
             B, h, w, K = x0.shape
@@ -320,35 +320,33 @@ class UNetTrainPlan(UNetPlan):
             a = L.TokenWgradArgs(dtype=self.code, M=M, K=K, N=N, x=x0.data_ptr(), x_stride=K, dy=dy.data_ptr(), dy_stride=N,
                                  dw=dw.data_ptr(), accumulate=1)
             self._emit_wgrad(self.lib.pd_token_wgrad, a, "wgrad_linear", 2.0 * M * K * N, (M * (K + N)) * self._esz() + K * N * 4.0, self._twgrad_args)
+            self._mark_ready(name)
             return
         B, hin, win, c0 = x0.shape
         c1 = x1.shape[3] if x1 is not None else 0
         _, hout, wout, cout = dy.shape
-        if phase:          # sub-pixel phase of an upsampler (pd_wgrad_args.phase): dy is the gradient of the UPSAMPLED output, the grid is the low-resolution one
+        if phases:         # (pd_wgrad_args.phase): dy is the gradient of the UPSAMPLED output, the grid is the low-resolution one
             hout, wout, ksize, pad = hin, win, 2, 0
-        a = L.WgradArgs(dtype=self.code, B=B, Hin=hin, Win=win, Hout=hout, Wout=wout, C0=c0, C1=c1, Cout=cout, ksize=ksize,
-                        stride=stride, pad=pad, upsample=upsample, silu=silu, x0=x0.data_ptr(), x1=L.ptr(x1),
-                        scale=L.ptr(gn[0]) if gn else None, shift=L.ptr(gn[1]) if gn else None, dy=dy.data_ptr(),
-                        dw=dw.data_ptr(), Cout_valid=cout_valid, Cin_valid=cin_valid, accumulate=1, phase=phase)
-        flops = 2.0 * B * hout * wout * cout * (c0 + c1) * ksize * ksize
-        nbytes = (x0.numel() + (x1.numel() if x1 is not None else 0) + dy.numel()) * self._esz() + dw.numel() * 4
-        self._emit_wgrad(self.lib.pd_conv_wgrad, a, f"wgrad{ksize}x{ksize}", flops, nbytes, self._wgrad_args)
+        for phase in (1, 2, 3, 4) if phases else (0,):
+            a = L.WgradArgs(dtype=self.code, B=B, Hin=hin, Win=win, Hout=hout, Wout=wout, C0=c0, C1=c1, Cout=cout, ksize=ksize,
+                            stride=stride, pad=pad, upsample=upsample, silu=silu, x0=x0.data_ptr(), x1=L.ptr(x1),
+                            scale=L.ptr(gn[0]) if gn else None, shift=L.ptr(gn[1]) if gn else None, dy=dy.data_ptr(),
+                            dw=dw.data_ptr(), Cout_valid=cout_valid, Cin_valid=cin_valid, accumulate=1, phase=phase)
+            flops = 2.0 * B * hout * wout * cout * (c0 + c1) * ksize * ksize
+            nbytes = (x0.numel() + (x1.numel() if x1 is not None else 0) + dy.numel()) * self._esz() + dw.numel() * 4
+            self._emit_wgrad(self.lib.pd_conv_wgrad, a, f"wgrad{ksize}x{ksize}", flops, nbytes, self._wgrad_args)
+        self._mark_ready(name)
 
     def _emit_wgrad(self, fn, a, what, flops, nbytes, arglist):
         """One weight-gradient launch as two ops: stage 1 (the GEMM) in the main sequence and stage 2 (the fold of its slab into the gradient)
-        flagged ``side``, which :meth:`backward` runs on the plan's second stream; the gradient is final after the fold."""
+        flagged ``side``, which :meth:`backward` runs on the plan's second stream."""
         a.stage = 1
         a2 = type(a)()
         C.memmove(C.byref(a2), C.byref(a), C.sizeof(a))
         a2.stage = 2
         arglist.append((a, a2))
-        self._b(fn, a, what, flops, nbytes)
-        main = len(self.bwd_ops) - 1
-        self._b(fn, a2, what + "_fold", 0.0, 0.0)
-        self.bwd_ops[-1].side = True
-        for n, r in self.grad_ready.items():        # "the op at `main` writes this gradient" -> its fold does
-            if r == main:
-                self.grad_ready[n] = main + 1
+        self._emit(fn, a, what, flops, nbytes)
+        self._emit(fn, a2, what + "_fold", 0.0, 0.0).side = True
 
     def _dgrad(self, dy, wpk, cout, *, ksize=3, zero_stuff=False, into=None, tag="dz"):
         """Input gradient of a convolution: ``pd_conv`` over dy with the transposed/flipped weights (1x1: the GEMM kernel
@@ -362,17 +360,12 @@ class UNetTrainPlan(UNetPlan):
             self._drop_fused_sums(into[0])
         else:
             y, res = self._tmp((B, ho, wo, cout), tag), None
-        ops, self.ops = self.ops, self.bwd_ops
-        try:
-            if ksize == 1 and not zero_stuff and cin % 32 == 0 and cout % 8 == 0 and not _NO_LINEAR_GRADS:
-                self._linear(dy, wpk, self._zero_bias, cout, residual=res, y=y, what="dgrad_linear")
-            else:
-                # zero_stuff: True / 2 = samples at the even positions (stride-2 pad-1 forward), 3 = at the odd ones (pad-0 forward)
-                self._conv(dy, None, wpk, self._zero_bias, cout, ksize=ksize, pad=ksize // 2,
-                           upsample=(2 if zero_stuff is True else int(zero_stuff)) if zero_stuff else 0, residual=res, y=y, stats=False)
-                self.bwd_ops[-1].what = f"dgrad{ksize}x{ksize}"
-        finally:
-            self.ops = ops
+        if ksize == 1 and not zero_stuff and cin % 32 == 0 and cout % 8 == 0 and not _NO_LINEAR_GRADS:
+            self._linear(dy, wpk, self._zero_bias, cout, residual=res, y=y, what="dgrad_linear")
+        else:
+            # zero_stuff: True / 2 = samples at the even positions (stride-2 pad-1 forward), 3 = at the odd ones (pad-0 forward)
+            self._conv(dy, None, wpk, self._zero_bias, cout, ksize=ksize, pad=ksize // 2, residual=res, y=y, stats=False,
+                       upsample=(2 if zero_stuff is True else int(zero_stuff)) if zero_stuff else 0, what=f"dgrad{ksize}x{ksize}")
         return y
 
     def _gn_bwd(self, gn, dz, silu, *, combined=False, res=None, wname=None, mod_off=None):
@@ -387,7 +380,10 @@ class UNetTrainPlan(UNetPlan):
         splits = max(1, min(64, (h * w) // 64, -(-1024 // B)))
         partial = self._tmp((B * splits * (c0 + c1) * 2,), "gnpart", torch.float64)
         coef = self._tmp((B, self.groups, 2), "gncoef", torch.float32)
-        dgam, dbet = self._G2(wname + ".weight", wname + ".bias")
+        # weight and bias gradients come out of one launch: both, or neither when both are frozen (a frozen member of a half-frozen
+        # pair is written too and zeroed by ``FlatAdamWEMA.step``)
+        affine = (wname + ".weight", wname + ".bias")
+        dgam, dbet = self._grad(affine), self._grad(affine[::-1])
         a = L.GnBwdArgs(dtype=self.code, B=B, HW=h * w, C0=c0, C1=c1, groups=self.groups, silu=silu, x0=x0.data_ptr(),
                         x1=L.ptr(x1), dz0=dz.data_ptr(), dz1=None, mean=s.mean.data_ptr(), rstd=s.rstd.data_ptr(),
                         gamma=s.gamma.data_ptr(), beta=s.beta.data_ptr(), partial=partial.data_ptr(), splits=splits,
@@ -414,9 +410,11 @@ class UNetTrainPlan(UNetPlan):
             self.bufs.append(st)
             setattr(a, fld, st.data_ptr())
             self._sum_owner[id(src)] = (a, fld)
-            self._fused_sums[id(gb[0])] = (st, splits, True)       # (`st` belongs to this launch alone)
+            self._fused_sums[id(gb[0])] = _FusedSums(st, splits, True)       # (`st` belongs to this launch alone)
         n = B * h * w * (c0 + c1)
-        self._b(self.lib.pd_gn_silu_bwd, a, "gn_silu_bwd", 0.0, n * self._esz() * (5 + (1 if res is not None else 0)))
+        self._emit(self.lib.pd_gn_silu_bwd, a, "gn_silu_bwd", 0.0, n * self._esz() * (5 + (1 if res is not None else 0)))
+        if dgam is not None:
+            self._mark_ready(affine)
 
     # ---- backward plan ---------------------------------------------------------------------------
     def _zero_bias_len(self):
@@ -424,6 +422,7 @@ class UNetTrainPlan(UNetPlan):
 
     def _build_backward(self):
         w = self.w
+        self._sink = self.bwd_ops       # the forward is laid out: every emitter (the forward's `_conv` / `_linear` / `_gn_apply` included) now appends here
         self._zero_bias = torch.zeros(self._zero_bias_len(), dtype=torch.float32, device=self.device)
         self.dproj = self._f32(self.B, w.proj_dim)
         self._twgrad_args = []
@@ -444,7 +443,6 @@ class UNetTrainPlan(UNetPlan):
     def _bwd_record(self, rec):
         """Emit the backward launches of one forward tape record."""
         m, w, tw, c = self.m, self.w, self.tw, self.m.config
-        G = self._G
         B, H, W = self.B, self.H, self.W
         boc0 = c.block_out_channels[0]
         k = rec.kind
@@ -453,17 +451,15 @@ class UNetTrainPlan(UNetPlan):
             a = L.NchwToNhwcArgs(dtype=self.code, B=B, C=c.out_channels, HW=H * W, Cpad=w.conv_out_pad, x=None,
                                  out=dy.data_ptr())
             self._dout_args = a
-            self._b(self.lib.pd_nchw_to_nhwc, a, "nchw_to_nhwc", 0.0, B * H * W * c.out_channels * 4.0)
-            self._bias_grad(dy, G("conv_out.bias"), valid=c.out_channels)
-            self._wgrad(rec.x, None, rec.gn, 1, dy, G("conv_out.weight"), cout_valid=c.out_channels)
+            self._emit(self.lib.pd_nchw_to_nhwc, a, "nchw_to_nhwc", 0.0, B * H * W * c.out_channels * 4.0)
+            self._bias_grad(dy, "conv_out.bias", valid=c.out_channels)
+            self._wgrad(rec.x, None, rec.gn, 1, dy, "conv_out.weight", cout_valid=c.out_channels)
             dz = self._dgrad(dy, tw.conv_out_d, boc0)
             self._gn_bwd(rec.gn, dz, 1, wname="conv_norm_out")
         elif k == "resnet":
             self._resnet_bwd(rec)
-        elif k == "attn":
+        elif k in ("attn", "attn_nhwc"):
             self._attn_bwd(rec)
-        elif k == "attn_nhwc":
-            self._attn_nhwc_bwd(rec)
         elif k == "down":
             # Downsample2D(padding=0) pads (0, 1, 0, 1) and convolves without padding (orig_google_ddpm_model_denoiser.json):
             # y[o] = sum_k w[k] x[2 o + k], so its input gradient is the pad-1 convolution over dY zero-stuffed at the ODD positions
@@ -471,24 +467,17 @@ class UNetTrainPlan(UNetPlan):
             if pad not in (0, 1):
                 raise NotImplementedError(f"training: Downsample2D with padding {pad}")
             dout = self._g(rec.out)[0]
-            self._bias_grad(dout, G(rec.name + ".conv.bias"))
-            self._wgrad(rec.x, None, None, 0, dout, G(rec.name + ".conv.weight"), stride=2, pad=pad)
+            self._bias_grad(dout, rec.name + ".conv.bias")
+            self._wgrad(rec.x, None, None, 0, dout, rec.name + ".conv.weight", stride=2, pad=pad)
             self._dgrad(dout, tw.samplers[rec.name].wd, rec.x.shape[3], zero_stuff=(2 if pad == 1 else 3), into=self._g(rec.x))
         elif k == "up":
             dout = self._g(rec.out)[0]
-            self._bias_grad(dout, G(rec.name + ".conv.bias"))
+            self._bias_grad(dout, rec.name + ".conv.bias")
             gx = self._g(rec.x)
             _, h, ww, ch = rec.x.shape
             wd4 = getattr(tw.samplers[rec.name], "wd4", None)
             sub = wd4 is not None and self._subpixel_up_ok(rec.x)
-            if sub:        # the weight gradient through the four phases as well: each adds its 2x2 tap gradients to the 3x3 taps they sum (4 / 9 of the FLOPs)
-                gw = G(rec.name + ".conv.weight")
-                for ph in range(4):
-                    self._wgrad(rec.x, None, None, 0, dout, gw, phase=1 + ph)
-                if gw is not None:      # the gradient is final after the LAST of the four launches (G() recorded the first: the overlapped all-reduce hands its bucket over there)
-                    self.grad_ready[rec.name + ".conv.weight"] = len(self.bwd_ops) - 1
-            else:
-                self._wgrad(rec.x, None, None, 0, dout, G(rec.name + ".conv.weight"), upsample=1)
+            self._wgrad(rec.x, None, None, 0, dout, rec.name + ".conv.weight", upsample=0 if sub else 1, phases=sub)
             if sub:
                 # d x = sum over the four phases of a 2x2 convolution over that phase's pixels of d out (transposed, flipped phase kernels):
                 # each launch accumulates into the gradient of the low-resolution tensor through `residual`
@@ -498,8 +487,8 @@ class UNetTrainPlan(UNetPlan):
                                    w_packed=wd4[ph].data_ptr(), bias=self._zero_bias.data_ptr(), temb=None, temb_stride=self.w.proj_dim,
                                    residual=(gx[0].data_ptr() if (gx[1] or ph > 0) else None), y=gx[0].data_ptr(), stats_out=None, im2col3=0,
                                    tail_x0=None, tail_x1=None, tail_C0=0, tail_C1=0, phase=1 + ph, phase_in=1)
-                    self._b(self.lib.pd_conv, a, "dgrad3x3", 2.0 * B * 4 * h * ww * ch * ch * 9 / 4.0,
-                            (B * 4 * h * ww * ch / 4.0 + 2.0 * B * h * ww * ch) * self._esz() + ch * ch * 4 * self._esz())
+                    self._emit(self.lib.pd_conv, a, "dgrad3x3", 2.0 * B * 4 * h * ww * ch * ch * 9 / 4.0,
+                               (B * 4 * h * ww * ch / 4.0 + 2.0 * B * h * ww * ch) * self._esz() + ch * ch * 4 * self._esz())
                 gx[1] = True
                 self._drop_fused_sums(gx[0])
             else:
@@ -508,52 +497,51 @@ class UNetTrainPlan(UNetPlan):
                                   accumulate=int(gx[1]))
                 gx[1] = True
                 self._drop_fused_sums(gx[0])
-                self._b(self.lib.pd_pool2x2_sum, a, "pool2x2", 0.0, du.numel() * self._esz() * 1.25)
+                self._emit(self.lib.pd_pool2x2_sum, a, "pool2x2", 0.0, du.numel() * self._esz() * 1.25)
         elif k == "conv_in":
             dout = self._g(rec.out)[0]
             if self.input_grad:
-                ops, self.ops = self.ops, self.bwd_ops
-                try:
-                    self._conv(dout, None, tw.conv_in_d, self._zero_bias, c.in_channels, out_mode=L.PD_OUT_NCHW_F32,
-                               cout_pad=32, y=self.dsample, stats=False)
-                finally:
-                    self.ops = ops
-                self.bwd_ops[-1].what = "dgrad3x3"
-                if getattr(self, "_centered", None) is not None:      # d (2 x - 1) / d x = 2 (cond_unet_2d.py:272-273)
+                self._conv(dout, None, tw.conv_in_d, self._zero_bias, c.in_channels, out_mode=L.PD_OUT_NCHW_F32,
+                           cout_pad=32, y=self.dsample, stats=False, what="dgrad3x3")
+                if self._centered is not None:      # d (2 x - 1) / d x = 2 (cond_unet_2d.py:272-273)
                     ones, two, _ = self._center_const
                     zero = torch.zeros_like(two)
                     self.bufs.append(zero)
                     sa = L.AddNoiseArgs(numel=self.dsample.numel(), per_sample=self.dsample[0].numel(), velocity=0, x=self.dsample.data_ptr(),
                                         noise=ones.data_ptr(), sa=two.data_ptr(), sb=zero.data_ptr(), out=self.dsample.data_ptr())
-                    self._b(self.lib.pd_add_noise, sa, "center_bwd", 0.0, 2.0 * self.dsample.numel() * 4)
+                    self._emit(self.lib.pd_add_noise, sa, "center_bwd", 0.0, 2.0 * self.dsample.numel() * 4)
             if not self.param_grads:
                 return
-            self._bias_grad(dout, G("conv_in.bias"))
-            if "conv_in.weight" in self.frozen:
-                return
-            cols = self._tmp((B, H, W, 32), "im2col")
-            a = L.Im2col3Args(dtype=self.code, B=B, H=H, W=W, C=c.in_channels, x=None, out=cols.data_ptr())
-            self._sample_ptr_args.append(a)
-            self._b(self.lib.pd_im2col3, a, "im2col3", 0.0, cols.numel() * self._esz())
-            self._wgrad(cols, None, None, 0, dout, G("conv_in.weight"), ksize=1, pad=0, cin_valid=c.in_channels * 9)
+            self._im2col_wgrad(dout, "conv_in")
         else:
             raise NotImplementedError(f"backward of tape record {k!r}")
 
+    def _im2col_wgrad(self, dout, name):
+        """Bias and weight gradient of the im2col ``conv_in`` (3 input channels as one 1x1 layer over 27 of 32 columns)."""
+        B, H, W, cin = self.B, self.H, self.W, self.m.config.in_channels
+        self._bias_grad(dout, name + ".bias")
+        if name + ".weight" in self.frozen:
+            return
+        cols = self._tmp((B, H, W, 32), "im2col")
+        a = L.Im2col3Args(dtype=self.code, B=B, H=H, W=W, C=cin, x=None, out=cols.data_ptr())
+        self._sample_ptr_args.append(a)
+        self._emit(self.lib.pd_im2col3, a, "im2col3", 0.0, cols.numel() * self._esz())
+        self._wgrad(cols, None, None, 0, dout, name + ".weight", ksize=1, pad=0, cin_valid=cin * 9)
+
     def _resnet_bwd(self, rec):
         e, te = rec.e, self.tw.resnets[rec.name]
-        G = self._G
         n = rec.name
         x0, x1 = rec.x0, rec.x1
         cin = e.cin
         dout = self._g(rec.out)[0]
-        self._bias_grad(dout, G(n + ".conv2.bias"))
+        self._bias_grad(dout, n + ".conv2.bias")
         if rec.z2 is not None:
-            self._wgrad(rec.z2, None, None, 0, dout, G(n + ".conv2.weight"))
+            self._wgrad(rec.z2, None, None, 0, dout, n + ".conv2.weight")
         else:
-            self._wgrad(rec.h1, None, rec.gn2, 1, dout, G(n + ".conv2.weight"))
+            self._wgrad(rec.h1, None, rec.gn2, 1, dout, n + ".conv2.weight")
         if e.fused_shortcut:
-            self._bias_grad(dout, G(n + ".conv_shortcut.bias"))
-            self._wgrad(x0, x1, None, 0, dout, G(n + ".conv_shortcut.weight"), ksize=1, pad=0)
+            self._bias_grad(dout, n + ".conv_shortcut.bias")
+            self._wgrad(x0, x1, None, 0, dout, n + ".conv_shortcut.weight", ksize=1, pad=0)
             res = self._dgrad(dout, te.wsd, cin, ksize=1, tag="dshort")
         else:
             res = dout
@@ -564,29 +552,39 @@ class UNetTrainPlan(UNetPlan):
         self._gn_bwd(rec.gn2, dz2, 1, wname=n + ".norm2", mod_off=e.temb_off if ss else None)
         dh1 = self._g(rec.h1)[0]
         if ss or e.temb_off is None:        # (None: a ResNet block without a time embedding -- the VAE's)
-            self._bias_grad(dh1, G(n + ".conv1.bias"))
+            self._bias_grad(dh1, n + ".conv1.bias")
         else:
             # d time_emb_proj output [n][co] = sum over pixels of d h1 (the projection is broadcast over the pixels)
             per = self.dproj[:, e.temb_off:]
-            self._bias_grad(dh1, G(n + ".conv1.bias"), per_sample=per, per_stride=self.w.proj_dim)
+            self._bias_grad(dh1, n + ".conv1.bias", per_sample=per, per_stride=self.w.proj_dim)
         if rec.z1 is not None:
-            self._wgrad(rec.z1, None, None, 0, dh1, G(n + ".conv1.weight"))
+            self._wgrad(rec.z1, None, None, 0, dh1, n + ".conv1.weight")
         else:
-            self._wgrad(x0, x1, rec.gn1, 1, dh1, G(n + ".conv1.weight"))
+            self._wgrad(x0, x1, rec.gn1, 1, dh1, n + ".conv1.weight")
         dz1 = self._dgrad(dh1, te.w1d, cin, tag="dz1")
         self._gn_bwd(rec.gn1, dz1, 1, combined=True, res=res, wname=n + ".norm1")
 
     def _attn_bwd(self, rec):
+        """Backward of ``UNetPlan._attn`` / ``_attn_nhwc``: the out projection's gradients, the attention itself (by the layout its
+        forward left q | k | v in), then the fused q | k | v projection's gradients and the GroupNorm backward."""
         e, te, n = rec.e, self.tw.attns[rec.name], rec.name
-        G = self._G
         B, h, w, ch = rec.x.shape
-        N = h * w
         dout = self._g(rec.out)[0]
-        self._bias_grad(dout, G(n + ".to_out.0.bias"))
-        self._wgrad(rec.o, None, None, 0, dout, G(n + ".to_out.0.weight"), ksize=1, pad=0)
+        self._bias_grad(dout, n + ".to_out.0.bias")
+        self._wgrad(rec.o, None, None, 0, dout, n + ".to_out.0.weight", ksize=1, pad=0)
         do = self._dgrad(dout, te.wod, ch, ksize=1, tag="do")
         dqkv = self._tmp((B, h, w, 3 * ch), "dqkv")
-        delta = self._tmp((B, e.heads, N), "delta", torch.float32)
+        delta = self._tmp((B, e.heads, h * w), "delta", torch.float32)
+        (self._attn_d8_core if rec.kind == "attn" else self._attn_nhwc_core)(rec, do, dqkv, delta)
+        self._bias_grad(dqkv, [f"{n}.{x}.bias" for x in ("to_q", "to_k", "to_v")])                       # [dq | dk | dv] biases are adjacent
+        self._wgrad(rec.x, None, rec.gn, 0, dqkv, [f"{n}.{x}.weight" for x in ("to_q", "to_k", "to_v")], ksize=1, pad=0)
+        dz = self._dgrad(dqkv, te.wqkvd, ch, ksize=1, tag="dzattn")
+        self._gn_bwd(rec.gn, dz, 0, res=dout, wname=n + ".group_norm")
+
+    def _attn_d8_core(self, rec, do, dqkv, delta):
+        e = rec.e
+        B, h, w, ch = rec.x.shape
+        N = h * w
         a = L.AttnBwdArgs(dtype=self.code, B=B, heads=e.heads, N=N, q=rec.qkv[0].data_ptr(), k=rec.qkv[1].data_ptr(),
                           v=rec.qkv[2].data_ptr(), o=rec.o.data_ptr(), dout=do.data_ptr(), lse=rec.lse.data_ptr(),
                           delta=delta.data_ptr(), dqkv=dqkv.data_ptr())
@@ -594,95 +592,79 @@ class UNetTrainPlan(UNetPlan):
         # layers of the step share.  OPT-IN (PD_ATTN_BWD_FUSED=1): 4-5 % faster than the two kernels as an op (1.21 vs 1.28 ms per
         # configs[1] layer) and neutral-to-slower on the whole step (2 324 vs 2 339 images/s, 4 alternating rounds:
         # profiles/r5_ab_attn_bwd_one_pass.log) -- 200 registers hold it at 2 waves per SIMD, where matrix and vector work do not overlap
-        need = int(self.lib.pd_attn_d8_bwd_workspace(C.byref(a))) if __import__("os").environ.get("PD_ATTN_BWD_FUSED", "0") == "1" else 0
+        need = int(self.lib.pd_attn_d8_bwd_workspace(C.byref(a))) if os.environ.get("PD_ATTN_BWD_FUSED", "0") == "1" else 0
         if need > 0:
             slab = self._tmp((need // 4,), "attn_dq_slab", torch.float32)
             a.slab, a.slab_bytes = slab.data_ptr(), need
-        self._b(self.lib.pd_attn_d8_bwd, a, "attn_d8_bwd", 10.0 * B * e.heads * N * N * 8, 8.0 * B * N * ch * self._esz())
-        self._bias_grad(dqkv, G(n + ".to_q.bias", (n + ".to_k.bias", n + ".to_v.bias")))                       # [dq | dk | dv] biases are adjacent
-        self._wgrad(rec.x, None, rec.gn, 0, dqkv, G(n + ".to_q.weight", (n + ".to_k.weight", n + ".to_v.weight")), ksize=1, pad=0)
-        dz = self._dgrad(dqkv, te.wqkvd, ch, ksize=1, tag="dzattn")
-        self._gn_bwd(rec.gn, dz, 0, res=dout, wname=n + ".group_norm")
+        self._emit(self.lib.pd_attn_d8_bwd, a, "attn_d8_bwd", 10.0 * B * e.heads * N * N * 8, 8.0 * B * N * ch * self._esz())
 
-    def _attn_nhwc_bwd(self, rec):
-        """Backward of ``UNetPlan._attn_nhwc`` (head_dim 16 / 32 / 64, or one wide head of 128 / 256 / 512 channels: ``attention_head_dim``
-        null of orig_google_ddpm_model_denoiser.json): q | k | v live NHWC in one [B][N][3C] tensor, so the attention gradient
-        is written straight into the fused projection's output gradient [dq | dk | dv]."""
-        e, te, n = rec.e, self.tw.attns[rec.name], rec.name
-        G = self._G
+    def _attn_nhwc_core(self, rec, do, dqkv, delta):
+        """Head_dim 16 / 32 / 64, or one wide head of 128 / 256 / 512 channels (``attention_head_dim`` null of
+        orig_google_ddpm_model_denoiser.json): q | k | v live NHWC in one [B][N][3C] tensor, so the attention gradient is written straight
+        into the fused projection's output gradient [dq | dk | dv]."""
+        e, d = rec.e, rec.d
         B, h, w, ch = rec.x.shape
-        N, esz, d = h * w, self._esz(), rec.d
-        dout = self._g(rec.out)[0]
-        self._bias_grad(dout, G(n + ".to_out.0.bias"))
-        self._wgrad(rec.o, None, None, 0, dout, G(n + ".to_out.0.weight"), ksize=1, pad=0)
-        do = self._dgrad(dout, te.wod, ch, ksize=1, tag="do")
-        dqkv = self._tmp((B, h, w, 3 * ch), "dqkv")
-        delta = self._tmp((B, e.heads, N), "delta", torch.float32)
+        N, esz = h * w, self._esz()
         p, dp = rec.qkv.data_ptr(), dqkv.data_ptr()
         common = dict(dtype=self.code, B=B, heads=e.heads, Nq=N, Nkv=N, q=p, q_stride=3 * ch, k=p + ch * esz, v=p + 2 * ch * esz,
                       kv_stride=3 * ch, o=rec.o.data_ptr(), dout=do.data_ptr(), o_stride=ch, lse=rec.lse.data_ptr(),
                       delta=delta.data_ptr(), dq=dp, dq_stride=3 * ch, dk=dp + ch * esz, dv=dp + 2 * ch * esz, dkv_stride=3 * ch)
         if d == 64:
-            self._b(self.lib.pd_attn_d64_bwd, L.AttnD64BwdArgs(**common), "attn_d64_bwd", 10.0 * B * N * N * ch, 8.0 * B * N * ch * esz)
+            fn, a, what = self.lib.pd_attn_d64_bwd, L.AttnD64BwdArgs(**common), "attn_d64_bwd"
         elif d in (16, 32):
-            self._b(self.lib.pd_attn_hd_bwd, L.AttnHdBwdArgs(D=d, scale=float(d) ** -0.5, **common), "attn_hd_bwd",
-                    10.0 * B * N * N * ch, 8.0 * B * N * ch * esz)
+            fn, a, what = self.lib.pd_attn_hd_bwd, L.AttnHdBwdArgs(D=d, scale=float(d) ** -0.5, **common), "attn_hd_bwd"
         else:
-            self._b(self.lib.pd_attn_wide_bwd, L.AttnWideBwdArgs(D=d, scale=float(d) ** -0.5, **common), "attn_wide_bwd",
-                    10.0 * B * N * N * ch, 8.0 * B * N * ch * esz)
-        self._bias_grad(dqkv, G(n + ".to_q.bias", (n + ".to_k.bias", n + ".to_v.bias")))
-        self._wgrad(rec.x, None, rec.gn, 0, dqkv, G(n + ".to_q.weight", (n + ".to_k.weight", n + ".to_v.weight")), ksize=1, pad=0)
-        dz = self._dgrad(dqkv, te.wqkvd, ch, ksize=1, tag="dzattn")
-        self._gn_bwd(rec.gn, dz, 0, res=dout, wname=n + ".group_norm")
+            fn, a, what = self.lib.pd_attn_wide_bwd, L.AttnWideBwdArgs(D=d, scale=float(d) ** -0.5, **common), "attn_wide_bwd"
+        self._emit(fn, a, what, 10.0 * B * N * N * ch, 8.0 * B * N * ch * esz)
+
+    def _linear_wgrad(self, wnames, bnames, **shape_and_inputs):
+        """Weight + bias gradient of one fp32 Linear layer of the time-embedding chain (``pd_linear_wgrad``; the projections of all
+        ResNet blocks are ONE stacked layer).  The chain's launches write a layer's weight and bias together: a partially frozen chain
+        runs whole, ``FlatAdamWEMA.step`` zeroes the frozen members' gradient segments."""
+        wnames, bnames = _names(wnames), _names(bnames)
+        a = L.LinearWgradArgs(rows=self.B, dw=self.grads[wnames[0]].data_ptr(), db=self.grads[bnames[0]].data_ptr(), **shape_and_inputs)
+        self._emit(self.lib.pd_linear_wgrad, a, "linear_wgrad")
+        self._mark_ready(wnames + bnames)
+
+    def _linear_dgrad(self, wname, **shape_and_inputs):
+        a = L.LinearDgradArgs(rows=self.B, w=self.params[wname].data_ptr(), **shape_and_inputs)
+        self._emit(self.lib.pd_linear_dgrad, a, "linear_dgrad")
 
     def _temb_bwd(self):
         if not self._temb_trains:
             return
-        m, w, P = self.m, self.w, self.params
-        # (this chain's launches write weight and bias of a layer together and the projections of all ResNet blocks as one stacked
-        # matrix: a partially frozen chain runs whole, FlatAdamWEMA.step zeroes the frozen members' gradient segments)
-        def G(name, span=()):
-            for n in (name,) + tuple(span):
-                if n not in self.frozen:
-                    self.grad_ready[n] = len(self.bwd_ops)
-            return self.grads[name]
-        B, tdim, c0, pd = self.B, m.time_embed_dim, m.config.block_out_channels[0], w.proj_dim
+        m = self.m
+        B, tdim, c0, pd = self.B, m.time_embed_dim, m.config.block_out_channels[0], self.w.proj_dim
         res = [n for n, mod in m.named_modules() if isinstance(mod, _Resnet)]
-        first = res[0]
-        lib = self.lib
         demb, dz1 = self._f32(B, tdim), self._f32(B, tdim)
-        self._b(lib.pd_linear_wgrad, L.LinearWgradArgs(rows=B, in_dim=tdim, out_dim=pd, x_silu=1, dy=self.dproj.data_ptr(),
-                x=self.t_emb.data_ptr(),
-                dw=G(first + ".time_emb_proj.weight", [r + ".time_emb_proj.weight" for r in res[1:]]).data_ptr(),
-                db=G(first + ".time_emb_proj.bias", [r + ".time_emb_proj.bias" for r in res[1:]]).data_ptr()), "linear_wgrad")
-        self._b(lib.pd_linear_dgrad, L.LinearDgradArgs(rows=B, in_dim=tdim, out_dim=pd, dy=self.dproj.data_ptr(),
-                w=P[first + ".time_emb_proj.weight"].data_ptr(), pre=self.t_emb.data_ptr(), dx=demb.data_ptr()), "linear_dgrad")
+        self._linear_wgrad([r + ".time_emb_proj.weight" for r in res], [r + ".time_emb_proj.bias" for r in res],
+                           in_dim=tdim, out_dim=pd, x_silu=1, dy=self.dproj.data_ptr(), x=self.t_emb.data_ptr())
+        self._linear_dgrad(res[0] + ".time_emb_proj.weight", in_dim=tdim, out_dim=pd, dy=self.dproj.data_ptr(), pre=self.t_emb.data_ptr(),
+                           dx=demb.data_ptr())
         if getattr(getattr(m, "class_embedding", None), "weight", None) is not None and "class_embedding.weight" not in self.frozen:
+            # the class table's gradient is launched by `backward` (it needs the step's labels) in FRONT of the op emitted next, and is
+            # final after that op
             self._emb_grad_args = L.EmbeddingGradArgs(rows=B, dim=tdim, num_classes=m.class_embedding.weight.shape[0], labels=None,
-                                                      d=demb.data_ptr(), dtable=G("class_embedding.weight").data_ptr())
+                                                      d=demb.data_ptr(), dtable=self.grads["class_embedding.weight"].data_ptr())
             self._emb_grad_at = len(self.bwd_ops)
+            self._mark_ready("class_embedding.weight", at=self._emb_grad_at)
         if self._class_mlp and any(n.startswith("class_embedding.") and n not in self.frozen for n in self.grads):
             # emb = time_embedding(...) + class_embedding(time_proj(labels)): the class MLP sees the same d emb.  These three launches run
             # only on steps whose labels went through the MLP (`backward` skips the [start, end) range otherwise)
             dcz1 = self._f32(B, tdim)
             start = len(self.bwd_ops)
-            self._b(lib.pd_linear_wgrad, L.LinearWgradArgs(rows=B, in_dim=tdim, out_dim=tdim, x_silu=1, dy=demb.data_ptr(),
-                    x=self.c_z1.data_ptr(), dw=G("class_embedding.linear_2.weight").data_ptr(),
-                    db=G("class_embedding.linear_2.bias").data_ptr()), "linear_wgrad")
-            self._b(lib.pd_linear_dgrad, L.LinearDgradArgs(rows=B, in_dim=tdim, out_dim=tdim, dy=demb.data_ptr(),
-                    w=P["class_embedding.linear_2.weight"].data_ptr(), pre=self.c_z1.data_ptr(), dx=dcz1.data_ptr()), "linear_dgrad")
-            self._b(lib.pd_linear_wgrad, L.LinearWgradArgs(rows=B, in_dim=c0, out_dim=tdim, x_silu=0, dy=dcz1.data_ptr(),
-                    x=self.c_feat.data_ptr(), dw=G("class_embedding.linear_1.weight").data_ptr(),
-                    db=G("class_embedding.linear_1.bias").data_ptr()), "linear_wgrad")
+            self._time_mlp_bwd("class_embedding", demb, dcz1, self.c_z1, self.c_feat)
             self._class_mlp_ops = (start, len(self.bwd_ops))
-        self._b(lib.pd_linear_wgrad, L.LinearWgradArgs(rows=B, in_dim=tdim, out_dim=tdim, x_silu=1, dy=demb.data_ptr(),
-                x=self.t_z1.data_ptr(), dw=G("time_embedding.linear_2.weight").data_ptr(),
-                db=G("time_embedding.linear_2.bias").data_ptr()), "linear_wgrad")
-        self._b(lib.pd_linear_dgrad, L.LinearDgradArgs(rows=B, in_dim=tdim, out_dim=tdim, dy=demb.data_ptr(),
-                w=P["time_embedding.linear_2.weight"].data_ptr(), pre=self.t_z1.data_ptr(), dx=dz1.data_ptr()), "linear_dgrad")
-        self._b(lib.pd_linear_wgrad, L.LinearWgradArgs(rows=B, in_dim=c0, out_dim=tdim, x_silu=0, dy=dz1.data_ptr(),
-                x=self.t_feat.data_ptr(), dw=G("time_embedding.linear_1.weight").data_ptr(),
-                db=G("time_embedding.linear_1.bias").data_ptr()), "linear_wgrad")
+        self._time_mlp_bwd("time_embedding", demb, dz1, self.t_z1, self.t_feat)
+
+    def _time_mlp_bwd(self, name, demb, dz1, z1, feat):
+        """linear_2(silu(linear_1(feat))) of the time-embedding MLP (or the class MLP of the same shape), given d emb."""
+        tdim, c0 = self.m.time_embed_dim, self.m.config.block_out_channels[0]
+        self._linear_wgrad(name + ".linear_2.weight", name + ".linear_2.bias", in_dim=tdim, out_dim=tdim, x_silu=1, dy=demb.data_ptr(),
+                           x=z1.data_ptr())
+        self._linear_dgrad(name + ".linear_2.weight", in_dim=tdim, out_dim=tdim, dy=demb.data_ptr(), pre=z1.data_ptr(), dx=dz1.data_ptr())
+        self._linear_wgrad(name + ".linear_1.weight", name + ".linear_1.bias", in_dim=c0, out_dim=tdim, x_silu=0, dy=dz1.data_ptr(),
+                           x=feat.data_ptr())
 
     # ---- execution -------------------------------------------------------------------------------
     def backward(self, dout: torch.Tensor, stream, after_op=None):
@@ -690,9 +672,8 @@ class UNetTrainPlan(UNetPlan):
         ``after_op``: {op index: callable} run right after that op was enqueued (gradient buckets becoming final)."""
         self._dout_args.x = dout.data_ptr()
         byref, check = C.byref, L.check
-        labels = getattr(self, "_labels", None)
-        emb_at = getattr(self, "_emb_grad_at", -1)
-        skip0, skip1 = getattr(self, "_class_mlp_ops", (0, 0)) if not getattr(self, "_class_mlp_ran", False) else (0, 0)
+        labels, emb_at = self._labels, self._emb_grad_at
+        skip0, skip1 = (0, 0) if self._class_mlp_ran else self._class_mlp_ops
         side, ms, evs, join = self._side_streams(stream)
         if after_op is not None or _data_parallel():
             # data-parallel run (gradient buckets are handed to the exchange on its own stream): the folds stay on the main stream, right behind
@@ -734,7 +715,7 @@ class UNetTrainPlan(UNetPlan):
 
     def _side_streams(self, stream):
         """(second stream, the main stream as a torch object, one event per side op, a join event) -- or (None, ...) when the plan has no side op."""
-        st = getattr(self, "_side_state", None)
+        st = self._side_state
         if st is None:
             n = sum(1 for op in self.bwd_ops if op.side)
             if n == 0:
@@ -813,22 +794,30 @@ class UNetTrainer:
         ``requires_grad`` flags say (:func:`phendiff_amd.training.resolve_trainable`: the reference freezes with
         ``requires_grad_(False)`` and ``--attention_fine_tuning`` re-enables ``module.attentions``, train.py:189-220).  Frozen
         parameters get no gradient launches, no AdamW / EMA update, and stay out of the global norm and of the all-reduce buckets."""
-        from .training import DiffusionLoss, FlatAdamWEMA, broadcast_from_rank0_, resolve_trainable
+        from .training import resolve_trainable
         self.model, self.scheduler = model, scheduler
-        dev = device or model.device
-        if torch.device(dev).type != "cuda":
-            raise L.PhenDiffHipError("phendiff_amd trains on MI355X only (no CPU fallback): move the model to 'cuda'")
         order = training_param_order(model)
         flags = resolve_trainable(order, model, trainable)
+        tail = [(n, p, f) for (n, p), f in zip(order, flags) if n.startswith("class_embedding.")]
+        tail = (sum(p.numel() for _, p, _ in tail), tuple(n for n, _, _ in tail)) if tail and all(f for _, _, f in tail) else None
+        self._cond = True
+        self._init_state(order, flags, tail, lr, device, use_ema, max_grad_norm, group, adamw)
+
+    def _init_state(self, order, flags, tail, lr, device, use_ema, max_grad_norm, group, adamw):
+        """What every trainer holds beside its model: the flat optimizer over ``order`` (``flags``: what trains; ``tail``: (elements, names)
+        of the class-embedding segment with its own step count, or None), the name -> tensor views, loss, caches and the knobs callers set."""
+        from .training import DiffusionLoss, FlatAdamWEMA, LossScaler, broadcast_from_rank0_
+        model, name = self.model, type(self).__name__
+        self.device = device or model.device
+        if torch.device(self.device).type != "cuda":
+            raise L.PhenDiffHipError("phendiff_amd trains on MI355X only (no CPU fallback): move the model to 'cuda'")
         if not any(flags):
-            raise ValueError("UNetTrainer: no trainable parameter (every parameter is frozen)")
+            raise ValueError(f"{name}: no trainable parameter (every parameter is frozen)")
         self.frozen = frozenset(n for (n, _), f in zip(order, flags) if not f)
         self.opt = FlatAdamWEMA([p for _, p in order], lr, use_ema=use_ema, max_grad_norm=max_grad_norm, **adamw)
         self.opt.set_trainable(flags)
-        tail = [(n, p, f) for (n, p), f in zip(order, flags) if n.startswith("class_embedding.")]
-        if tail and all(f for _, _, f in tail):
-            self.opt.set_tail(sum(p.numel() for _, p, _ in tail), tuple(n for n, _, _ in tail))
-        self._cond = True
+        if tail is not None:
+            self.opt.set_tail(*tail)
         # DDP's wrap-time broadcast (train.py:311-326): rank 0's parameters everywhere; the EMA shadow starts from them
         broadcast_from_rank0_(self.opt.flat, group)
         if self.opt.ema is not None:
@@ -836,15 +825,18 @@ class UNetTrainer:
         self.params = {n: p.data for n, p in order}
         self.grads = {n: p.grad for n, p in order}
         model.invalidate()
-        self.loss_fn = DiffusionLoss(scheduler, dev)
+        self.loss_fn = DiffusionLoss(self.scheduler, self.device)
         # --mixed_precision fp16 (args_parser.py:381-390): fp16 activation gradients need the loss scale accelerate's GradScaler applies
         if getattr(model, "compute_dtype", None) == "fp16":
-            from .training import LossScaler
             self.opt.scaler = LossScaler()
-        self.device = dev
-        self._plans = {}
-        self._tw = None
-        self._repack = None
+        self._plans, self._tw, self._repack, self._bound_w = {}, None, None, None
+        self._bucket_key, self._comm_events = None, None
+        # set by callers (bench.py, tests, attach_sampler / use_native_comm)
+        self.sampler = None               # DeviceTrainingSampler: step_clean / step_images draw noise and timesteps on the device
+        self.native_comm = None           # phendiff_amd.comm.NativeComm: RCCL through the C ABI (pd_allreduce_bucket)
+        self.force_collectives = False    # run the exchange at world size 1 too
+        self.comm_timing = False          # events around every bucket's collective on the comm stream
+        self.skip_collectives = False     # the same step with the exchange left out (`step_ms_no_comm`)
 
     # kernel-layout weight copies: the model owns the inference set (``model._weights``), the trainer the gradient set and the
     # re-packer.  ``model.to()`` / ``.cuda()`` / ``load_state_dict()`` / ``pipeline.to()`` drop ``model._weights`` (``invalidate``)
@@ -866,7 +858,7 @@ class UNetTrainer:
         """Make the trainer's caches refer to the model's CURRENT packed weights; returns True when they had to be rebuilt
         (plans dropped, gradient-layout weights and re-packer rebuilt)."""
         m = self.model
-        if m._weights is not None and m._weights is getattr(self, "_bound_w", None):
+        if m._weights is not None and m._weights is self._bound_w:
             return False
         for n, p in m.named_parameters():
             t = self.params.get(n)
@@ -923,7 +915,7 @@ class UNetTrainer:
         computes the earlier layers' gradients -> clip + AdamW + EMA -> re-pack."""
         import torch.distributed as dist
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
-        if world == 1 and not getattr(self, "force_collectives", False):
+        if world == 1 and not self.force_collectives:
             loss, _ = self.forward_backward(noisy, timesteps, clean, noise, class_labels, class_emb)
         elif not overlap:
             from .training import allreduce_mean_ranges_
@@ -949,10 +941,9 @@ class UNetTrainer:
         return sampler
 
     def _require_sampler(self, what):
-        sampler = getattr(self, "sampler", None)
-        if sampler is None:
+        if self.sampler is None:
             raise L.PhenDiffHipError(f"{what} needs a DeviceTrainingSampler (attach_sampler)")
-        return sampler
+        return self.sampler
 
     def step_clean(self, clean, class_labels=None, class_emb=None, **step_kwargs):
         """:meth:`step` from the clean batch alone: the attached sampler draws (noise, timesteps, noisy) on the device."""
@@ -969,14 +960,13 @@ class UNetTrainer:
         B, _, H, W = noisy.shape
         plan = self.plan_for(B, H, W)
         key = (id(plan), bucket_bytes)
-        if getattr(self, "_bucket_key", None) != key:
+        if self._bucket_key != key:
             names = list(self.grads)
             last = len(plan.bwd_ops) - 1
             # buckets are cut inside each run of trainable parameters: a frozen parameter's gradient segment is not exchanged
             self._buckets, off, run = [], 0, [0, [], []]
-            frozen = getattr(self, "frozen", frozenset())
             for n in names + [None]:
-                if n is None or n in frozen:
+                if n is None or n in self.frozen:
                     if run[1]:
                         self._buckets += [(run[0] + a, run[0] + b, r) for a, b, r in plan_grad_buckets(run[1], run[2], max(1, bucket_bytes // 4))]
                     if n is None:
@@ -996,10 +986,7 @@ class UNetTrainer:
         flat = self.opt.grad
         works, hooks = [], {}
 
-        native = getattr(self, "native_comm", None)      # phendiff_amd.comm.NativeComm: RCCL through the C ABI (pd_allreduce_bucket)
-
-        timing = getattr(self, "comm_timing", False)      # bench.py: events around every bucket's collective on the comm stream
-        skip = getattr(self, "skip_collectives", False)   # bench.py: the same step with the exchange left out (`step_ms_no_comm`)
+        native, timing, skip = self.native_comm, self.comm_timing, self.skip_collectives
         if timing:
             self._comm_events = []
 
@@ -1043,7 +1030,7 @@ class UNetTrainer:
         backward.  comm_ms = busy time of the comm stream (sum over the buckets' collectives, which run one after the other on it);
         exposed_ms = what was left of it when the backward's last launch finished (the optimizer waits that long); overlap_frac =
         (comm_ms - exposed_ms) / comm_ms -- SURVEY 8(d) cfg4's "all-reduce overlap fraction"."""
-        evs = getattr(self, "_comm_events", None)
+        evs = self._comm_events
         if not evs:
             return None
         comm_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in evs)
@@ -1077,7 +1064,7 @@ class UNetTrainer:
         dropped or replaced its packed weights since (``invalidate``), rebind first -- the replacement may have been packed
         from older parameters, so it is re-packed as well."""
         m = self.model
-        if m._weights is None and getattr(self, "_bound_w", None) is None:
+        if m._weights is None and self._bound_w is None:
             return                                   # nothing packed yet: the first plan packs the current parameters
         self._bind_weights()
         if self._repack is None:

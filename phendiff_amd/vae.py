@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .training import mark_requires_grad_calls
-from .unet import UNetPlan, _Attention, _Block, _DT, _Op, _Sampler
+from .unet import UNetPlan, _Attention, _Block, _DT, _Sampler
 from .weight_layout import WeightSet
 
 SD_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512),
@@ -380,7 +380,7 @@ class VaeDecodePlan(_VaePlan):
         boc, B, H, W = c.block_out_channels, self.B, self.H, self.W
         lat = self._act(H, W, 32)
         self._in_args = L.NchwToNhwcArgs(dtype=self.code, B=B, C=c.latent_channels, HW=H * W, Cpad=32, x=None, out=lat.data_ptr())
-        self.ops.append(_Op(self.lib.pd_nchw_to_nhwc, self._in_args, "nchw_to_nhwc", 0.0, B * H * W * c.latent_channels * 4.0))
+        self._emit(self.lib.pd_nchw_to_nhwc, self._in_args, "nchw_to_nhwc", 0.0, B * H * W * c.latent_channels * 4.0)
         z, _ = self._conv(lat, None, w.post_quant_w, w.post_quant_b, 32, ksize=1, pad=0, stats=False)
         h, _ = self._conv(z, None, w.dec_in_w, w.dec_in_b, boc[-1])
         h = self._mid("decoder", h)

@@ -19,7 +19,7 @@ import torch
 from . import _lib as L
 from .unet import _Attention, _Sampler
 from .unet_train import UNetTrainPlan
-from .weight_layout import Repacker, WeightSet, contiguous_after as _contiguous_after, require_alias
+from .weight_layout import Repacker, WeightSet, require_alias
 from .vae import AutoencoderKL, VaeEncodePlan, _VaePlan, _VaeResnet, _VaeWeights
 
 VAE_PREFIX = "vae."
@@ -84,17 +84,11 @@ class VaeEncodeTrainPlan(UNetTrainPlan, VaeEncodePlan):
         self._dout_args = SimpleNamespace(x=None)
         self._init_train(tw, params, grads, False, frozen)
 
-    def _check_layout(self):
-        for d in (self.params, self.grads):
-            for n, mod in self.m.encoder.named_modules(prefix="encoder"):
-                if isinstance(mod, _Attention):
-                    for suffix in ("weight", "bias"):
-                        q, k, v = (d[f"{n}.{x}.{suffix}"] for x in ("to_q", "to_k", "to_v"))
-                        if not (_contiguous_after(q, k) and _contiguous_after(k, v)):
-                            raise ValueError("to_q/to_k/to_v parameters must be adjacent (use vae_training_param_order)")
-            for t in d.values():
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != torch.device(self.device):
-                    raise ValueError("training parameters / gradients must be contiguous fp32 tensors on the plan's device")
+    param_order_name = "vae_training_param_order"
+
+    def _fused_param_groups(self):
+        return [("to_q/to_k/to_v parameters must be adjacent", [f"{n}.{x}.{suffix}" for x in ("to_q", "to_k", "to_v")])
+                for n, mod in self.m.encoder.named_modules(prefix="encoder") if isinstance(mod, _Attention) for suffix in ("weight", "bias")]
 
     # ---- forward -----------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, moments: torch.Tensor, stream):
@@ -106,33 +100,23 @@ class VaeEncodeTrainPlan(UNetTrainPlan, VaeEncodePlan):
 
     # ---- backward ----------------------------------------------------------------------------------------------------
     def _bwd_record(self, rec):
-        c, tw, G = self.m.config, self.tw, self._G
+        c, tw = self.m.config, self.tw
         lat2 = 2 * c.latent_channels
         if rec.kind == "vae_out":
             dmom = self.dmom
             # quant_conv: 2 latent -> 2 latent inside 32 / 32 lanes.  The pad lanes of its input (conv_out's zero weights and bias)
             # and of its output gradient (pd_latent_chain_bwd) hold exact zeros; only the valid slice reaches the parameter
-            self._bias_grad(dmom, G("quant_conv.bias"), valid=lat2)
-            self._wgrad(rec.z, None, None, 0, dmom, G("quant_conv.weight"), ksize=1, pad=0, cout_valid=lat2, cin_valid=lat2)
+            self._bias_grad(dmom, "quant_conv.bias", valid=lat2)
+            self._wgrad(rec.z, None, None, 0, dmom, "quant_conv.weight", ksize=1, pad=0, cout_valid=lat2, cin_valid=lat2)
             dz = self._dgrad(dmom, tw.quant_d, 32, ksize=1, tag="dz_quant")
             # encoder.conv_out: block_out_channels[-1] -> 2 latent inside 32 lanes, over SiLU(GroupNorm(x))
-            self._bias_grad(dz, G("encoder.conv_out.bias"), valid=lat2)
-            self._wgrad(rec.x, None, rec.gn, 1, dz, G("encoder.conv_out.weight"), cout_valid=lat2)
+            self._bias_grad(dz, "encoder.conv_out.bias", valid=lat2)
+            self._wgrad(rec.x, None, rec.gn, 1, dz, "encoder.conv_out.weight", cout_valid=lat2)
             dx = self._dgrad(dz, tw.enc_out_d, rec.x.shape[3], tag="dz_out")
             self._gn_bwd(rec.gn, dx, 1, wname="encoder.conv_norm_out")
         elif rec.kind == "vae_conv_in":
-            if not self.param_grads:
-                return
-            B, H, W = self.B, self.H, self.W
-            dout = self._g(rec.out)[0]
-            self._bias_grad(dout, G("encoder.conv_in.bias"))
-            if "encoder.conv_in.weight" in self.frozen:
-                return
-            cols = self._tmp((B, H, W, 32), "im2col")
-            a = L.Im2col3Args(dtype=self.code, B=B, H=H, W=W, C=c.in_channels, x=None, out=cols.data_ptr())
-            self._sample_ptr_args.append(a)
-            self._b(self.lib.pd_im2col3, a, "im2col3", 0.0, cols.numel() * self._esz())
-            self._wgrad(cols, None, None, 0, dout, G("encoder.conv_in.weight"), ksize=1, pad=0, cin_valid=c.in_channels * 9)
+            if self.param_grads:
+                self._im2col_wgrad(self._g(rec.out)[0], "encoder.conv_in")
         else:
             super()._bwd_record(rec)
 

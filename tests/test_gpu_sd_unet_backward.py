@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from test_gpu_sd_unet import SMALL, TINY, WIDE, make_pair
-from test_gpu_unet_backward import compare
+from test_gpu_unet_backward import assert_fused_groups_become_ready_together, assert_grad_ready_is_the_last_writer, compare
 from test_gpu_unet_ddib import rel
 
 pytestmark = pytest.mark.gpu
@@ -187,6 +187,9 @@ def test_sd_training_step_bf16_reduces_loss_and_overlapped_path():
         op = plan.bwd_ops[idx]
         ptrs = [getattr(op.args, f) for f, _ in op.args._fields_]
         assert any(isinstance(v, int) and lo <= v < hi for v in ptrs), (name, idx, op.what)
+    # ... the LAST such launch, for every parameter; attn1's to_q / to_k / to_v, attn2's to_k / to_v and the stacked time_emb_proj share theirs
+    assert_grad_ready_is_the_last_writer(plan, tr.grads)
+    assert_fused_groups_become_ready_together(plan, tr.grads)
 
 
 def test_sd_save_state_resume_continues_bitwise(tmp_path):

@@ -46,6 +46,43 @@ def compare(ref, got, per_param_tol, global_tol):
     assert num ** 0.5 / gnorm < global_tol
 
 
+def assert_grad_ready_is_the_last_writer(plan, grads):
+    """``grad_ready[name]`` is where the overlapped all-reduce hands the parameter's bucket over: no backward op after it may carry a
+    pointer into that parameter's own gradient segment [data_ptr, data_ptr + 4 numel) (a later writer would be reduced over)."""
+    import bisect
+    import ctypes as C
+    segs = sorted((g.data_ptr(), g.data_ptr() + g.numel() * 4, n) for n, g in grads.items() if n in plan.grad_ready)
+    starts = [s[0] for s in segs]
+    for i, op in enumerate(plan.bwd_ops):
+        for f, ctype in op.args._fields_:
+            v = getattr(op.args, f)
+            if ctype is not C.c_void_p or not v:
+                continue
+            k = bisect.bisect_right(starts, v) - 1
+            if k >= 0 and v < segs[k][1]:
+                name = segs[k][2]
+                assert i <= plan.grad_ready[name], (name, plan.grad_ready[name], i, op.what, f)
+
+
+def fused_gradient_groups(names):
+    """Parameters ONE launch writes the gradients of: each attention's to_q / to_k / to_v (weights, and biases where they exist), a cross
+    attention's (``attn2``) to_k / to_v, and the stacked time_emb_proj weights (biases) of all ResNet blocks."""
+    names = list(names)
+    for suffix in ("weight", "bias"):
+        for n in names:
+            if n.endswith(".to_k." + suffix):
+                base = n[:-len("to_k." + suffix)]
+                yield [f"{base}{x}.{suffix}" for x in (("to_k", "to_v") if base.endswith(".attn2.") else ("to_q", "to_k", "to_v"))]
+        yield [n for n in names if n.endswith(".time_emb_proj." + suffix)]
+
+
+def assert_fused_groups_become_ready_together(plan, grads):
+    groups = [g for g in fused_gradient_groups(grads) if g]
+    assert len(groups) >= 3
+    for g in groups:
+        assert len({plan.grad_ready[n] for n in g}) == 1, {n: plan.grad_ready[n] for n in g}
+
+
 @pytest.mark.parametrize("mode,per_tol,glob_tol", [("f32", 2e-4, 2e-5), ("bf16", 8e-2, 2e-2)])
 @pytest.mark.parametrize("size", [32, 64, 128])          # 128 = BASELINE configs[1]'s image size
 def test_unet_backward_matches_autograd(mode, per_tol, glob_tol, size):
@@ -399,7 +436,7 @@ def test_overlapped_gradient_allreduce_path_single_rank():
         assert set(plan.grad_ready) == set(tr.grads)                      # every parameter has a completion point
         assert plan.grad_ready["conv_out.weight"] < plan.grad_ready["mid_block.resnets.0.conv1.weight"] \
             < plan.grad_ready["conv_in.weight"] <= plan.grad_ready["time_embedding.linear_1.weight"]
-        # ... and that point IS a launch that writes into the flat gradient buffer (a helper launch emitted between _G() and the writer --
+        # ... and that point IS a launch that writes into the flat gradient buffer (a helper launch emitted in front of the writer --
         # the GroupNorm pre-apply of the q/k/v weight gradient -- once made a bucket's hand-over one launch early: invisible at one rank,
         # stale values reduced over the real gradient at two: tests/test_gpu_two_rank_overlap.py)
         lo, hi = tr.opt.grad.data_ptr(), tr.opt.grad.data_ptr() + tr.opt.grad.numel() * 4
@@ -407,6 +444,14 @@ def test_overlapped_gradient_allreduce_path_single_rank():
             op = plan.bwd_ops[idx]
             ptrs = [getattr(op.args, f) for f, _ in op.args._fields_]
             assert any(isinstance(v, int) and lo <= v < hi for v in ptrs), (name, idx, op.what)
+        # ... the LAST such launch, for every parameter; the members of a fused gradient launch share it
+        assert_grad_ready_is_the_last_writer(plan, tr.grads)
+        assert_fused_groups_become_ready_together(plan, tr.grads)
+        # the upsampler 16 -> 32 runs as four sub-pixel phases (eight ops: GEMM + fold each): its weight gradient is final after the fold of the
+        # fourth, and the hand-over must not sit inside the run
+        kinds = [op.what for op in plan.bwd_ops]
+        up = plan.grad_ready["up_blocks.1.upsamplers.0.conv.weight"]
+        assert kinds[up - 7:up + 1] == ["wgrad2x2", "wgrad2x2_fold"] * 4 and not kinds[up + 1].startswith("wgrad2x2"), kinds[up - 8:up + 2]
         loss = tr._forward_backward_overlapped(*args, labels.cuda(), None, None, 1, 4 << 20)
         torch.cuda.synchronize()
         assert len(tr._buckets) >= 4 and float(loss) > 0
