@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from .pipeline import ConditionalDDIMPipeline
-from .schedulers import DDIMInverseScheduler
+from .schedulers import DDIMInverseScheduler, randn_tensor
 
 
 @torch.no_grad()
@@ -318,47 +318,87 @@ class _ClassRows:
         plan.temb_rows(ts_rows, self.labels, self.emb, st, rows=self.rows, out=out)
 
 
-class DDIBGraph:
+def _sample_hw(unet, height, width):
+    ss = unet.config.sample_size
+    return height or (ss if isinstance(ss, int) else ss[0]), width or (ss if isinstance(ss, int) else ss[1])
+
+
+def _check_shape(what: torch.Tensor, static: torch.Tensor):
+    if tuple(what.shape) != tuple(static.shape):
+        raise ValueError(f"expected images of shape {tuple(static.shape)}, got {tuple(what.shape)}")
+
+
+class _TrajectoryRunner:
+    """What the captured trajectories share: the runner's stream, one capture, one replay, ``join`` and the graph's teardown.  A subclass
+    lays out its plan, static buffers and argument tables, then calls ``_capture()``; it supplies ``_enqueue(st)`` (the trajectory as
+    launches on ``st``, the runner's stream, which is also torch's current one) and ``_fill(*inputs)`` (a batch copied into the static
+    buffers, on the runner's stream)."""
+
+    def __init__(self, unet, batch_size: int, num_inference_steps: int, height, width, device, use_graph: bool):
+        self.device = torch.device(device) if device is not None else unet.device
+        self.H, self.W = _sample_hw(unet, height, width)
+        self.B, self.S = batch_size, num_inference_steps
+        self.lib = L.lib()
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.graph = C.c_void_p(None)
+        self.use_graph = use_graph
+
+    def _capture(self):
+        if not self.use_graph:
+            return
+        st = self.stream.cuda_stream
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.pd_graph_begin(st), "pd_graph_begin")
+        try:
+            with torch.cuda.stream(self.stream):
+                self._enqueue(st)
+        finally:
+            rc = self.lib.pd_graph_end(st, C.byref(self.graph))
+        L.check(rc, "pd_graph_end")
+
+    @torch.no_grad()
+    def _replay(self, join: bool, *inputs):
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self._fill(*inputs)
+            if self.use_graph:
+                L.check(self.lib.pd_graph_launch(self.graph, self.stream.cuda_stream), "pd_graph_launch")
+            else:
+                self._enqueue(self.stream.cuda_stream)
+        return self.join() if join else self
+
+    def join(self):
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return self
+
+    def __del__(self):
+        try:
+            if self.graph:
+                self.lib.pd_graph_destroy(self.graph)
+        except Exception:
+            pass
+
+
+class DDIBGraph(_TrajectoryRunner):
     """One hipGraph for the whole invert -> class-swap -> denoise trajectory of a batch.
 
     ``run(images, orig_labels, target_labels)`` copies the batch into static buffers, replays the graph and
     returns the float NHWC ``[0,1]`` images on the device (``.images``), the inverted latents (``.inverted``)
     and optionally the uint8 quantisation."""
 
+    def __new__(cls, pipe, batch_size, num_inference_steps, height=None, width=None, *args, **kw):
+        if cls is DDIBGraph and batch_size > pipe.unet.max_batch(*_sample_hw(pipe.unet, height, width)):
+            cls = _SlicedDDIBGraph
+        return super().__new__(cls)
+
     def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, height: int = None,
                  width: int = None, variant: str = "0.18.2", device=None, use_graph: bool = True, private_plan: bool = False):
         self.pipe = pipe
         unet = pipe.unet
-        self.device = torch.device(device) if device is not None else unet.device
-        ss = unet.config.sample_size
-        H = height or (ss if isinstance(ss, int) else ss[0])
-        W = width or (ss if isinstance(ss, int) else ss[1])
-        self.B, self.S, self.H, self.W = batch_size, num_inference_steps, H, W
-        B, S = self.B, self.S
-        dev = self.device
-        self.lib = L.lib()
+        super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, S, H, W, dev = self.B, self.S, self.H, self.W, self.device
         cin = unet.config.in_channels
-        self._bounds = None
-        mb = unet.max_batch(H, W)
-        if B > mb:
-            # One launch plan addresses each tensor with 32-bit byte offsets (< 2 GiB: 127 images of 256 x 256 x 64 bf16 channels), so a
-            # larger batch (SURVEY 8(d) sweeps batch_size up to 128) is replayed as even slices -- the samples of a batch are independent
-            # (utils_Img2Img.py:566-612: no cross-sample op anywhere on the path).  Slices of equal size share ONE captured graph.
-            n_sl = -(-B // mb)
-            step = -(-B // n_sl)
-            self._bounds = [(b0, min(B, b0 + step)) for b0 in range(0, B, step)]
-            self._runners = {}
-            for b0, b1 in self._bounds:
-                if b1 - b0 not in self._runners:
-                    self._runners[b1 - b0] = DDIBGraph(pipe, b1 - b0, S, H, W, variant, dev, use_graph, private_plan)
-            first = self._runners[self._bounds[0][1] - self._bounds[0][0]]
-            self.plan, self.stream, self.inv_ts, self.gen_ts = first.plan, first.stream, first.inv_ts, first.gen_ts
-            self.inverted = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
-            self.images = torch.empty((B, H, W, cin), dtype=torch.float32, device=dev)
-            self.images_u8 = torch.empty((B, H, W, cin), dtype=torch.uint8, device=dev)
-            self.graph = C.c_void_p(None)
-            self.use_graph = use_graph
-            return
         self.plan = unet.new_plan(B, H, W, dev) if private_plan else unet.plan_for(B, H, W, dev)
         # schedulers (host tables)
         self.inv = DDIMInverseScheduler.from_config(pipe.scheduler.config, variant=variant)
@@ -376,30 +416,20 @@ class DDIBGraph:
         self.inverted = torch.empty_like(self.x)
         self.images = torch.empty((B, H, W, cin), dtype=torch.float32, device=dev)
         self.images_u8 = torch.empty((B, H, W, cin), dtype=torch.uint8, device=dev)
-        self.ts_rows = torch.empty((nsteps * B,), dtype=torch.float32, device=dev)
+        self.ts_rows = torch.tensor(self.inv_ts + self.gen_ts, dtype=torch.float32).repeat_interleave(B).to(dev)
         self.class_rows = _ClassRows(self.plan, nsteps * B, dev)
-        ts_host = torch.tensor(self.inv_ts + self.gen_ts, dtype=torch.float32).repeat_interleave(B)
-        self.ts_rows.copy_(ts_host)
         self.temb = torch.empty((nsteps * B, self.plan.w.proj_dim), dtype=torch.float32, device=dev)
-        # per-step scheduler args
-        self.step_args = []
-        for sched, ts in ((self.inv, self.inv_ts), (fwd, self.gen_ts)):
-            c = sched.config
-            for t in ts:
-                sa, sb, sap, dirc, _ = sched.step_coefficients(t, 0.0)
-                self.step_args.append(L.DdimStepArgs(
-                    numel=self.x.numel(), per_sample=self.x[0].numel(), pred_type=L.PD_PRED[c.prediction_type],
-                    clip=int(bool(c.clip_sample)), clip_range=float(c.clip_sample_range), use_clipped_model_output=0,
-                    sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=self.x.data_ptr(),
-                    model_out=self.model_out.data_ptr(), uncond_out=None, w=None, w_per_sample=0, guidance_cfg=0,
-                    prev_sample=self.x.data_ptr(), pred_x0=None))
+        self.step_args = [sched.ddim_step_args(t, self.x, self.model_out, self.x)
+                          for sched, ts in ((self.inv, self.inv_ts), (fwd, self.gen_ts)) for t in ts]
         self.post_args = L.PostprocArgs(B=B, C=cin, H=H, W=W, x=self.x.data_ptr(), out_f32=self.images.data_ptr(),
                                         out_u8=self.images_u8.data_ptr())
-        self.stream = torch.cuda.Stream(device=dev)
-        self.graph = C.c_void_p(None)
-        self.use_graph = use_graph
-        if use_graph:
-            self._capture()
+        # device-to-device snapshot of the inverted latents via the add_noise kernel: 1*x + 0*x
+        self._ones = torch.ones((B,), dtype=torch.float32, device=dev)
+        self._zeros = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.snapshot_args = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0, x=self.x.data_ptr(),
+                                            noise=self.x.data_ptr(), sa=self._ones.data_ptr(), sb=self._zeros.data_ptr(),
+                                            out=self.inverted.data_ptr())
+        self._capture()
 
     # the trajectory, as launches on `st`
     def _enqueue(self, st):
@@ -411,84 +441,70 @@ class DDIBGraph:
             plan.run(self.x.data_ptr(), self.temb.data_ptr() + i * B * row_bytes, self.model_out.data_ptr(), st)
             L.check(lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
             if i == n_inv - 1:
-                self._copy_inverted(st)
+                L.check(lib.pd_add_noise(C.byref(self.snapshot_args), st), "pd_add_noise")
         L.check(lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
 
-    def _copy_inverted(self, st):
-        # device-to-device snapshot of the inverted latents via the add_noise kernel: 1*x + 0*x
-        a = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0, x=self.x.data_ptr(),
-                           noise=self.x.data_ptr(), sa=self._ones.data_ptr(), sb=self._zeros.data_ptr(),
-                           out=self.inverted.data_ptr())
-        L.check(self.lib.pd_add_noise(C.byref(a), st), "pd_add_noise")
+    def _fill(self, clean_images, orig_class_labels, target_class_labels):
+        B, n_inv, n_gen = self.B, len(self.inv_ts), len(self.gen_ts)
+        self.x.copy_(clean_images, non_blocking=True)
+        self.class_rows.fill(slice(0, n_inv * B), n_inv, B, orig_class_labels)
+        self.class_rows.fill(slice(n_inv * B, (n_inv + n_gen) * B), n_gen, B, target_class_labels)
 
-    def _capture(self):
-        st = self.stream.cuda_stream
-        self._ones = torch.ones((self.B,), dtype=torch.float32, device=self.device)
-        self._zeros = torch.zeros((self.B,), dtype=torch.float32, device=self.device)
-        torch.cuda.synchronize(self.device)
-        L.check(self.lib.pd_graph_begin(st), "pd_graph_begin")
-        try:
-            self._enqueue(st)
-        finally:
-            rc = self.lib.pd_graph_end(st, C.byref(self.graph))
-        L.check(rc, "pd_graph_end")
-
-    @torch.no_grad()
     def run(self, clean_images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor,
             join: bool = True):
         """``join=False`` leaves the caller's stream un-joined (call ``self.join()`` before reading the outputs), so several
         runners can replay concurrently on their own streams."""
-        B = self.B
-        if self._bounds is not None:
-            if tuple(clean_images.shape) != (B,) + tuple(self.inverted.shape[1:]):
-                raise ValueError(f"expected images of shape {tuple(self.inverted.shape)}, got {tuple(clean_images.shape)}")
-            for b0, b1 in self._bounds:
-                r = self._runners[b1 - b0]
-                r.run(clean_images[b0:b1], orig_class_labels[b0:b1], target_class_labels[b0:b1], join=False)
-                with torch.cuda.stream(r.stream):      # stream-ordered before the runner's next replay overwrites its outputs
-                    self.images[b0:b1].copy_(r.images, non_blocking=True)
-                    self.images_u8[b0:b1].copy_(r.images_u8, non_blocking=True)
-                    self.inverted[b0:b1].copy_(r.inverted, non_blocking=True)
-            if join:
-                self.join()
-            return self
-        if clean_images.shape != self.x.shape:
-            raise ValueError(f"expected images of shape {tuple(self.x.shape)}, got {tuple(clean_images.shape)}")
-        n_inv, n_gen = len(self.inv_ts), len(self.gen_ts)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.x.copy_(clean_images, non_blocking=True)
-            self.class_rows.fill(slice(0, n_inv * B), n_inv, B, orig_class_labels)
-            self.class_rows.fill(slice(n_inv * B, (n_inv + n_gen) * B), n_gen, B, target_class_labels)
-            if self.use_graph:
-                L.check(self.lib.pd_graph_launch(self.graph, self.stream.cuda_stream), "pd_graph_launch")
-            else:
-                if not hasattr(self, "_ones"):
-                    self._ones = torch.ones((B,), dtype=torch.float32, device=self.device)
-                    self._zeros = torch.zeros((B,), dtype=torch.float32, device=self.device)
-                self._enqueue(self.stream.cuda_stream)
-        if join:
-            cur.wait_stream(self.stream)
-        return self
+        _check_shape(clean_images, self.x)
+        return self._replay(join, clean_images, orig_class_labels, target_class_labels)
+
+
+class _SlicedDDIBGraph(DDIBGraph):
+    """What ``DDIBGraph(...)`` builds for a batch beyond ``unet.max_batch``: one launch plan addresses each tensor with 32-bit byte offsets
+    (< 2 GiB: 127 images of 256 x 256 x 64 bf16 channels), so a larger batch (SURVEY 8(d) sweeps batch_size up to 128) is replayed as even
+    slices -- the samples of a batch are independent (utils_Img2Img.py:566-612: no cross-sample op anywhere on the path).  Slices of equal
+    size share ONE single-plan runner, hence one captured graph; the outputs are gathered into buffers of the whole batch."""
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, height: int = None,
+                 width: int = None, variant: str = "0.18.2", device=None, use_graph: bool = True, private_plan: bool = False):
+        self.pipe = pipe
+        unet = pipe.unet
+        self.device = dev = torch.device(device) if device is not None else unet.device
+        self.H, self.W = H, W = _sample_hw(unet, height, width)
+        self.B, self.S = B, S = batch_size, num_inference_steps
+        n_sl = -(-B // unet.max_batch(H, W))
+        step = -(-B // n_sl)
+        self._bounds = [(b0, min(B, b0 + step)) for b0 in range(0, B, step)]
+        self._runners = {}
+        for b0, b1 in self._bounds:
+            if b1 - b0 not in self._runners:
+                self._runners[b1 - b0] = DDIBGraph(pipe, b1 - b0, S, H, W, variant, dev, use_graph, private_plan)
+        first = self._runners[self._bounds[0][1] - self._bounds[0][0]]
+        self.plan, self.stream, self.inv_ts, self.gen_ts = first.plan, first.stream, first.inv_ts, first.gen_ts
+        cin = unet.config.in_channels
+        self.inverted = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
+        self.images = torch.empty((B, H, W, cin), dtype=torch.float32, device=dev)
+        self.images_u8 = torch.empty((B, H, W, cin), dtype=torch.uint8, device=dev)
+        self.graph, self.use_graph = C.c_void_p(None), use_graph       # (the slices' runners own the graphs)
+
+    @torch.no_grad()
+    def run(self, clean_images, orig_class_labels, target_class_labels, join: bool = True):
+        _check_shape(clean_images, self.inverted)
+        for b0, b1 in self._bounds:
+            r = self._runners[b1 - b0]
+            r.run(clean_images[b0:b1], orig_class_labels[b0:b1], target_class_labels[b0:b1], join=False)
+            with torch.cuda.stream(r.stream):      # stream-ordered before the runner's next replay overwrites its outputs
+                self.images[b0:b1].copy_(r.images, non_blocking=True)
+                self.images_u8[b0:b1].copy_(r.images_u8, non_blocking=True)
+                self.inverted[b0:b1].copy_(r.inverted, non_blocking=True)
+        return self.join() if join else self
 
     def join(self):
-        if self._bounds is not None:
-            for r in self._runners.values():
-                r.join()
-            return self
-        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        for r in self._runners.values():
+            r.join()
         return self
 
-    def __del__(self):
-        try:
-            if self.graph:
-                self.lib.pd_graph_destroy(self.graph)
-        except Exception:
-            pass
 
-
-class SDDDIBGraph:
+class SDDDIBGraph(_TrajectoryRunner):
     """One hipGraph for the latent-diffusion DDIB transfer -- ``_ddib`` with a ``CustomStableDiffusionImg2ImgPipeline``
     (utils_Img2Img.py:566-612; custom_pipeline_stable_diffusion_img2img.py:667-711): VAE encode -> posterior sample (x
     ``scaling_factor``) -> S inversion steps under the original class -> class swap -> S denoising steps -> VAE decode ->
@@ -498,12 +514,10 @@ class SDDDIBGraph:
 
     def __init__(self, pipe, batch_size: int, num_inference_steps: int, height: int, width: int, variant: str = "0.18.2",
                  device=None, use_graph: bool = True):
-        from .schedulers import DDIMInverseScheduler as Inv
         self.pipe = pipe
         unet, vae = pipe.unet, pipe.vae
-        self.device = dev = torch.device(device) if device is not None else unet.device
-        self.B, self.S, self.H, self.W = B, S, H, W = batch_size, num_inference_steps, height, width
-        self.lib = L.lib()
+        super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, S, H, W, dev = self.B, self.S, self.H, self.W, self.device
         sf = 1 << (len(vae.config.block_out_channels) - 1)
         h, w = H // sf, W // sf
         lc = vae.config.latent_channels
@@ -513,13 +527,12 @@ class SDDDIBGraph:
             return [(b0, min(step, B - b0), vae._plan(kind, min(step, B - b0), ph, pw, dev)) for b0 in range(0, B, step)]
         self.enc_chunks, self.dec_chunks = chunks("enc", H, W), chunks("dec", h, w)
         self.plan = unet.plan_for(B, h, w, 77, dev)
-        self.inv = Inv.from_config(pipe.scheduler.config, variant=variant)
+        self.inv = DDIMInverseScheduler.from_config(pipe.scheduler.config, variant=variant)
         self.inv.set_timesteps(S)
         fwd = pipe.scheduler
         fwd.set_timesteps(S, device=dev)
         gen_ts, _ = pipe.get_timesteps(S, 1.0, dev)                     # strength = 1: all S steps (custom_pipeline...:375-382)
         self.inv_ts, self.gen_ts = [int(t) for t in self.inv.timesteps], [int(t) for t in gen_ts]
-        nsteps = len(self.inv_ts) + len(self.gen_ts)
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         self.x, self.moments, self.noise = f32(B, 3, H, W), f32(B, 2 * lc, h, w), f32(B, lc, h, w)
         self.latents, self.model_out, self.inverted, self.dec_in = f32(B, lc, h, w), f32(B, lc, h, w), f32(B, lc, h, w), f32(B, lc, h, w)
@@ -528,32 +541,12 @@ class SDDDIBGraph:
         self.ehs_orig, self.ehs_target = f32(B, 77, D), f32(B, 77, D)
         self.ts_rows = torch.tensor(self.inv_ts + self.gen_ts, dtype=torch.float32).repeat_interleave(B).to(dev)
         self.scaling = float(vae.config.scaling_factor)
-        self.step_args = []
-        for sched, ts in ((self.inv, self.inv_ts), (fwd, self.gen_ts)):
-            c = sched.config
-            for t in ts:
-                sa, sb, sap, dirc, _ = sched.step_coefficients(t, 0.0)
-                self.step_args.append(L.DdimStepArgs(
-                    numel=self.latents.numel(), per_sample=self.latents[0].numel(), pred_type=L.PD_PRED[c.prediction_type],
-                    clip=int(bool(c.clip_sample)), clip_range=float(c.clip_sample_range), use_clipped_model_output=0,
-                    sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=self.latents.data_ptr(),
-                    model_out=self.model_out.data_ptr(), uncond_out=None, w=None, w_per_sample=0, guidance_cfg=0,
-                    prev_sample=self.latents.data_ptr(), pred_x0=None))
+        self.step_args = [sched.ddim_step_args(t, self.latents, self.model_out, self.latents)
+                          for sched, ts in ((self.inv, self.inv_ts), (fwd, self.gen_ts)) for t in ts]
         self.sample_args = L.LatentSampleArgs(B=B, C=lc, HW=h * w, scale=self.scaling, moments=self.moments.data_ptr(),
                                               noise=self.noise.data_ptr(), out=self.latents.data_ptr())
         self.post_args = L.PostprocArgs(B=B, C=3, H=H, W=W, x=self.decoded.data_ptr(), out_f32=self.images.data_ptr(), out_u8=None)
-        self.stream = torch.cuda.Stream(device=dev)
-        self.graph = C.c_void_p(None)
-        self.use_graph = use_graph
-        if use_graph:
-            torch.cuda.synchronize(dev)
-            L.check(self.lib.pd_graph_begin(self.stream.cuda_stream), "pd_graph_begin")
-            try:
-                with torch.cuda.stream(self.stream):
-                    self._enqueue(self.stream.cuda_stream)
-            finally:
-                rc = self.lib.pd_graph_end(self.stream.cuda_stream, C.byref(self.graph))
-            L.check(rc, "pd_graph_end")
+        self._capture()
 
     def _enqueue(self, st):
         """The trajectory as launches on the current stream (``st``); the three torch calls are plain device-to-device kernels
@@ -581,40 +574,28 @@ class SDDDIBGraph:
             plan_.run(self.dec_in[b0:b0 + nb].data_ptr(), self.decoded[b0:b0 + nb].data_ptr(), st)
         L.check(lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
 
+    def _fill(self, clean_images, noise, ehs_orig, ehs_target):
+        self.x.copy_(clean_images, non_blocking=True)
+        self.noise.copy_(noise, non_blocking=True)
+        self.ehs_orig.copy_(ehs_orig)
+        self.ehs_target.copy_(ehs_target)
+
     @torch.no_grad()
     def run(self, clean_images, orig_class_labels, target_class_labels, generator=None, noise=None):
-        from .schedulers import randn_tensor
         from .sd_pipeline import hack_class_embedding
-        if clean_images.shape != self.x.shape:
-            raise ValueError(f"expected images of shape {tuple(self.x.shape)}, got {tuple(clean_images.shape)}")
+        _check_shape(clean_images, self.x)
         pipe, dev = self.pipe, self.device
-        cur = torch.cuda.current_stream(dev)
         if noise is None:
             noise = randn_tensor(tuple(self.noise.shape), generator, dev)
         eo = hack_class_embedding(pipe._encode_class(class_labels=orig_class_labels, device=dev, do_classifier_free_guidance=False))
         et = hack_class_embedding(pipe._encode_class(class_labels=target_class_labels, device=dev, do_classifier_free_guidance=False))
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.x.copy_(clean_images, non_blocking=True)
-            self.noise.copy_(noise, non_blocking=True)
-            self.ehs_orig.copy_(eo)
-            self.ehs_target.copy_(et)
-            if self.use_graph:
-                L.check(self.lib.pd_graph_launch(self.graph, self.stream.cuda_stream), "pd_graph_launch")
-            else:
-                self._enqueue(self.stream.cuda_stream)
-        cur.wait_stream(self.stream)
-        return self
-
-    def __del__(self):
-        try:
-            if self.graph:
-                self.lib.pd_graph_destroy(self.graph)
-        except Exception:
-            pass
+        # the trajectory leaves ITS context in the shared plan's `ehs` and k / v buffers, replayed or enqueued: an eager forward that
+        # comes back with the tensor it projected before this run must project it again
+        self.plan.forget_context()
+        return self._replay(True, clean_images, noise, eo, et)
 
 
-class CFGForwardStartGraph:
+class CFGForwardStartGraph(_TrajectoryRunner):
     """hipGraph form of the CFG forward-start transfer (utils_Img2Img.py:615-648 +
     pipeline_conditionial_ddim.py:248-347): ``add_noise`` to the first kept timestep, then per step a conditional
     and an unconditional UNet evaluation (``class_emb = 0``, pipeline :310-317) feeding ONE fused
@@ -629,12 +610,8 @@ class CFGForwardStartGraph:
         if guidance_eqn not in ("imagen", "CFG"):
             raise ValueError(f"Unknown guidance equation '{guidance_eqn}'; should be 'imagen' or 'CFG'")
         unet = pipe.unet
-        self.device = dev = torch.device(device) if device is not None else unet.device
-        ss = unet.config.sample_size
-        H = height or (ss if isinstance(ss, int) else ss[0])
-        W = width or (ss if isinstance(ss, int) else ss[1])
-        self.B, self.S = B, S = batch_size, num_inference_steps
-        self.lib = L.lib()
+        super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, S, H, W, dev = self.B, self.S, self.H, self.W, self.device
         if B > unet.max_batch(H, W):
             raise ValueError(f"batch_size {B} exceeds what one launch plan holds at {H}x{W} ({unet.max_batch(H, W)} images)")
         self.plan = unet.plan_for(B, H, W, dev)
@@ -665,30 +642,11 @@ class CFGForwardStartGraph:
         self.noise_args = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0,
                                          x=self.clean.data_ptr(), noise=self.noise.data_ptr(), sa=sa.data_ptr(),
                                          sb=sb.data_ptr(), out=self.x.data_ptr())
-        c = sch.config
-        self.step_args = []
-        for t in self.ts:
-            sa_, sb_, sap, dirc, _ = sch.step_coefficients(t, 0.0)
-            self.step_args.append(L.DdimStepArgs(
-                numel=self.x.numel(), per_sample=self.x[0].numel(), pred_type=L.PD_PRED[c.prediction_type],
-                clip=int(bool(c.clip_sample)), clip_range=float(c.clip_sample_range), use_clipped_model_output=0,
-                sqrt_a=sa_, sqrt_b=sb_, sqrt_ap=sap, dir_coef=dirc, sample=self.x.data_ptr(), model_out=self.cond_out.data_ptr(),
-                uncond_out=(self.uncond_out.data_ptr() if self.do_cfg else None), w=self.w_dev.data_ptr(), w_per_sample=0,
-                guidance_cfg=int(guidance_eqn == "CFG"), prev_sample=self.x.data_ptr(), pred_x0=None))
+        self.step_args = [sch.ddim_step_args(t, self.x, self.cond_out, self.x, self.uncond_out if self.do_cfg else None, self.w_dev,
+                                             guidance_cfg=guidance_eqn == "CFG") for t in self.ts]
         self.post_args = L.PostprocArgs(B=B, C=cin, H=H, W=W, x=self.x.data_ptr(), out_f32=self.images.data_ptr(),
                                         out_u8=self.images_u8.data_ptr())
-        self.stream = torch.cuda.Stream(device=dev)
-        self.graph = C.c_void_p(None)
-        self.use_graph = use_graph
-        if use_graph:
-            torch.cuda.synchronize(dev)
-            st = self.stream.cuda_stream
-            L.check(self.lib.pd_graph_begin(st), "pd_graph_begin")
-            try:
-                self._enqueue(st)
-            finally:
-                rc = self.lib.pd_graph_end(st, C.byref(self.graph))
-            L.check(rc, "pd_graph_end")
+        self._capture()
 
     def _enqueue(self, st):
         lib, plan, B = self.lib, self.plan, self.B
@@ -705,25 +663,13 @@ class CFGForwardStartGraph:
             L.check(lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
         L.check(lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
 
-    @torch.no_grad()
-    def run(self, clean_images: torch.Tensor, target_class_labels: torch.Tensor, noise: torch.Tensor):
+    def _fill(self, clean_images, target_class_labels, noise):
         n, B = len(self.ts), self.B
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.clean.copy_(clean_images, non_blocking=True)
-            self.noise.copy_(noise, non_blocking=True)
-            self.class_rows.fill(slice(0, n * B), n, B, target_class_labels)
-            if self.use_graph:
-                L.check(self.lib.pd_graph_launch(self.graph, self.stream.cuda_stream), "pd_graph_launch")
-            else:
-                self._enqueue(self.stream.cuda_stream)
-        cur.wait_stream(self.stream)
-        return self
+        self.clean.copy_(clean_images, non_blocking=True)
+        self.noise.copy_(noise, non_blocking=True)
+        self.class_rows.fill(slice(0, n * B), n, B, target_class_labels)
 
-    def __del__(self):
-        try:
-            if self.graph:
-                self.lib.pd_graph_destroy(self.graph)
-        except Exception:
-            pass
+    def run(self, clean_images: torch.Tensor, target_class_labels: torch.Tensor, noise: torch.Tensor):
+        _check_shape(clean_images, self.clean)
+        _check_shape(noise, self.noise)
+        return self._replay(True, clean_images, target_class_labels, noise)

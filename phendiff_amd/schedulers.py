@@ -118,35 +118,46 @@ class _SchedulerBase:
         dirc = (1 - ap - sigma ** 2) ** 0.5
         return float(sa), float(sb), float(sap), float(dirc), float(sigma)
 
+    def ddim_step_args(self, timestep, sample, model_out, prev_sample, uncond_out=None, w=None, guidance_cfg=False,
+                       use_clipped_model_output=False, pred_x0=None, eta=0.0, numel=None, per_sample=None, w_per_sample=None):
+        """The ``pd_ddim_step`` argument struct of one update at ``timestep``: prediction type and clipping from the config, the four
+        coefficients from :meth:`step_coefficients`.  Buffers are dense fp32 tensors or raw device pointers (ints); ``numel`` /
+        ``per_sample`` default to ``sample``'s and ``w_per_sample`` to "``w`` holds more than one weight", so raw pointers need them
+        spelled out.  ``uncond_out`` + ``w``: the guidance combine runs inside the update (``guidance_cfg``: the "CFG" equation)."""
+        sa, sb, sap, dirc, _ = self.step_coefficients(timestep, eta)
+        ptr = lambda b: b.data_ptr() if torch.is_tensor(b) else b
+        if numel is None:
+            numel, per_sample = sample.numel(), sample[0].numel()
+        if w_per_sample is None:
+            w_per_sample = torch.is_tensor(w) and w.numel() > 1
+        c = self.config
+        return L.DdimStepArgs(numel=numel, per_sample=per_sample, pred_type=_PRED[c.prediction_type], clip=int(bool(c.clip_sample)),
+                              clip_range=float(c.clip_sample_range), use_clipped_model_output=int(bool(use_clipped_model_output)),
+                              sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=ptr(sample), model_out=ptr(model_out),
+                              uncond_out=ptr(uncond_out), w=ptr(w), w_per_sample=int(w_per_sample), guidance_cfg=int(guidance_cfg),
+                              prev_sample=ptr(prev_sample), pred_x0=ptr(pred_x0))
+
     def _device_step(self, model_output, timestep, sample, eta, use_clipped_model_output, generator, variance_noise,
                      uncond_output=None, w=None, guidance_cfg=False, out=None, want_x0=True, stream=None):
         if not (sample.is_cuda and model_output.is_cuda):
             raise L.PhenDiffHipError("phendiff_amd schedulers step on MI355X tensors only (no CPU fallback)")
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        lib = L.lib()
-        sa, sb, sap, dirc, sigma = self.step_coefficients(timestep, eta)
         x = sample.contiguous().float()
         mo = model_output.contiguous().float()
         prev = torch.empty_like(x) if out is None else out
         x0 = torch.empty_like(x) if want_x0 else None
-        c = self.config
         wt = uo = None
         if uncond_output is not None:
             uo = uncond_output.contiguous().float()      # the kernel reads dense fp32, as it does model_output
             wt = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
-        a = L.DdimStepArgs(numel=x.numel(), per_sample=x[0].numel(), pred_type=_PRED[c.prediction_type],
-                           clip=int(bool(c.clip_sample)), clip_range=float(c.clip_sample_range),
-                           use_clipped_model_output=int(bool(use_clipped_model_output)),
-                           sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=x.data_ptr(), model_out=mo.data_ptr(),
-                           uncond_out=L.ptr(uo), w=L.ptr(wt), w_per_sample=int(wt is not None and wt.numel() > 1),
-                           guidance_cfg=int(guidance_cfg), prev_sample=prev.data_ptr(), pred_x0=L.ptr(x0))
+        a = self.ddim_step_args(timestep, x, mo, prev, uo, wt, guidance_cfg, use_clipped_model_output, x0, eta)
         st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
-        L.check(lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
+        L.check(L.lib().pd_ddim_step(C.byref(a), st), "pd_ddim_step")
         if eta > 0:
             if variance_noise is None:
                 variance_noise = randn_tensor(mo.shape, generator, mo.device, mo.dtype)
-            prev = prev + sigma * variance_noise.to(device=mo.device, dtype=mo.dtype)
+            prev = prev + self.step_coefficients(timestep, eta)[4] * variance_noise.to(device=mo.device, dtype=mo.dtype)
         return prev, x0
 
     def _per_sample_coefs(self, timesteps, device):

@@ -490,6 +490,11 @@ class SDUNetPlan(UNetPlan):
         self.run(sample.data_ptr(), self.temb_table.data_ptr(), out.data_ptr(), stream, context=fresh)
         self.keepalive = (sample, ts, ehs, out)
 
+    def forget_context(self):
+        """For whoever rewrites ``self.ehs`` and the k / v buffers behind ``forward``'s back (a captured trajectory running on this plan):
+        the next ``forward`` copies and projects its context again, whichever tensor it is."""
+        self._ctx_src = None
+
     def run(self, x_ptr, temb_ptr, out_ptr, stream, context=True):
         """``context=False``: the conditioning (``self.ehs``) is what the previous ``run`` saw -- its k / v projections are kept."""
         if self._cur != (x_ptr, temb_ptr, out_ptr):

@@ -342,3 +342,27 @@ def test_cross_attention_context_is_projected_once_per_context():
     ehs_b.copy_(ehs_a)                                                   # in-place change of the cached tensor: version bump -> fresh
     o4 = unet(lat, 500, ehs_b, return_dict=False)[0].clone()
     assert calls[-2:] == [True, True] and torch.equal(o4, o1)
+
+
+@pytest.mark.parametrize("use_graph", [True, False])
+def test_eager_forward_after_an_sd_ddib_graph_projects_its_context_again(use_graph):
+    """SDDDIBGraph runs on the UNet's shared plan and leaves its own class context in the plan's ``ehs`` and cross-attention k / v buffers,
+    replayed or enqueued eagerly.  An eager forward that comes back afterwards with the very tensor it projected before the run must not
+    take the cached-context shortcut."""
+    import phendiff_amd as P
+    from phendiff_amd.sd_pipeline import hack_class_embedding
+    _, pipe = make_pipe("f32")
+    unet = pipe.unet
+    g = torch.Generator().manual_seed(3)
+    lat = torch.randn(2, 4, 16, 16, generator=g).cuda()
+    x = (torch.rand(2, 3, 32, 32, generator=g) * 2 - 1).cuda()
+    noise = torch.randn(2, 4, 16, 16, generator=g).cuda()
+    labels = torch.tensor([0, 1]).cuda()
+    E = hack_class_embedding(pipe._encode_class(class_labels=labels, device=lat.device, do_classifier_free_guidance=False)).contiguous()
+    o1 = unet(lat, 500, E, return_dict=False)[0].clone()
+    runner = P.SDDDIBGraph(pipe, batch_size=2, num_inference_steps=2, height=32, width=32, use_graph=use_graph)
+    assert runner.plan is unet.plan_for(2, 16, 16, 77, lat.device)
+    runner.run(x, 1 - labels, 1 - labels, noise=noise)             # both phases under the other context
+    o2 = unet(lat, 500, E, return_dict=False)[0]
+    torch.cuda.synchronize()
+    assert torch.equal(o1, o2)

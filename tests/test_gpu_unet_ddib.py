@@ -403,6 +403,23 @@ def test_cfg_forward_start_eager_and_graph_vs_oracle(eqn, w):
     assert rel(out2.images, ref2) < 2e-4
 
 
+def test_cfg_forward_start_graph_refuses_a_batch_of_another_shape():
+    """A (1, C, H, W) batch or noise handed to a B = 3 runner is refused like DDIBGraph / SDDDIBGraph refuse it (``copy_`` would broadcast
+    it silently); nothing is launched: the output buffer keeps what it held."""
+    import phendiff_amd as P
+    _, pgot = _pipes("f32")
+    x, labels = synth_batch(3, 32)
+    noise = torch.randn(x.shape, generator=torch.Generator().manual_seed(7))
+    g = P.CFGForwardStartGraph(pgot, batch_size=3, num_inference_steps=4, height=32, width=32)
+    g.images.fill_(-7.0)
+    with pytest.raises(ValueError, match=r"expected images of shape \(3, 3, 32, 32\), got \(1, 3, 32, 32\)"):
+        g.run(x[:1].cuda(), labels.cuda(), noise.cuda())
+    with pytest.raises(ValueError, match=r"expected images of shape \(3, 3, 32, 32\), got \(1, 3, 32, 32\)"):
+        g.run(x.cuda(), labels.cuda(), noise[:1].cuda())
+    torch.cuda.synchronize()
+    assert bool((g.images == -7.0).all())
+
+
 def test_inverted_regeneration_reconstructs():
     """"inverted_regeneration" (utils_Img2Img.py:374-384) = DDIB with target = original class; more steps reconstruct
     the input at least as well (trend of saved_figures/reco_err_*.png), checked on the engine itself."""

@@ -61,6 +61,34 @@ def test_step_coefficients_match_oracle_arithmetic():
         assert sigma == 0.0
 
 
+def test_ddim_step_args_builder_reads_the_config_and_passes_pointers_through():
+    """``ddim_step_args`` (the one place a ``pd_ddim_step`` argument struct is built): coefficients of ``step_coefficients(t, 0)``,
+    prediction type and clipping from the config, everything else as the arguments say.  Raw pointers, no device."""
+    import phendiff_amd._lib as L
+    fwd = P.DDIMScheduler(**dict(P.SCHEDULER_CONFIGS["3k_steps_clipping_rescaling"], clip_sample=True, clip_sample_range=0.75))
+    inv = P.DDIMInverseScheduler(**dict(P.SCHEDULER_CONFIGS["SD_orig_config"], clip_sample=False, prediction_type="epsilon"))
+    for sched, t in ((fwd, 1500), (inv, 400)):
+        sched.set_timesteps(10)
+        c = sched.config
+        a = sched.ddim_step_args(t, 0x1000, 0x2000, 0x3000, numel=96, per_sample=48)
+        assert (a.sqrt_a, a.sqrt_b, a.sqrt_ap, a.dir_coef) == tuple(np.float32(v) for v in sched.step_coefficients(t, 0.0)[:4])
+        assert a.pred_type == L.PD_PRED[c.prediction_type] and a.clip == int(c.clip_sample)
+        assert a.clip_range == np.float32(c.clip_sample_range)
+        assert (a.numel, a.per_sample, a.sample, a.model_out, a.prev_sample) == (96, 48, 0x1000, 0x2000, 0x3000)
+        assert (a.uncond_out, a.w, a.pred_x0) == (None, None, None)
+        assert (a.w_per_sample, a.guidance_cfg, a.use_clipped_model_output) == (0, 0, 0)
+        b = sched.ddim_step_args(t, 0x1000, 0x2000, 0x1000, uncond_out=0x4000, w=0x5000, guidance_cfg=True,
+                                 use_clipped_model_output=True, pred_x0=0x6000, numel=96, per_sample=48, w_per_sample=True)
+        assert (b.uncond_out, b.w, b.pred_x0, b.prev_sample) == (0x4000, 0x5000, 0x6000, 0x1000)
+        assert (b.w_per_sample, b.guidance_cfg, b.use_clipped_model_output) == (1, 1, 1)
+        assert (b.sqrt_a, b.dir_coef, b.pred_type, b.clip) == (a.sqrt_a, a.dir_coef, a.pred_type, a.clip)
+    assert fwd.config.prediction_type != inv.config.prediction_type        # the two cases read different configs
+    # tensors in place of pointers: sizes and the per-sample-weight flag come from them
+    x, w3 = torch.zeros(2, 3, 4, 4), torch.ones(2)
+    a = fwd.ddim_step_args(1500, x, x, x, uncond_out=x, w=w3)
+    assert (a.numel, a.per_sample, a.sample, a.w, a.w_per_sample) == (96, 48, x.data_ptr(), w3.data_ptr(), 1)
+
+
 def test_no_cpu_fallback():
     s = P.DDIMScheduler(**P.SCHEDULER_CONFIGS["3k_steps_clipping_rescaling"])
     s.set_timesteps(4)
