@@ -37,7 +37,7 @@ extern "C" {
  * 8 = pd_geglu_bwd_args.sums / sum_splits / B, pd_layernorm_bwd_args.dxsum (bias gradients without a pass over dY), pd_upsample_phase_weights,
  * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
  * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample, pd_sample_stats
- * (+ pd_sample_stats_workspace). */
+ * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -892,6 +892,62 @@ typedef struct {
 } pd_sample_stats_args;
 size_t pd_sample_stats_workspace(int64_t B, int64_t n, int bins);
 int pd_sample_stats(const pd_sample_stats_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_kid_mmd, pd_feature_moments (added under ABI 8): the statistics of KID and FID over features that stay on the device -- torch-fidelity's
+ * metric_kid.py (polynomial-kernel MMD^2 over random subsets) and metric_fid.py (mean and np.cov) -- in fp64 on v_mfma_f64_16x16x4_f64 from
+ * fp32 features (every element widened exactly before any arithmetic).  csrc/metric_stats.hip; host side phendiff_amd.metrics
+ * (kernel_inception_distance_device, fid_statistics_device).  The matrix square root of FID and the Inception score stay on the host.
+ *
+ * pd_kid_mmd: for subset s, a_i = f1[idx1[s][i]] and b_i = f2[idx2[s][i]] (i < m), k(x, y) = (x . y * gamma + coef0)^degree (the power by
+ * repeated multiplication):
+ *     sums[s] = ( sum_{i != j} k(a_i, a_j),  sum_{i != j} k(b_i, b_j),  sum_{i, j} k(a_i, b_j) )
+ *     mmd[s]  = (sums[s][0] + sums[s][1]) / (m (m - 1)) - 2 sums[s][2] / m^2
+ *   f1 [N1][f1_stride], f2 [N2][f2_stride]: fp32, 16-byte aligned, strides in elements (>= D, multiples of 4); D a multiple of 64 in 64 .. 4096.
+ *   idx1, idx2: int32, row s at element s * idx_stride (idx_stride >= m); only the first m entries of a row are read.  CONTRACT:
+ *     0 <= idx1 < N1 and 0 <= idx2 < N2 -- the contents cannot be checked without a launch; the caller draws them and answers for them.
+ *   One workgroup per PD_METRIC_STATS_TILE^2 tile of a kernel matrix (XX and YY: upper-triangle tiles, an off-diagonal one counted twice; XY:
+ *   all); the matrices are never stored.  Rows at or past m of a ragged tile are not read and their kernel values are selected away (not
+ *   multiplied by zero), as are the diagonals of XX / YY.  One fp64 partial per tile goes to the workspace, a second launch folds a subset's
+ *   partials in tile order: no atomics, every sum in a fixed order -- results are bitwise reproducible and subset s does not depend on S or
+ *   on the other subsets.
+ *   workspace: pd_kid_mmd_workspace(S, m) bytes (8 per tile; 0 for sizes the call refuses), 8-byte aligned, contents irrelevant.
+ *   Refused before any launch: null args / pointers, misaligned f1 / f2, degree outside 1 .. 8, non-finite gamma / coef0, a workspace_bytes
+ *   below the query's (PD_ERR_ARG); D, the strides, S < 1, m < 2, m > min(N1, N2), idx_stride < m, more than 2^31 - 1 workgroups (PD_ERR_SHAPE).
+ *
+ * pd_feature_moments: mean [D] = sum_n f[n] / N and cov [D][cov_stride] = (F - mean)^T (F - mean) / (N - 1) (np.cov(rowvar=False)), fp64.
+ *   Column sums per chunk of PD_FEATURE_MOMENTS_CHUNK rows, folded in chunk order; the covariance contracts the centred rows (centred in fp64,
+ *   rows at or past N selected to zero) per upper-triangle tile and writes the tile and its mirror image from the same registers: cov is
+ *   bitwise symmetric, every element of its D columns is written, columns D .. cov_stride - 1 are left alone.
+ *   workspace: pd_feature_moments_workspace(N, D) bytes (the chunk sums; 0 for sizes the call refuses).
+ *   Refused before any launch: null args / pointers, misaligned f, a workspace_bytes below the query's (PD_ERR_ARG); D not a multiple of 64
+ *   in 64 .. 4096, f_stride < D or not a multiple of 4, cov_stride < D, N < 2, N >= 2^31 (PD_ERR_SHAPE). */
+#define PD_METRIC_STATS_TILE 64
+#define PD_FEATURE_MOMENTS_CHUNK 64
+typedef struct {
+  int D, S, m, degree;
+  int64_t N1, N2;
+  int64_t f1_stride, f2_stride;
+  int64_t idx_stride;
+  double gamma, coef0;
+  const float* f1; const float* f2;
+  const int32_t* idx1; const int32_t* idx2;
+  double* sums; double* mmd;
+  void* workspace; size_t workspace_bytes;
+} pd_kid_mmd_args;
+size_t pd_kid_mmd_workspace(int64_t S, int64_t m);
+int pd_kid_mmd(const pd_kid_mmd_args* a, void* stream);
+
+typedef struct {
+  int D;
+  int64_t N;
+  int64_t f_stride, cov_stride;
+  const float* f;
+  double* mean; double* cov;
+  void* workspace; size_t workspace_bytes;
+} pd_feature_moments_args;
+size_t pd_feature_moments_workspace(int64_t N, int D);
+int pd_feature_moments(const pd_feature_moments_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_comm_*: the data-parallel gradient exchange -- DistributedDataParallel's bucketed all-reduce under accelerator.backward(loss)

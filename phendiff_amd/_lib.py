@@ -334,6 +334,23 @@ SAMPLE_STATS_CHUNK = 8192
 SAMPLE_STATS_MAX_BINS = 4096
 
 
+class KidMmdArgs(C.Structure):
+    _fields_ = [("D", C.c_int), ("S", C.c_int), ("m", C.c_int), ("degree", C.c_int), ("N1", C.c_int64), ("N2", C.c_int64),
+                ("f1_stride", C.c_int64), ("f2_stride", C.c_int64), ("idx_stride", C.c_int64), ("gamma", C.c_double), ("coef0", C.c_double),
+                ("f1", vp), ("f2", vp), ("idx1", vp), ("idx2", vp), ("sums", vp), ("mmd", vp), ("workspace", vp),
+                ("workspace_bytes", C.c_size_t)]
+
+
+class FeatureMomentsArgs(C.Structure):
+    _fields_ = [("D", C.c_int), ("N", C.c_int64), ("f_stride", C.c_int64), ("cov_stride", C.c_int64), ("f", vp), ("mean", vp), ("cov", vp),
+                ("workspace", vp), ("workspace_bytes", C.c_size_t)]
+
+
+# pd_kid_mmd / pd_feature_moments: the tile of a Gram product and the rows per column-sum chunk, as the header defines them
+METRIC_STATS_TILE = 64
+FEATURE_MOMENTS_CHUNK = 64
+
+
 # every symbol include/phendiff_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pd_abi_version": (C.c_int, []),
@@ -401,6 +418,10 @@ SYMBOLS = {
     "pd_train_sample": (C.c_int, [C.POINTER(TrainSampleArgs), vp]),
     "pd_sample_stats": (C.c_int, [C.POINTER(SampleStatsArgs), vp]),
     "pd_sample_stats_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "pd_kid_mmd": (C.c_int, [C.POINTER(KidMmdArgs), vp]),
+    "pd_kid_mmd_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "pd_feature_moments": (C.c_int, [C.POINTER(FeatureMomentsArgs), vp]),
+    "pd_feature_moments_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
     "pd_graph_begin": (C.c_int, [vp]),
     "pd_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
     "pd_graph_launch": (C.c_int, [vp, vp]),

@@ -9,7 +9,8 @@ splits, 100 KID subsets, polynomial kernel (degree 3, gamma 1/d, coef0 1), RNG s
 
 Here the network runs on the HIP engine (``csrc/metric_kernels.hip``: ``pd_resize_tf1``, ``pd_conv_rect`` with the BatchNorm folded into
 weights and bias at pack time and the branch concatenations written in place, ``pd_pool2d``, ``pd_fc_f32``); the statistics are fp64 on the
-host, like the library's (numpy / scipy).  Deviation, stated: the reference writes PNG files and torch-fidelity reads them back; this module
+host, like the library's (numpy / scipy) -- or, with ``device_statistics=True``, fp64 on the device for the heavy part (``csrc/metric_stats.hip``:
+``pd_kid_mmd``, ``pd_feature_moments``) with the matrix square root and the Inception score still on the host.  Deviation, stated: the reference writes PNG files and torch-fidelity reads them back; this module
 takes the uint8 arrays themselves (``round(255 x)`` of the pipeline's float output -- the bytes the PNGs would hold), so there is no file
 round trip.  The module tree carries torch-fidelity's state_dict names: its published ``pt_inception-2015-12-05`` weights load with
 ``load_state_dict``.  They are not obtainable here (no network), so tests and examples run the structure on seeded random weights."""
@@ -335,6 +336,90 @@ def kernel_inception_distance(features_1, features_2, kid_subsets: int = 100, ki
     return {KEY_KID_MEAN: float(np.mean(mmds)), KEY_KID_STD: float(np.std(mmds))}
 
 
+def kid_subset_indices(n1: int, n2: int, kid_subsets: int = 100, kid_subset_size: int = 1000, rng_seed: int = 2020):
+    """The rows :func:`kernel_inception_distance` draws, as two int32 tables [kid_subsets][kid_subset_size]: per subset
+    ``rng.choice(n1, m, replace=False)`` and then ``rng.choice(n2, m, replace=False)`` from one ``RandomState(rng_seed)``."""
+    if kid_subset_size > n1 or kid_subset_size > n2:
+        raise ValueError(f"kid_subset_size {kid_subset_size} exceeds the number of samples ({n1}, {n2})")
+    rng = np.random.RandomState(rng_seed)
+    i1 = np.empty((kid_subsets, kid_subset_size), dtype=np.int32)
+    i2 = np.empty((kid_subsets, kid_subset_size), dtype=np.int32)
+    for i in range(kid_subsets):
+        i1[i] = rng.choice(n1, kid_subset_size, replace=False)
+        i2[i] = rng.choice(n2, kid_subset_size, replace=False)
+    return i1, i2
+
+
+# ---- the statistics of KID and FID on the device (csrc/metric_stats.hip: fp64 MFMA over the fp32 features; no host fallback) -----------
+def _device_features(f, what: str) -> torch.Tensor:
+    if not torch.is_tensor(f) or not f.is_cuda:
+        raise L.PhenDiffHipError(f"{what}: phendiff_amd runs on MI355X only (no CPU fallback): pass the features as a 'cuda' tensor")
+    if f.dtype != torch.float32 or f.ndim != 2:
+        raise ValueError(f"{what}: expecting fp32 features of shape (N, D), got {f.dtype} {tuple(f.shape)}")
+    if f.stride(1) != 1 or f.stride(0) % 4 or f.stride(0) < f.shape[1] or f.data_ptr() % 16:
+        f = f.contiguous()
+    return f
+
+
+def kid_mmd_device(f1: torch.Tensor, f2: torch.Tensor, idx1, idx2, degree: int = 3, gamma: Optional[float] = None, coef0: float = 1):
+    """One ``pd_kid_mmd`` call: ``(sums, mmd)`` ON THE DEVICE -- fp64 [S][3] (the off-diagonal sums of k(a, a) and k(b, b) and the whole
+    sum of k(a, b)) and fp64 [S] (the unbiased MMD^2) of the subsets ``a = f1[idx1[s]]``, ``b = f2[idx2[s]]``.  The index tables
+    (int32 [S][m], host arrays or tensors) are checked against the row counts here, on the host: the kernel cannot."""
+    f1, f2 = _device_features(f1, "kid_mmd_device"), _device_features(f2, "kid_mmd_device")
+    if f1.device != f2.device or f1.shape[1] != f2.shape[1]:
+        raise ValueError("kid_mmd_device: the two feature sets must share a device and a width")
+    i1 = np.ascontiguousarray(idx1.cpu().numpy() if torch.is_tensor(idx1) else idx1, dtype=np.int32)
+    i2 = np.ascontiguousarray(idx2.cpu().numpy() if torch.is_tensor(idx2) else idx2, dtype=np.int32)
+    if i1.ndim != 2 or i1.shape != i2.shape:
+        raise ValueError(f"kid_mmd_device: index tables of shapes {i1.shape} and {i2.shape} (two [S][m] tables)")
+    S, m = i1.shape
+    for tab, n in ((i1, f1.shape[0]), (i2, f2.shape[0])):
+        if tab.size and (tab.min() < 0 or tab.max() >= n):
+            raise ValueError(f"kid_mmd_device: a subset index outside 0 .. {n - 1}")
+    dev, D = f1.device, f1.shape[1]
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        d1, d2 = torch.from_numpy(i1).to(dev), torch.from_numpy(i2).to(dev)
+        sums = torch.empty((S, 3), dtype=torch.float64, device=dev)
+        mmd = torch.empty((S,), dtype=torch.float64, device=dev)
+        ws_bytes = lib.pd_kid_mmd_workspace(S, m)
+        ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
+        a = L.KidMmdArgs(D=D, S=S, m=m, degree=int(degree), N1=f1.shape[0], N2=f2.shape[0], f1_stride=f1.stride(0), f2_stride=f2.stride(0),
+                         idx_stride=m, gamma=float(gamma if gamma is not None else 1.0 / D), coef0=float(coef0), f1=f1.data_ptr(),
+                         f2=f2.data_ptr(), idx1=d1.data_ptr(), idx2=d2.data_ptr(), sums=sums.data_ptr(), mmd=mmd.data_ptr(),
+                         workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+        L.check(lib.pd_kid_mmd(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "pd_kid_mmd")
+    return sums, mmd
+
+
+def kernel_inception_distance_device(features_1: torch.Tensor, features_2: torch.Tensor, kid_subsets: int = 100, kid_subset_size: int = 1000,
+                                     degree: int = 3, gamma: Optional[float] = None, coef0: float = 1, rng_seed: int = 2020) -> dict:
+    """:func:`kernel_inception_distance` over fp32 features that stay on the device: the same subsets (:func:`kid_subset_indices`), the
+    per-subset MMD^2 from ``pd_kid_mmd`` in fp64; the mean and ``np.std`` of the ``kid_subsets`` values are taken on the host."""
+    f1, f2 = _device_features(features_1, "kernel_inception_distance_device"), _device_features(features_2, "kernel_inception_distance_device")
+    i1, i2 = kid_subset_indices(f1.shape[0], f2.shape[0], kid_subsets, kid_subset_size, rng_seed)
+    _, mmd = kid_mmd_device(f1, f2, i1, i2, degree, gamma, coef0)
+    mmds = mmd.cpu().numpy()
+    return {KEY_KID_MEAN: float(np.mean(mmds)), KEY_KID_STD: float(np.std(mmds))}
+
+
+def fid_statistics_device(features: torch.Tensor) -> tuple:
+    """:func:`fid_statistics` over fp32 features that stay on the device (``pd_feature_moments``): ``(mu [D], sigma [D][D])`` as fp64 device
+    tensors; :func:`fid_from_statistics` takes their ``.cpu().numpy()`` (the matrix square root stays on the host)."""
+    f = _device_features(features, "fid_statistics_device")
+    dev, (N, D) = f.device, f.shape
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        mu = torch.empty((D,), dtype=torch.float64, device=dev)
+        sigma = torch.empty((D, D), dtype=torch.float64, device=dev)
+        ws_bytes = lib.pd_feature_moments_workspace(N, D)
+        ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
+        a = L.FeatureMomentsArgs(D=D, N=N, f_stride=f.stride(0), cov_stride=D, f=f.data_ptr(), mean=mu.data_ptr(), cov=sigma.data_ptr(),
+                                 workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+        L.check(lib.pd_feature_moments(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "pd_feature_moments")
+    return mu, sigma
+
+
 def to_uint8(images) -> np.ndarray:
     """What the reference's PNG files hold: ``(images * 255).round().astype("uint8")`` of the pipeline's float NHWC output in [0, 1]
     (utils_training.py:829,915); uint8 arrays pass through."""
@@ -354,11 +439,46 @@ def extract_features(net: InceptionV3Features, images, batch_size: int = 64) -> 
     return {k: np.concatenate([o[k] for o in outs]) for k in outs[0]}
 
 
+def extract_features_device(net: InceptionV3Features, images, batch_size: int = 64) -> dict:
+    """:func:`extract_features` without the trip to the host: all three feature sets as fp32 tensors on ``net.device``.  ``images``: what
+    :func:`extract_features` takes, or a uint8 tensor already on the device (then nothing passes through the host)."""
+    if torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8:
+        u8 = images
+    else:
+        u8 = torch.from_numpy(np.ascontiguousarray(to_uint8(images)))
+    outs = [net(u8[i:i + batch_size].to(net.device)) for i in range(0, len(u8), batch_size)]
+    return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
+
+
+def _calculate_metrics_device(net, input1, input2, isc, fid, kid, kid_subset_size, batch_size, input2_features) -> dict:
+    f1 = extract_features_device(net, input1, batch_size)
+    out = {}
+    if isc:
+        out.update(inception_score(f1["logits_unbiased"].double().cpu().numpy()))
+    if fid or kid:
+        f2 = input2_features if input2_features is not None else extract_features_device(net, input2, batch_size)
+        g1, g2 = f1["2048"], f2["2048"]
+        if not torch.is_tensor(g2):      # features cached on the host: fp32 features widened to fp64, so the way back is exact
+            g2 = torch.from_numpy(np.ascontiguousarray(g2, dtype=np.float32))
+        g2 = g2.to(g1.device)
+        if fid:
+            out[KEY_FID] = fid_from_statistics(*(t.cpu().numpy() for t in fid_statistics_device(g1)),
+                                               *(t.cpu().numpy() for t in fid_statistics_device(g2)))
+        if kid:
+            out.update(kernel_inception_distance_device(g1, g2, kid_subset_size=kid_subset_size))
+    return out
+
+
 def calculate_metrics(net: InceptionV3Features, input1, input2=None, *, isc: bool = True, fid: bool = True, kid: bool = False,
-                      kid_subset_size: int = 1000, batch_size: int = 64, input2_features: Optional[dict] = None) -> dict:
+                      kid_subset_size: int = 1000, batch_size: int = 64, input2_features: Optional[dict] = None,
+                      device_statistics: bool = False) -> dict:
     """``torch_fidelity.calculate_metrics(input1=generated, input2=real, isc=, fid=, kid=, kid_subset_size=)`` on image arrays: IS of
     ``input1``; FID / KID between ``input1`` and ``input2``.  ``input2_features``: features of the real images extracted once (what the
-    reference gets from ``cache_root`` / ``input2_cache_name``)."""
+    reference gets from ``cache_root`` / ``input2_cache_name``).  ``device_statistics``: the 2048-d features stay on the device and the
+    statistics of FID (mean, covariance) and KID (per-subset MMD^2) come from ``pd_feature_moments`` / ``pd_kid_mmd``; the logits go to
+    the host for the Inception score, the covariances for the matrix square root; ``input2_features`` may then hold device tensors."""
+    if device_statistics:
+        return _calculate_metrics_device(net, input1, input2, isc, fid, kid, kid_subset_size, batch_size, input2_features)
     f1 = extract_features(net, input1, batch_size)
     out = {}
     if isc:
@@ -373,18 +493,21 @@ def calculate_metrics(net: InceptionV3Features, input1, input2=None, *, isc: boo
 
 
 def class_metrics_hook(net: InceptionV3Features, real_images_by_class: Dict[int, Sequence], results: dict, *, isc: bool = True,
-                       fid: bool = True, kid: bool = False, kid_subset_size: int = 1000, batch_size: int = 64):
+                       fid: bool = True, kid: bool = False, kid_subset_size: int = 1000, batch_size: int = 64,
+                       device_statistics: bool = False):
     """``on_class_done`` callback for :func:`phendiff_amd.eval_generation.generate_samples`: what ``_compute_log_metrics`` does after a
     class's images were generated (utils_training.py:948-1001) -- metrics of that class's generated images against its real images
-    (their features cached per class, like ``input2_cache_name``), stored as ``results[f"{metric}/{class_name}"]``."""
+    (their features cached per class, like ``input2_cache_name``), stored as ``results[f"{metric}/{class_name}"]``.
+    ``device_statistics``: as in :func:`calculate_metrics` (the cached features are device tensors then)."""
     cache: Dict[int, dict] = {}
+    extract = extract_features_device if device_statistics else extract_features
 
     def done(class_label: int, class_name: str, batches):
         gen = np.concatenate([to_uint8(b.images) for b in batches])
         if class_label not in cache:
-            cache[class_label] = extract_features(net, real_images_by_class[class_label], batch_size)
+            cache[class_label] = extract(net, real_images_by_class[class_label], batch_size)
         m = calculate_metrics(net, gen, isc=isc, fid=fid, kid=kid, kid_subset_size=kid_subset_size, batch_size=batch_size,
-                              input2_features=cache[class_label])
+                              input2_features=cache[class_label], device_statistics=device_statistics)
         for k, v in m.items():
             results[f"{k}/{class_name}"] = v
     return done
