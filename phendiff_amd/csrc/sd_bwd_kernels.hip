@@ -318,6 +318,18 @@ __global__ __launch_bounds__(256) void attn_d64_dkv_kernel(const pd_attn_d64_bwd
 // reductions per token
 // DXS (round 6, pd_layernorm_bwd_args.dxsum): a third column sum -- of dx as stored, the bias gradient of the Linear layer that wrote the residual
 // stream this dx is the gradient of (attn1 / attn2 to_out, proj_in): pd_channel_sum no longer reads dx back for it
+// fp16 only: a value materialised in an fp32 register before it is rounded to half.  Without it the compiler may fold the last multiply(-add) of
+// an expression into the fp16 conversion (v_fma_mix*_f16: ONE rounding) in one kernel and keep multiply + convert (two roundings) in another, and
+// two kernels that must store the same bits differ in the last fp16 bit about once in 10^5 elements (found by the fp16 runs of
+// test_layernorm_backward / test_geglu_backward).  f32 and bf16 have no such instruction: for them this is the identity and their code is unchanged.
+template <typename T>
+__device__ __forceinline__ float pin_f32(float x) {
+  if constexpr (std::is_same<T, half_t>::value) asm("" : "+v"(x));
+  return x;
+}
+
+// The DXS = true / false instantiations must store the SAME dx (the tests compare them): in fp16 the value that is rounded to the storage type is
+// an fp32 register (pin_f32).
 template <typename T, int NP, bool DXS>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const pd_layernorm_bwd_args a) {
   using E = Elem<T>;
@@ -402,7 +414,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const pd_layernorm_b
       if (pc < pieces) {
         float o[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = rstd * (g[i][j] - mg - v[i][j] * mgx) + (a.res ? rv[i][j] : 0.f);
+        for (int j = 0; j < 8; ++j) o[j] = pin_f32<T>(rstd * (g[i][j] - mg - v[i][j] * mgx) + (a.res ? rv[i][j] : 0.f));
         const typename E::Frag fo = E::pack(o);
         E::store(dx + pc * 8, fo);
         if constexpr (DXS) {
@@ -463,6 +475,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float* 
 }
 
 // GEGLU backward: y = h * gelu(g)  ->  dh = dy * gelu(g),  dg = dy * h * (Phi(g) + g * phi(g));  dx = [dh | dg]
+// The two kernels below must store the SAME dx (with and without the column sums): in fp16 the values that are rounded to the storage type are
+// fp32 registers (pin_f32).
 template <typename T>
 __global__ __launch_bounds__(256) void geglu_bwd_kernel(const pd_geglu_bwd_args a) {
   using E = Elem<T>;
@@ -479,8 +493,8 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const pd_geglu_bwd_args 
     for (int j = 0; j < 8; ++j) {
       const float cdf = 0.5f * (1.0f + erff(gv[j] * 0.7071067811865476f));
       const float pdf = 0.3989422804014327f * __expf(-0.5f * gv[j] * gv[j]);
-      dh[j] = dyv[j] * gv[j] * cdf;
-      dgv[j] = dyv[j] * hv[j] * (cdf + gv[j] * pdf);
+      dh[j] = pin_f32<T>(dyv[j] * gv[j] * cdf);
+      dgv[j] = pin_f32<T>(dyv[j] * hv[j] * (cdf + gv[j] * pdf));
     }
     E::store((T*)a.dx + row * 2 * a.inner + pc * 8, E::pack(dh));
     E::store((T*)a.dx + row * 2 * a.inner + a.inner + pc * 8, E::pack(dgv));
@@ -514,8 +528,8 @@ __global__ __launch_bounds__(256) void geglu_bwd_sums_kernel(const pd_geglu_bwd_
     for (int j = 0; j < 8; ++j) {
       const float cdf = 0.5f * (1.0f + erff(gv[j] * 0.7071067811865476f));
       const float pdf = 0.3989422804014327f * __expf(-0.5f * gv[j] * gv[j]);
-      dh[j] = dyv[j] * gv[j] * cdf;
-      dgv[j] = dyv[j] * hv[j] * (cdf + gv[j] * pdf);
+      dh[j] = pin_f32<T>(dyv[j] * gv[j] * cdf);
+      dgv[j] = pin_f32<T>(dyv[j] * hv[j] * (cdf + gv[j] * pdf));
     }
     const typename E::Frag fh = E::pack(dh), fg = E::pack(dgv);
     E::store((T*)a.dx + row * 2 * a.inner + pc * 8, fh);

@@ -16,7 +16,7 @@ def from_nhwc(y):
     return y.float().cpu().permute(0, 3, 1, 2)
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("shape", [(2, 64, 96, 16, 16, 3), (1, 32, 64, 40, 24, 3), (2, 128, 64, 8, 8, 1)])
 def test_conv_input_gradient_stride1(env, mode, shape):
     from phendiff_amd.packing import dgrad_weight
@@ -30,7 +30,7 @@ def test_conv_input_gradient_stride1(env, mode, shape):
     assert rel(from_nhwc(got), ref) < TOL[mode]
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("hw", [(32, 32), (16, 48), (8, 8)])
 def test_conv_input_gradient_stride2_zero_stuffed(env, mode, hw):
     from phendiff_amd.packing import dgrad_weight
@@ -44,7 +44,7 @@ def test_conv_input_gradient_stride2_zero_stuffed(env, mode, hw):
     assert rel(from_nhwc(got), ref) < TOL[mode]
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 def test_conv_input_gradient_fused_upsample(env, mode):
     from phendiff_amd.packing import dgrad_weight
     L, lib, _, dev = env
@@ -65,7 +65,7 @@ def test_conv_input_gradient_fused_upsample(env, mode):
         assert rel(from_nhwc(dx), want) < TOL[mode]
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("combined", [0, 1])
 @pytest.mark.parametrize("cfg", [(2, 64, 0, 16, 16, 1), (2, 128, 64, 8, 8, 1), (1, 256, 256, 8, 4, 0), (3, 32, 32, 4, 4, 1),
                                  (2, 1280, 1280, 4, 4, 1), (1, 1280, 640, 8, 4, 1), (2, 1280, 0, 4, 4, 0)])
@@ -124,7 +124,7 @@ def test_groupnorm_silu_backward(env, mode, cfg, combined):
     assert rel(dgamma.cpu() - 1.0, rg) < 2e-5 and rel(dbeta.cpu() - 2.0, rb) < 2e-5
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 def test_channel_sum(env, mode):
     L, lib, _, dev = env
     code, tdt = DT[mode]
@@ -139,7 +139,7 @@ def test_channel_sum(env, mode):
     assert torch.equal(out.cpu()[:, 96:], torch.ones(3, 32))
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("Cc", [2560, 10240])
 def test_channel_sum_wide(env, mode, Cc):
     """More than 2048 channels (the GEGLU projection bias of the SD transformer blocks): walked in chunks; split-pixel form."""
@@ -160,8 +160,11 @@ def test_channel_sum_wide(env, mode, Cc):
 
 
 # relative L2 bounds named for tests/test_gpu_guard_bands.py (same numbers as asserted below)
-CONV_WGRAD_TOL = {"f32": 2e-5, "bf16": 1e-4}       # bf16 inputs are exact here: only the fp32 sum order differs
-ATTN_D8_BWD_TOL = {"f32": 3e-5, "bf16": 2.5e-2}    # bf16: P, dS and the outputs are rounded to 8 mantissa bits
+CONV_WGRAD_TOL = {"f32": 2e-5, "bf16": 1e-4, "fp16": 1e-4}       # 16-bit inputs are exact here: only the fp32 sum order differs
+ATTN_D8_BWD_TOL = {"f32": 3e-5, "bf16": 2.5e-2, "fp16": 6.25e-3}    # bf16: P, dS and the outputs are rounded to 8 mantissa bits; fp16: 11 bits -> the bf16 bound / 4
+# (fp16 rounds 8 x finer than bf16; a factor of 2 is left for what does not shrink with the format: fast exp / rcp)
+CONV_WGRAD_FUSED_TOL = {"f32": 2e-5, "bf16": 4e-3, "fp16": 1e-3}    # fused input transform: fast SiLU + rounding of Z to the storage type
+ATTN_D8_LSE_ATOL = {"f32": 1e-4, "bf16": 8e-2, "fp16": 2e-2}        # absolute, log2 domain: q * scale is rounded to the storage type before the MFMA
 
 
 def run_wgrad(env, mode, x0, dy, *, x1=None, ksize=3, stride=1, pad=1, upsample=0, silu=0, scale=None, shift=None,
@@ -205,7 +208,7 @@ def run_wgrad(env, mode, x0, dy, *, x1=None, ksize=3, stride=1, pad=1, upsample=
     return dw.cpu()
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("shape", [(2, 64, 64, 32, 32), (1, 32, 96, 16, 16), (3, 128, 64, 8, 8), (1, 64, 128, 40, 72), (2, 192, 32, 20, 12)])
 def test_conv_weight_gradient_3x3(env, mode, shape):
     B, cin, cout, H, W = shape
@@ -220,7 +223,7 @@ def test_conv_weight_gradient_3x3(env, mode, shape):
     assert rel(one_split, ref) < (2e-5 if mode == "f32" else 1e-4)
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 def test_conv_weight_gradient_fused_input_transform_and_concat(env, mode):
     B, c0, c1, cout, H, W = 2, 64, 32, 64, 24, 16
     g = torch.Generator().manual_seed(22)
@@ -232,10 +235,10 @@ def test_conv_weight_gradient_fused_input_transform_and_concat(env, mode):
     (ref,) = torch.autograd.grad(F.conv2d(z, w, None, padding=1), w, dy)
     prev = torch.randn(cout, c0 + c1, 3, 3, generator=g)
     got = run_wgrad(env, mode, x[:, :c0], dy, x1=x[:, c0:], silu=1, scale=scale, shift=shift, prev=prev)
-    assert rel(got - prev, ref) < (2e-5 if mode == "f32" else 4e-3)    # bf16: fast SiLU + rounding of Z to bf16
+    assert rel(got - prev, ref) < (2e-5 if mode == "f32" else 4e-3 if mode == "bf16" else CONV_WGRAD_FUSED_TOL[mode])    # bf16: fast SiLU + rounding of Z to bf16
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("hw", [(32, 32), (16, 48), (8, 8)])
 def test_conv_weight_gradient_stride2(env, mode, hw):
     H, W = hw
@@ -248,7 +251,7 @@ def test_conv_weight_gradient_stride2(env, mode, hw):
     assert rel(got, ref) < (2e-5 if mode == "f32" else 1e-4)
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 def test_conv_weight_gradient_upsample_and_1x1_and_padded_channels(env, mode):
     L, lib, _, dev = env
     code, tdt = DT[mode]
@@ -286,7 +289,7 @@ def test_conv_weight_gradient_upsample_and_1x1_and_padded_channels(env, mode):
     assert rel(got.reshape(64, 3, 3, 3), ref) < (2e-5 if mode == "f32" else 1e-4)
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("shape,splits", [((2, 64, 64, 8, 12), None), ((1, 96, 128, 33, 40), None), ((3, 64, 32, 32, 32), 1), ((2, 32, 64, 40, 70), 20)])
 def test_upsampler_weight_gradient_through_four_subpixel_phases(env, mode, shape, splits):
     """pd_conv_wgrad(phase = 1 + 2 a + b): the gradient of Upsample2D's 3x3 weights through the sub-pixel form -- phase (a, b) multiplies the
@@ -329,7 +332,7 @@ def test_upsampler_weight_gradient_through_four_subpixel_phases(env, mode, shape
     assert lib.pd_conv_wgrad(C.byref(a), stream()) != 0
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("cfg", [(2, 4, 64), (1, 8, 1024), (2, 8, 200), (1, 2, 16), (1, 3, 300),
                                  # round 5, the one-pass form: one key block exactly, three ragged key blocks, ragged queries and keys, two blocks x batch
                                  (2, 2, 512), (1, 2, 1300), (1, 3, 600), (2, 4, 2048)])
@@ -353,7 +356,7 @@ def test_attention_backward(env, mode, cfg):
     scores = torch.einsum("bhqd,bhkd->bhqk", q.detach().double(), k.detach().double()) / 8 ** 0.5
     want_lse = torch.logsumexp(scores, -1) * 1.4426950408889634
     torch.cuda.synchronize()
-    assert float((lse.cpu().double() - want_lse).abs().max()) < (1e-4 if mode == "f32" else 8e-2)   # bf16: q*scale is rounded to bf16 before the MFMA (forward and backward alike)
+    assert float((lse.cpu().double() - want_lse).abs().max()) < (1e-4 if mode == "f32" else 8e-2 if mode == "bf16" else ATTN_D8_LSE_ATOL[mode])   # bf16: q*scale is rounded to bf16 before the MFMA (forward and backward alike)
 
     DO = dout.to(tdt).to(dev).contiguous()
     delta = torch.empty((B, heads, N), device=dev)
@@ -414,3 +417,129 @@ def test_native_comm_world_one_allreduce(env):
     with pytest.raises(Exception):
         comm.allreduce_(x.half())
     comm.close()
+
+
+# ---- pd_gn_silu_bwd features that only the whole-UNet comparison reached: modulation, fused channel sums, ragged pixel splits ----------------------
+def run_gn_bwd(env, mode, cfg, splits, *, modulated=False, sums=False, seed=81):
+    """One pd_gn_silu_bwd call against fp64 autograd of z = silu?(F.group_norm(x, 32, gamma, beta) [* (1 + scale_n) + shift_n]).  dx0 accumulates on
+    a previous gradient, dgamma / dbeta on 1 / 2; dmod and the sum buffers start as NaN.  Returns what the GPU wrote and the fp64 references."""
+    L, lib, _, dev = env
+    code, tdt = DT[mode]
+    B, c0, c1, H, W, silu = cfg
+    Cc, hw = c0 + c1, H * W
+    g = torch.Generator().manual_seed(seed)
+    x = bf16_round(torch.randn(B, Cc, H, W, generator=g) * 1.5 + 0.3, mode).double().requires_grad_(True)
+    gamma = (torch.randn(Cc, generator=g) * 0.5 + 1.0).double().requires_grad_(True)
+    beta = (torch.randn(Cc, generator=g) * 0.3).double().requires_grad_(True)
+    dz = bf16_round(torch.randn(B, Cc, H, W, generator=g), mode)
+    stride = 2 * Cc + 24
+    mod = torch.randn(B, stride, generator=g) * 0.3                   # rows of [scale | shift | 24 columns nobody may read or write]
+    scale = mod[:, :Cc].double().requires_grad_(True)
+    shift = mod[:, Cc:2 * Cc].double().requires_grad_(True)
+    y = F.group_norm(x, 32, gamma, beta, eps=1e-5)
+    if modulated:
+        y = y * (1 + scale[:, :, None, None]) + shift[:, :, None, None]
+    z = F.silu(y) if silu else y
+    rx, rg, rb, rsc, rsh = torch.autograd.grad(z, (x, gamma, beta, scale, shift), dz.double(), allow_unused=True)
+
+    xd = x.detach().float()
+    X0, X1 = nhwc(xd[:, :c0].to(dev), tdt), (nhwc(xd[:, c0:].to(dev), tdt) if c1 else None)
+    D0, D1 = nhwc(dz[:, :c0].to(dev), tdt), (nhwc(dz[:, c0:].to(dev), tdt) if c1 else None)
+    xg = x.detach().reshape(B, 32, -1)
+    mean = xg.mean(-1).float().to(dev)
+    rstd = (1.0 / torch.sqrt(xg.var(-1, unbiased=False) + 1e-5)).float().to(dev)
+    partial = torch.empty((B, splits, Cc, 2), dtype=torch.float64, device=dev)
+    coef = torch.empty((B, 32, 2), device=dev)
+    prev0 = torch.randn(B, H, W, c0, generator=g).to(tdt).to(dev)
+    dx0 = prev0.clone()
+    dx1 = torch.full((B, H, W, c1), float("nan"), dtype=tdt, device=dev) if c1 else None
+    dgamma, dbeta = torch.ones(Cc, device=dev), torch.full((Cc,), 2.0, device=dev)
+    gm, bt = gamma.detach().float().to(dev), beta.detach().float().to(dev)
+    MOD = mod.to(dev) if modulated else None
+    dmod = torch.full((B, stride), float("nan"), device=dev) if modulated else None
+    sum0 = torch.full((B, splits, c0), float("nan"), device=dev) if sums else None
+    sum1 = torch.full((B, splits, c1), float("nan"), device=dev) if sums and c1 else None
+    b = L.GnBwdArgs(dtype=code, B=B, HW=hw, C0=c0, C1=c1, groups=32, silu=silu, x0=X0.data_ptr(), x1=L.ptr(X1), dz0=D0.data_ptr(), dz1=L.ptr(D1),
+                    mean=mean.data_ptr(), rstd=rstd.data_ptr(), gamma=gm.data_ptr(), beta=bt.data_ptr(), partial=partial.data_ptr(), splits=splits,
+                    coef=coef.data_ptr(), dx0=dx0.data_ptr(), dx1=L.ptr(dx1), accumulate0=1, accumulate1=0, dgamma=dgamma.data_ptr(),
+                    dbeta=dbeta.data_ptr(), dz_combined=0, res=None, sum0=L.ptr(sum0), sum1=L.ptr(sum1), mod=L.ptr(MOD),
+                    mod_stride=stride if modulated else 0, dmod=L.ptr(dmod))
+    L.check(lib.pd_gn_silu_bwd(C.byref(b), stream()), "pd_gn_silu_bwd")
+    torch.cuda.synchronize()
+    keep = (X0, X1, D0, D1, mean, rstd, partial, coef, gm, bt, MOD)      # the argument struct holds raw pointers into these
+    return dict(args=b, keep=keep, dx0=dx0, dx1=dx1, prev0=prev0, dgamma=dgamma, dbeta=dbeta, dmod=dmod, sum0=sum0, sum1=sum1,
+                rx=rx, rg=rg, rb=rb, rsc=rsc, rsh=rsh)
+
+
+def check_gn_bwd(mode, cfg, r):
+    c0, c1 = cfg[1], cfg[2]
+    tol = 2e-5 if mode == "f32" else TOL[mode]
+    assert rel(from_nhwc(r["dx0"]), r["rx"][:, :c0] + from_nhwc(r["prev0"])) < tol
+    if c1:
+        assert rel(from_nhwc(r["dx1"]), r["rx"][:, c0:]) < tol
+    assert rel(r["dgamma"].cpu() - 1.0, r["rg"]) < 2e-5 and rel(r["dbeta"].cpu() - 2.0, r["rb"]) < 2e-5
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
+@pytest.mark.parametrize("shape", [(3, 64, 4, 4), (2, 320, 9, 11)])
+def test_groupnorm_silu_backward_scale_shift_modulation(env, mode, shape):
+    """The scale_shift ResNets' norm2: z = silu(GroupNorm(x) (1 + scale_n) + shift_n) with [scale | shift] rows of stride 2 C + 24.  dgamma / dbeta
+    weight every sample with 1 + scale_n; dmod gets d scale_n and d shift_n and keeps its 24 padding columns; the forms the kernel cannot run are
+    refused (two sources with a modulation, dmod without mod)."""
+    L, lib, _, dev = env
+    B, Cc, H, W = shape
+    cfg = (B, Cc, 0, H, W, 1)
+    r = run_gn_bwd(env, mode, cfg, 4, modulated=True)
+    check_gn_bwd(mode, cfg, r)
+    dmod = r["dmod"].cpu()
+    assert rel(dmod[:, :Cc], r["rsc"]) < 2e-5
+    assert rel(dmod[:, Cc:2 * Cc], r["rsh"]) < 2e-5
+    assert bool(torch.isnan(dmod[:, 2 * Cc:]).all())
+    b = r["args"]
+    b.C0, b.C1 = Cc // 2, Cc // 2                      # a second source (pointers of the right kind, so that only the modulation is wrong)
+    b.x1, b.dz1, b.dx1 = b.x0, b.dz0, b.dx0
+    assert lib.pd_gn_silu_bwd(C.byref(b), stream()) != 0
+    b.C0, b.C1, b.x1, b.dz1, b.dx1 = Cc, 0, None, None, None
+    b.mod = None
+    assert lib.pd_gn_silu_bwd(C.byref(b), stream()) != 0
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
+def test_groupnorm_silu_backward_fused_channel_sums(env, mode):
+    """sum0 / sum1: the per-(sample, split, channel) sums of the dx values AS STORED (rounded, previous gradient included), in the workspace layout
+    pd_channel_sum(x = NULL) folds into per-sample sums and `total` -- the producer's bias / time-embedding gradients without another pass."""
+    L, lib, _, dev = env
+    code, tdt = DT[mode]
+    cfg, splits = (2, 128, 64, 8, 8, 1), 3
+    B, c0, c1 = cfg[:3]
+    r = run_gn_bwd(env, mode, cfg, splits, sums=True)
+    check_gn_bwd(mode, cfg, r)
+    for sums, dx, cs in ((r["sum0"], r["dx0"], c0), (r["sum1"], r["dx1"], c1)):
+        want = dx.double().sum((1, 2)).cpu()                       # [B][C] over the pixels of the stored tensor
+        assert rel(sums.double().sum(1).cpu(), want) < 1e-5
+        out = torch.full((B, cs), float("nan"), device=dev)
+        tot = torch.ones(cs, device=dev)
+        a = L.ChannelSumArgs(dtype=code, B=B, HW=cfg[3] * cfg[4], C=cs, x=None, out=out.data_ptr(), out_stride=cs, accumulate=0, total=tot.data_ptr(),
+                             total_valid=cs, workspace=sums.data_ptr(), splits=splits)
+        L.check(lib.pd_channel_sum(C.byref(a), stream()), "pd_channel_sum")
+        torch.cuda.synchronize()
+        assert rel(out.cpu(), want) < 1e-5
+        assert rel(tot.cpu() - 1.0, want.sum(0)) < 1e-5
+    # without a dx1 the call still runs, and sum0 does not change
+    b = r["args"]
+    dx0 = r["prev0"].clone()
+    sum0 = torch.full_like(r["sum0"], float("nan"))
+    b.dx0, b.dx1, b.sum0 = dx0.data_ptr(), None, sum0.data_ptr()
+    L.check(lib.pd_gn_silu_bwd(C.byref(b), stream()), "pd_gn_silu_bwd")
+    torch.cuda.synchronize()
+    assert torch.equal(sum0, r["sum0"]) and torch.equal(dx0, r["dx0"])
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16", "fp16"])
+@pytest.mark.parametrize("cfg,splits", [((2, 64, 0, 9, 33, 1), 7),       # HW = 297 = 6 x 43 + 39: a short last split
+                                        ((1, 320, 0, 3, 5, 0), 32)])     # more splits than pixels: empty splits; 40 pieces per chunk leave 16 threads idle
+def test_groupnorm_silu_backward_ragged_pixel_splits(env, mode, cfg, splits):
+    r = run_gn_bwd(env, mode, cfg, splits, sums=True)
+    check_gn_bwd(mode, cfg, r)
+    assert rel(r["sum0"].double().sum(1).cpu(), r["dx0"].double().sum((1, 2)).cpu()) < 1e-5

@@ -30,7 +30,7 @@ import torch.nn.functional as F
 
 from guard_bands import MIN_GUARD_BYTES, guard_size, guarded, guarded_rows
 from test_gpu_kernels import ATTN_D8_TOL, DT, bf16_round, env, rel, stream  # noqa: F401
-from test_gpu_sd_kernels import (ATTN_D64_BWD_TOL, ATTN_D64_LSE_TOL, ATTN_D64_TOL, KMAX2_RTOL, LINEAR_FOLD_TOL, LINEAR_GN_TOL, LN_BWD_PARAM_TOL, LN_BWD_TOL, ROW_OP_TOL,
+from test_gpu_sd_kernels import (ATTN_D64_BWD_TOL, ATTN_D64_LSE_TOL, ATTN_D64_TOL, GEGLU_BWD_TOL, KMAX2_RTOL, LINEAR_FOLD_TOL, LINEAR_GN_TOL, LN_BWD_PARAM_TOL, LN_BWD_TOL, ROW_OP_TOL,
                                  TOKEN_WGRAD_TOL)
 
 pytestmark = pytest.mark.gpu
@@ -963,7 +963,7 @@ def geglu_bwd_case(env_, mode, key):
     def check(O):
         h, gate = x.chunk(2, dim=-1)
         (h * F.gelu(gate)).backward(dy)
-        assert rel(O["dx"].float(), x.grad) < ROW_OP_TOL[mode]
+        assert rel(O["dx"].float(), x.grad) < GEGLU_BWD_TOL[mode]
 
     return Case(ins, outs, launch, check, nsamples=rows)
 
@@ -1004,9 +1004,9 @@ def temb_case(env_, mode, key):
 
 
 # ---- the tests ---------------------------------------------------------------------------------------------------------------------------
-ALL3, F32_BF16 = ["f32", "bf16", "fp16"], ["f32", "bf16"]
+ALL3 = ["f32", "bf16", "fp16"]
 PER_SAMPLE = ([("pd_attn_d64", attn_d64_case, k, m) for k in ATTN_D64_CASES for m in ALL3]
-              + [("pd_attn_d64_bwd", attn_d64_bwd_case, k, m) for k in ATTN_D64_BWD_CASES for m in F32_BF16]
+              + [("pd_attn_d64_bwd", attn_d64_bwd_case, k, m) for k in ATTN_D64_BWD_CASES for m in ALL3]
               + [("pd_attn_d8", attn_d8_case, k, m) for k, (_, km) in ATTN_D8_CASES.items() for m in (["bf16", "fp16"] if km else ALL3)]
               + [("pd_linear", linear_case, k, m) for k, (_, e) in LINEAR_CASES.items() for m in (ALL3 if not e else ["bf16", "fp16"])]
               + [("pd_linear-glu", linear_geglu_case, k, m) for k, (_, e) in LINEAR_GEGLU_CASES.items() for m in (ALL3 if not e else ["bf16", "fp16"])]
@@ -1015,17 +1015,17 @@ PER_SAMPLE = ([("pd_attn_d64", attn_d64_case, k, m) for k in ATTN_D64_CASES for 
               + [("pd_conv-tail", conv_tail_case, k, m) for k in CONV_TAIL_CASES for m in ALL3]
               + [("pd_conv-phase", conv_phase_case, k, m) for k in ("fwd-9x33", "fwd-20x17", "phase_in-9x33") for m in ALL3]
               + [("pd_conv-im2col3", conv_im2col3_case, k, m) for k in ("9x33", "24x40") for m in ALL3]
-              + [("pd_attn_d8_bwd", attn_d8_bwd_case, k, m) for k, (_, op1) in ATTN_D8_BWD_CASES.items() for m in (["bf16"] if op1 else F32_BF16)]
+              + [("pd_attn_d8_bwd", attn_d8_bwd_case, k, m) for k, (_, op1) in ATTN_D8_BWD_CASES.items() for m in (["bf16", "fp16"] if op1 else ALL3)]
               + [("pd_attn_wide", attn_wide_case, k, m) for k in ("fwd-B3-h2-d128-77-outstrided", "bwd-B3-h2-d128-77-dqkv-strided") for m in ALL3]
               + [("pd_gn", gn_case, k, m) for k in ("stats", "finalize", "apply") for m in ALL3]
-              + [("pd_layernorm_bwd", layernorm_bwd_case, k, m) for k in ("37x64", "513x1280-res") for m in F32_BF16]
-              + [("pd_geglu_bwd", geglu_bwd_case, k, m) for k in ("301x264", "333x256-sums-B3-s5") for m in F32_BF16]
+              + [("pd_layernorm_bwd", layernorm_bwd_case, k, m) for k in ("37x64", "513x1280-res") for m in ALL3]
+              + [("pd_geglu_bwd", geglu_bwd_case, k, m) for k in ("301x264", "333x256-sums-B3-s5") for m in ALL3]
               + [("pd_temb", temb_case, k, "f32") for k in ("11rows-emb", "3rows")]
               + [("pd_layernorm", layernorm_case, k, m) for k in ("37x64", "301x640", "5x2048") for m in ALL3]
               + [("pd_geglu", geglu_case, k, m) for k in ("301x256", "7x1288") for m in ALL3])
-SUMMED_CONV = [("pd_conv_wgrad", conv_wgrad_case, k, m) for k in CONV_WGRAD_CASES for m in F32_BF16]
+SUMMED_CONV = [("pd_conv_wgrad", conv_wgrad_case, k, m) for k in CONV_WGRAD_CASES for m in ALL3]
 SUMMED = [("pd_token_wgrad", (lambda e, m, k, acc=acc: token_wgrad_case(e, m, k, acc)), f"{k}-acc{acc}", m)
-          for k in TOKEN_WGRAD_CASES for acc in (0, 1) for m in F32_BF16]
+          for k in TOKEN_WGRAD_CASES for acc in (0, 1) for m in ALL3]
 _id = lambda c: f"{c[0]}-{c[2]}-{c[3]}"
 
 
