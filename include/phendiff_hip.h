@@ -37,7 +37,8 @@ extern "C" {
  * 8 = pd_geglu_bwd_args.sums / sum_splits / B, pd_layernorm_bwd_args.dxsum (bias gradients without a pass over dY), pd_upsample_phase_weights,
  * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
  * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample, pd_sample_stats
- * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace). */
+ * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace), pd_lp_guidance_scaled, pd_guided_step
+ * (+ pd_guided_step_args). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -732,6 +733,30 @@ typedef struct {
 int pd_lp_guidance(const pd_lp_guidance_args* a, void* stream);
 typedef struct { int64_t numel; float scale; const float* x; const float* g_direct; const float* g_unet; float* out; } pd_guidance_apply_args;
 int pd_guidance_apply(const pd_guidance_apply_args* a, void* stream);
+/* pd_lp_guidance_scaled: pd_lp_guidance with every d_model_out element multiplied by *grad_scale -- a DEVICE scalar the kernel reads (the
+ * host never does), so a captured launch follows the scale between replays.  losses and d_sample_direct are unscaled.  With a power-of-two
+ * scale the result is pd_lp_guidance followed by d_model_out * scale, bit for bit.  grad_scale = NULL is refused (PD_ERR_ARG). */
+int pd_lp_guidance_scaled(const pd_lp_guidance_args* a, const float* grad_scale, void* stream);
+/* pd_guided_step: the elementwise tail of a guided step in ONE launch -- per element
+ *   u = g_unet * (1 / *grad_scale)      pushed = sample - guidance_scale * (g_direct + u)      prev_sample = ddim_step(model_out, pushed)
+ * bit for bit what `g_unet *= 1 / scale`, pd_guidance_apply and pd_ddim_step(sample = pushed) give as three launches (no guidance combine).
+ * A g_unet element that is not finite makes its thread store 1 to *overflow (left untouched otherwise: the caller zeroes it).  Every
+ * tensor must be 16-byte aligned (f32x4 loads / stores); a tensor beyond 1024 x 1024 elements is walked in a grid-stride loop. */
+typedef struct {
+  int64_t numel, per_sample;
+  int pred_type, clip; float clip_range;      /* as pd_ddim_step */
+  int use_clipped_model_output;
+  float sqrt_a, sqrt_b, sqrt_ap, dir_coef;    /* as pd_ddim_step */
+  float guidance_scale;                       /* guidance_loss_scale */
+  const float* grad_scale;                    /* device scalar, or NULL = 1 */
+  const float* sample;                        /* x_t */
+  const float* g_direct; const float* g_unet; /* d_sample_direct, the UNet input gradient (scaled) */
+  const float* model_out;                     /* computed BEFORE the push */
+  float* prev_sample;                         /* out, may alias sample */
+  float* pushed;                              /* out or NULL: x_t - s * grad */
+  int* overflow;                              /* device, or NULL: set to 1 if any g_unet element is not finite */
+} pd_guided_step_args;
+int pd_guided_step(const pd_guided_step_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stream capture helpers (hipGraph): the S-step sampling loop is captured once and replayed.

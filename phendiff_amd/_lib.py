@@ -248,6 +248,14 @@ class GuidanceApplyArgs(C.Structure):
     _fields_ = [("numel", C.c_int64), ("scale", C.c_float), ("x", vp), ("g_direct", vp), ("g_unet", vp), ("out", vp)]
 
 
+class GuidedStepArgs(C.Structure):
+    _fields_ = [("numel", C.c_int64), ("per_sample", C.c_int64), ("pred_type", C.c_int), ("clip", C.c_int),
+                ("clip_range", C.c_float), ("use_clipped_model_output", C.c_int),
+                ("sqrt_a", C.c_float), ("sqrt_b", C.c_float), ("sqrt_ap", C.c_float), ("dir_coef", C.c_float),
+                ("guidance_scale", C.c_float), ("grad_scale", vp), ("sample", vp), ("g_direct", vp), ("g_unet", vp),
+                ("model_out", vp), ("prev_sample", vp), ("pushed", vp), ("overflow", vp)]
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("heads", C.c_int), ("N", C.c_int), ("q", vp), ("k", vp), ("v", vp),
                 ("o", vp), ("dout", vp), ("lse", vp), ("delta", vp), ("dqkv", vp), ("slab", vp), ("slab_bytes", C.c_size_t)]
@@ -407,6 +415,8 @@ SYMBOLS = {
     "pd_geglu": (C.c_int, [C.POINTER(GegluArgs), vp]),
     "pd_lp_guidance": (C.c_int, [C.POINTER(LpGuidanceArgs), vp]),
     "pd_guidance_apply": (C.c_int, [C.POINTER(GuidanceApplyArgs), vp]),
+    "pd_lp_guidance_scaled": (C.c_int, [C.POINTER(LpGuidanceArgs), vp, vp]),
+    "pd_guided_step": (C.c_int, [C.POINTER(GuidedStepArgs), vp]),
     "pd_diffusion_loss": (C.c_int, [C.POINTER(LossArgs), vp]),
     "pd_grad_norm": (C.c_int, [vp, C.c_int64, vp, C.c_float, vp, vp, vp]),
     "pd_adamw_ema": (C.c_int, [C.POINTER(AdamWEmaArgs), vp]),

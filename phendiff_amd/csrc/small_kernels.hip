@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include "pd_common.h"
+#include "pd_guided.h"
 
 namespace pd {
 
@@ -340,9 +341,7 @@ __global__ __launch_bounds__(1024) void gn_finalize3_kernel(const pd_gn_finalize
 // ================================================================================================
 // pd_ddim_step / pd_add_noise / pd_postproc: elementwise on fp32 NCHW
 // ================================================================================================
-// FP contraction is OFF here: the reference evaluates these formulas as separate fp32 mul / sub / div torch ops,
-// and epsilon-prediction divides by sqrt(alpha_bar) ~ 1e-5 near t = N, which amplifies a fused-vs-separate rounding
-// difference of the numerator by 1e5.  With contraction off every op is the same IEEE operation the CPU performs.
+// FP contraction is OFF in ddim_step_kernel and add_noise_kernel (ddim_step_elem, pd_guided.h, says why).
 __global__ __launch_bounds__(256) void ddim_step_kernel(const pd_ddim_step_args a) {
 #pragma clang fp contract(off)
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -368,14 +367,7 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const pd_ddim_step_args 
       const float w = a.w_per_sample ? a.w[(i0 + (j < cnt ? j : 0)) / a.per_sample] : a.w[0];
       out = a.guidance_cfg ? (o[j] + w * (o[j] - u[j])) : (u[j] + w * (o[j] - u[j]));
     }
-    float x0, eps;
-    if (a.pred_type == PD_PRED_EPSILON) { x0 = (x[j] - a.sqrt_b * out) / a.sqrt_a; eps = out; }
-    else if (a.pred_type == PD_PRED_SAMPLE) { x0 = out; eps = (x[j] - a.sqrt_a * x0) / a.sqrt_b; }
-    else { x0 = a.sqrt_a * x[j] - a.sqrt_b * out; eps = a.sqrt_a * out + a.sqrt_b * x[j]; }
-    if (a.clip) x0 = fminf(fmaxf(x0, -a.clip_range), a.clip_range);
-    if (a.use_clipped_model_output) eps = (x[j] - a.sqrt_a * x0) / a.sqrt_b;
-    x0v[j] = x0;
-    xp[j] = a.sqrt_ap * x0 + a.dir_coef * eps;
+    xp[j] = ddim_step_elem(a, x[j], out, x0v[j]);
   }
   if (cnt == 4) {
     *(f32x4*)(a.prev_sample + i0) = (f32x4){xp[0], xp[1], xp[2], xp[3]};

@@ -8,6 +8,8 @@ Two execution modes, same arithmetic:
   * graph  -- :class:`DDIBGraph` captures the whole 2*S-step trajectory (time/class embedding table, 2*S UNet
     evaluations, 2*S fused scheduler updates, post-processing) into ONE hipGraph and replays it per batch:
     no host round trip, no Python launch cost (~120 launches x 2*S per batch otherwise).
+The gradient-guided transfer (``:651-760``) has the same two modes: ``custom_guided_generation`` and :class:`GuidedTransferGraph` /
+:class:`SDGuidedTransferGraph`.
 """
 from __future__ import annotations
 
@@ -362,11 +364,15 @@ class _TrajectoryRunner:
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             self._fill(*inputs)
-            if self.use_graph:
-                L.check(self.lib.pd_graph_launch(self.graph, self.stream.cuda_stream), "pd_graph_launch")
-            else:
-                self._enqueue(self.stream.cuda_stream)
+            self._launch()
         return self.join() if join else self
+
+    def _launch(self):
+        """The trajectory once more over what the static buffers hold (on the runner's stream, which the caller made current)."""
+        if self.use_graph:
+            L.check(self.lib.pd_graph_launch(self.graph, self.stream.cuda_stream), "pd_graph_launch")
+        else:
+            self._enqueue(self.stream.cuda_stream)
 
     def join(self):
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
@@ -673,3 +679,295 @@ class CFGForwardStartGraph(_TrajectoryRunner):
         _check_shape(clean_images, self.clean)
         _check_shape(noise, self.noise)
         return self._replay(True, clean_images, target_class_labels, noise)
+
+
+# fp16 engine: the gradient scale is not halved below this (`custom_guided_generation` gives up at the same point)
+GUIDANCE_MIN_GRAD_SCALE = 2.0 ** -10
+
+
+def _check_guided_request(pipe, pipe_type, p):
+    """What a guided runner refuses before it packs a weight or builds a plan."""
+    if isinstance(p, str) or not (1.0 <= float(p) < 1e6):
+        raise NotImplementedError("Lp guidance: finite p >= 1 only (the reference config uses p = 2)")
+    if not isinstance(pipe, pipe_type):
+        raise NotImplementedError(f"{type(pipe).__name__}: this runner drives a {pipe_type.__name__}")
+    if pipe.unet.device.type != "cuda":
+        raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the pipeline to 'cuda'")
+
+
+class _GuidedSteps:
+    """The guided half of a captured trajectory: per step the input-gradient plan's forward, ``pd_lp_guidance`` (fp16:
+    ``pd_lp_guidance_scaled``), the plan's backward and ``pd_guided_step`` -- the launches of ``custom_guided_generation`` with its
+    per-step host decision moved to the device.  fp16: the gradient scale is a one-element device tensor the two kernels read and
+    ``overflow`` a device int ``pd_guided_step`` sets; :meth:`settle` reads it once per trajectory.
+
+    ``x``: the working buffer (updated in place), ``target``: the inverted start the Lp loss pulls towards, ``forward(i, ts, st)``: the
+    plan's forward of step ``i`` (``ts``: its (B,) timesteps) from ``x`` into ``model_out``."""
+
+    def __init__(self, lib, unet, plan, sched, timesteps, x, model_out, target, p, guidance_loss_scale, forward):
+        self.lib, self.plan, self.forward = lib, plan, forward
+        dev, B = x.device, x.shape[0]
+        self.fp16 = getattr(unet, "compute_dtype", None) == "fp16"
+        self.grad_scale = float(GUIDANCE_GRAD_SCALE) if self.fp16 else 1.0
+        self.scale_dev = torch.tensor([self.grad_scale], dtype=torch.float32, device=dev) if self.fp16 else None
+        self.overflow = torch.zeros((1,), dtype=torch.int32, device=dev) if self.fp16 else None
+        self.d_out, self.d_direct = torch.empty_like(x), torch.empty_like(x)
+        S = len(timesteps)
+        self.ts_rows = torch.tensor(timesteps, dtype=torch.float32).repeat_interleave(B).to(dev)
+        self.losses = torch.zeros((S, B), dtype=torch.float32, device=dev)
+        splits = max(1, min(64, x[0].numel() // 4096))
+        self.partial = torch.empty(B * splits, dtype=torch.float64, device=dev)
+        c = sched.config
+        common = dict(numel=x.numel(), per_sample=x[0].numel(), pred_type=L.PD_PRED[c.prediction_type], clip=int(bool(c.clip_sample)),
+                      clip_range=float(c.clip_sample_range))
+        self.lp_args, self.step_args = [], []
+        for i, t in enumerate(timesteps):
+            sa, sb, sap, dirc, _ = sched.step_coefficients(t)
+            self.lp_args.append(L.LpGuidanceArgs(sqrt_a=sa, sqrt_b=sb, p=float(p), sample=x.data_ptr(), model_out=model_out.data_ptr(),
+                                                 target=target.data_ptr(), partial=self.partial.data_ptr(), splits=splits,
+                                                 d_model_out=self.d_out.data_ptr(), d_sample_direct=self.d_direct.data_ptr(),
+                                                 losses=self.losses[i].data_ptr(), **common))
+            self.step_args.append(L.GuidedStepArgs(use_clipped_model_output=0, sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc,
+                                                   guidance_scale=float(guidance_loss_scale), grad_scale=L.ptr(self.scale_dev),
+                                                   sample=x.data_ptr(), g_direct=self.d_direct.data_ptr(), g_unet=plan.dsample.data_ptr(),
+                                                   model_out=model_out.data_ptr(), prev_sample=x.data_ptr(), pushed=None,
+                                                   overflow=L.ptr(self.overflow), **common))
+        plan._side_streams(torch.cuda.current_stream(dev).cuda_stream)      # (anything the backward creates lazily exists before a capture)
+
+    def enqueue(self, st):
+        lib, B = self.lib, self.d_out.shape[0]
+        for i, (lp, step) in enumerate(zip(self.lp_args, self.step_args)):
+            self.forward(i, self.ts_rows[i * B:(i + 1) * B], st)
+            if self.fp16:
+                L.check(lib.pd_lp_guidance_scaled(C.byref(lp), self.scale_dev.data_ptr(), st), "pd_lp_guidance_scaled")
+            else:
+                L.check(lib.pd_lp_guidance(C.byref(lp), st), "pd_lp_guidance")
+            # after_op given: the backward keeps every launch on `st` (one chain in the capture, no second stream)
+            self.plan.backward(self.d_out, st, after_op={})
+            L.check(lib.pd_guided_step(C.byref(step), st), "pd_guided_step")
+
+    def reset(self):
+        if self.fp16:
+            self.overflow.zero_()
+
+    def settle(self, runner):
+        """fp16: the one host read of a trajectory.  A gradient that was not finite anywhere along it halves the scale and runs the whole
+        trajectory again from the inputs the runner kept (a step cannot be redone alone: the launches after it have already consumed
+        its result); the scale reached stays for the runs that follow."""
+        if not self.fp16:
+            return
+        with torch.cuda.stream(runner.stream):
+            while bool(self.overflow.item()):
+                if self.grad_scale * 0.5 < GUIDANCE_MIN_GRAD_SCALE:
+                    raise FloatingPointError("gradient-guided transfer (fp16): the UNet input gradient is not finite at any scale")
+                self.grad_scale *= 0.5
+                self.scale_dev.mul_(0.5)
+                self.overflow.zero_()
+                runner._launch()
+
+
+class GuidedTransferGraph(_TrajectoryRunner):
+    """One hipGraph for the gradient-guided transfer (``_linear_interp_custom_guidance_inverted_start``, utils_Img2Img.py:651-760) with a
+    ``ConditionalDDIMPipeline``: S inversion steps under the original class, then S guided steps under the target class -- UNet
+    forward, Lp loss gradient, input-gradient backward, push + scheduler update -- and the post-processing; what
+    ``linear_interp_custom_guidance_inverted_start`` computes, bit for bit.
+
+    ``run(images, orig_labels, target_labels)`` leaves ``.images`` (NHWC float in [0, 1]), ``.images_u8``, ``.guided`` (the [-1, 1] NCHW
+    tensor of ``output_type="pt"``), ``.inverted``, ``.losses`` ((S, B): the Lp loss of every step) and ``.grad_scale``.
+
+    fp16 engine: the gradient scale lives on the device and starts at :data:`GUIDANCE_GRAD_SCALE`; a trajectory whose UNet input
+    gradient was not finite somewhere is replayed at half the scale (one host read per trajectory instead of one per step), down to
+    2^-10, and the scale reached is kept.
+
+    The inversion half runs on the model's inference plan (the one ``inversion`` uses: the same bits, no statistics kept), the guided
+    half on its input-gradient plan: both plans' activations are resident, the price of an inversion at inference speed."""
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, p: float, guidance_loss_scale: float,
+                 height: int = None, width: int = None, variant: str = "0.18.2", device=None, use_graph: bool = True):
+        _check_guided_request(pipe, ConditionalDDIMPipeline, p)
+        self.pipe = pipe
+        unet = pipe.unet
+        H, W = _sample_hw(unet, height, width)
+        if batch_size > unet.max_batch(H, W):
+            raise ValueError(f"batch_size {batch_size} exceeds what one launch plan holds at {H}x{W} ({unet.max_batch(H, W)} images)")
+        super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, S, dev = self.B, self.S, self.device
+        cin = unet.config.in_channels
+        self.plan = unet.plan_for(B, H, W, dev)
+        self.gplan = unet.input_grad_plan(B, H, W, dev)
+        self.inv = DDIMInverseScheduler.from_config(pipe.scheduler.config, variant=variant)
+        self.inv.set_timesteps(S)
+        fwd = pipe.scheduler
+        fwd.set_timesteps(S)
+        self.inv_ts, self.gen_ts = [int(t) for t in self.inv.timesteps], [int(t) for t in fwd.timesteps]
+        n_inv = len(self.inv_ts)
+        self.x = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
+        self.clean, self.model_out, self.inverted = (torch.empty_like(self.x) for _ in range(3))
+        self.guided = self.x
+        self.images = torch.empty((B, H, W, cin), dtype=torch.float32, device=dev)
+        self.images_u8 = torch.empty((B, H, W, cin), dtype=torch.uint8, device=dev)
+        self.ts_rows = torch.tensor(self.inv_ts, dtype=torch.float32).repeat_interleave(B).to(dev)
+        self.class_rows = _ClassRows(self.plan, n_inv * B, dev)
+        self.temb = torch.empty((n_inv * B, self.plan.w.proj_dim), dtype=torch.float32, device=dev)
+        self.inv_args = [self.inv.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.inv_ts]
+        # the target class of the guided half, in the form the input-gradient plan's forward takes without converting (a capture must
+        # not allocate): int64 ids (class table), fp32 values ("timestep") or the fp32 embedding rows themselves ("identity")
+        self.class_mode = getattr(self.gplan.w, "class_mode", None)
+        if self.class_mode == "identity":
+            self.g_labels, self.g_emb = None, torch.zeros((B, unet.time_embed_dim), dtype=torch.float32, device=dev)
+        else:
+            self.g_labels, self.g_emb = torch.zeros((B,), dtype=torch.int64 if self.class_mode is None else torch.float32, device=dev), None
+        self.steps = _GuidedSteps(self.lib, unet, self.gplan, fwd, self.gen_ts, self.x, self.model_out, self.inverted, p, guidance_loss_scale,
+                                  lambda i, ts, st: self.gplan.forward(self.x, ts, self.g_labels, self.g_emb, self.model_out, st))
+        self.losses = self.steps.losses
+        self.post_args = L.PostprocArgs(B=B, C=cin, H=H, W=W, x=self.x.data_ptr(), out_f32=self.images.data_ptr(),
+                                        out_u8=self.images_u8.data_ptr())
+        self._ones = torch.ones((B,), dtype=torch.float32, device=dev)
+        self._zeros = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.snapshot_args = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0, x=self.x.data_ptr(),
+                                            noise=self.x.data_ptr(), sa=self._ones.data_ptr(), sb=self._zeros.data_ptr(),
+                                            out=self.inverted.data_ptr())
+        self._capture()
+
+    @property
+    def grad_scale(self) -> float:
+        return self.steps.grad_scale
+
+    def _enqueue(self, st):
+        lib, plan, B = self.lib, self.plan, self.B
+        self.x.copy_(self.clean)              # the trajectory works in place: the batch itself stays for a replay at another scale
+        self.class_rows.temb(self.ts_rows, st, self.temb)
+        row_bytes = plan.w.proj_dim * 4
+        for i, a in enumerate(self.inv_args):
+            plan.run(self.x.data_ptr(), self.temb.data_ptr() + i * B * row_bytes, self.model_out.data_ptr(), st)
+            L.check(lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
+        L.check(lib.pd_add_noise(C.byref(self.snapshot_args), st), "pd_add_noise")
+        self.steps.enqueue(st)
+        L.check(lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
+
+    def _fill(self, clean_images, orig_class_labels, target_class_labels):
+        B, n_inv, dev = self.B, len(self.inv_ts), self.device
+        self.clean.copy_(clean_images, non_blocking=True)
+        self.class_rows.fill(slice(0, n_inv * B), n_inv, B, orig_class_labels)
+        if self.class_mode == "identity":
+            rows = target_class_labels.to(device=dev, dtype=torch.float32)
+            if rows.numel() != self.g_emb.numel():
+                raise ValueError(f"class_embed_type='identity': pass the (B, time_embed_dim) embedding rows, got {tuple(rows.shape)}")
+            self.g_emb.copy_(rows.view_as(self.g_emb))
+        else:
+            self.g_labels.copy_(target_class_labels.to(device=dev).view(B))
+        self.steps.reset()
+
+    def run(self, clean_images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor, join: bool = True):
+        """``join=False`` leaves the caller's stream un-joined (``self.join()`` before reading the outputs).  fp16: returns after the one
+        host read of the overflow flag, that is with the trajectory finished."""
+        _check_shape(clean_images, self.x)
+        self._replay(False, clean_images, orig_class_labels, target_class_labels)
+        self.steps.settle(self)
+        return self.join() if join else self
+
+
+class SDGuidedTransferGraph(_TrajectoryRunner):
+    """One hipGraph for the gradient-guided transfer with a ``CustomStableDiffusionImg2ImgPipeline`` (utils_Img2Img.py:651-760, latent
+    branch): VAE encode -> posterior sample (x ``scaling_factor``) -> S inversion steps on the latents under the original class -> S
+    guided steps through the SD UNet's input-gradient plan under the target class embeddings -> VAE decode.  The reference's min-max
+    renormalisation (:689-695: two reductions over the whole batch) runs after the replay, outside the capture.
+
+    ``run(images, orig_labels, target_labels, generator=None, noise=None)`` (the posterior noise is an input, as for
+    :class:`SDDDIBGraph`) leaves ``.guided`` (renormalised [-1, 1] NCHW, ``output_type="pt"``), ``.images`` (NHWC float in [0, 1]),
+    ``.guided_latents``, ``.inverted``, ``.losses`` and ``.grad_scale``; fp16 as in :class:`GuidedTransferGraph`.  The inversion half
+    runs on the inference plan, like there."""
+
+    def __init__(self, pipe, batch_size: int, num_inference_steps: int, p: float, guidance_loss_scale: float, height: int, width: int,
+                 variant: str = "0.18.2", device=None, use_graph: bool = True):
+        from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
+        _check_guided_request(pipe, CustomStableDiffusionImg2ImgPipeline, p)
+        self.pipe = pipe
+        unet, vae = pipe.unet, pipe.vae
+        super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, S, H, W, dev = self.B, self.S, self.H, self.W, self.device
+        sf = 1 << (len(vae.config.block_out_channels) - 1)
+        h, w = H // sf, W // sf
+        lc = vae.config.latent_channels
+
+        def chunks(kind, ph, pw):      # the VAE in sub-batches of what one of its launch plans addresses, like SDDDIBGraph
+            step = vae._max_batch(H, W, kind)
+            return [(b0, min(step, B - b0), vae._plan(kind, min(step, B - b0), ph, pw, dev)) for b0 in range(0, B, step)]
+        self.enc_chunks, self.dec_chunks = chunks("enc", H, W), chunks("dec", h, w)
+        self.plan = unet.plan_for(B, h, w, 77, dev)
+        self.gplan = unet.input_grad_plan(B, h, w, 77, dev)
+        self.inv = DDIMInverseScheduler.from_config(pipe.scheduler.config, variant=variant)
+        self.inv.set_timesteps(S)
+        fwd = pipe.scheduler
+        fwd.set_timesteps(S)
+        self.inv_ts, self.gen_ts = [int(t) for t in self.inv.timesteps], [int(t) for t in fwd.timesteps]
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self.x, self.moments, self.noise = f32(B, 3, H, W), f32(B, 2 * lc, h, w), f32(B, lc, h, w)
+        self.latents, self.model_out, self.inverted, self.dec_in = f32(B, lc, h, w), f32(B, lc, h, w), f32(B, lc, h, w), f32(B, lc, h, w)
+        self.guided_latents = self.latents
+        self.decoded = f32(B, 3, H, W)
+        self.guided = self.images = None
+        D = unet.config.cross_attention_dim
+        self.ehs_orig, self.ehs_target = f32(B, 77, D), f32(B, 77, D)
+        self.ts_rows = torch.tensor(self.inv_ts, dtype=torch.float32).repeat_interleave(B).to(dev)
+        self.scaling = float(vae.config.scaling_factor)
+        self.inv_args = [self.inv.ddim_step_args(t, self.latents, self.model_out, self.latents) for t in self.inv_ts]
+        self.sample_args = L.LatentSampleArgs(B=B, C=lc, HW=h * w, scale=self.scaling, moments=self.moments.data_ptr(),
+                                              noise=self.noise.data_ptr(), out=self.latents.data_ptr())
+        self.steps = _GuidedSteps(self.lib, unet, self.gplan, fwd, self.gen_ts, self.latents, self.model_out, self.inverted, p,
+                                  guidance_loss_scale,
+                                  lambda i, ts, st: self.gplan.forward(self.latents, ts, self.ehs_target, self.model_out, st))
+        self.losses = self.steps.losses
+        self._capture()
+
+    @property
+    def grad_scale(self) -> float:
+        return self.steps.grad_scale
+
+    def _enqueue(self, st):
+        lib, plan, B = self.lib, self.plan, self.B
+        for b0, nb, plan_ in self.enc_chunks:
+            plan_.run(self.x[b0:b0 + nb].data_ptr(), self.moments[b0:b0 + nb].data_ptr(), st)
+        L.check(lib.pd_latent_sample(C.byref(self.sample_args), st), "pd_latent_sample")
+        ta = plan.temb_args
+        plan.ehs.view(B, 77, -1).copy_(self.ehs_orig)      # (B, 77, D) fp32 -> the inference plan's compute-dtype buffer
+        for i, a in enumerate(self.inv_args):
+            ta.rows = B
+            ta.timesteps, ta.labels, ta.class_emb = self.ts_rows.data_ptr() + 4 * i * B, None, None
+            ta.emb, ta.proj = plan.temb_emb.data_ptr(), plan.temb_table.data_ptr()
+            L.check(lib.pd_temb(C.byref(ta), st), "pd_temb")
+            plan.run(self.latents.data_ptr(), plan.temb_table.data_ptr(), self.model_out.data_ptr(), st, context=(i == 0))
+            L.check(lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
+        self.inverted.copy_(self.latents)
+        self.steps.enqueue(st)
+        torch.div(self.latents, self.scaling, out=self.dec_in)        # vae.decode(latents / scaling_factor)
+        for b0, nb, plan_ in self.dec_chunks:
+            plan_.run(self.dec_in[b0:b0 + nb].data_ptr(), self.decoded[b0:b0 + nb].data_ptr(), st)
+
+    def _fill(self, clean_images, noise, ehs_orig, ehs_target):
+        self.x.copy_(clean_images, non_blocking=True)
+        self.noise.copy_(noise, non_blocking=True)
+        self.ehs_orig.copy_(ehs_orig)
+        self.ehs_target.copy_(ehs_target)
+        self.steps.reset()
+
+    @torch.no_grad()
+    def run(self, clean_images, orig_class_labels, target_class_labels, generator=None, noise=None, join: bool = True):
+        from .sd_pipeline import hack_class_embedding
+        _check_shape(clean_images, self.x)
+        pipe, dev = self.pipe, self.device
+        if noise is None:
+            noise = randn_tensor(tuple(self.noise.shape), generator, dev)
+        eo = hack_class_embedding(pipe._encode_class(class_labels=orig_class_labels, device=dev, do_classifier_free_guidance=False))
+        et = hack_class_embedding(pipe._encode_class(class_labels=target_class_labels, device=dev, do_classifier_free_guidance=False))
+        # the inversion leaves ITS context in the shared inference plan's `ehs` and k / v buffers: an eager forward that comes back with
+        # the tensor it projected before this run must project it again (the input-gradient plan projects on every forward anyway)
+        self.plan.forget_context()
+        self._replay(False, clean_images, noise, eo, et)
+        self.steps.settle(self)
+        with torch.cuda.stream(self.stream):      # :689-695, outside the capture: two reductions over the whole batch
+            image = self.decoded - self.decoded.min()
+            image = image / image.max()
+            self.guided = image * 2 - 1
+            self.images = (self.guided / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).contiguous()
+        return self.join() if join else self
