@@ -38,7 +38,7 @@ extern "C" {
  * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
  * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample, pd_sample_stats
  * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace), pd_lp_guidance_scaled, pd_guided_step
- * (+ pd_guided_step_args). */
+ * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -828,6 +828,29 @@ typedef struct {
   float* y_f32; unsigned char* y_u8;
 } pd_image_preprocess_args;
 int pd_image_preprocess(const pd_image_preprocess_args* a, void* stream);
+
+/* pd_image_preprocess_bands (added under ABI 8): the same transform for image stacks that are not RGB (Cell Painting's five stains, multiplexed
+ * immunofluorescence): C interleaved uint8 bands in, C bands out -- no replication, no dropped channel.  Every band is an independent mode-L
+ * image: the tables, the 22-bit fixed point and the horizontal-then-vertical order are those of pd_image_preprocess (one device function
+ * serves both kernels).  Fields as in pd_image_preprocess_args, except:
+ *   C in 1..32 channels are read from every pixel (C <= pixel_stride <= 64: a wider stride reads a strided view and skips the rest);
+ *   mean, std: device float32 [C] (read only when y_f32 is given);
+ *   y_u8 uint8 NHWC [out_slots][OH][OW][C]; y_f32 float32 NCHW [out_slots][C][OH][OW] = ((float)u8 / 255.f - mean[c]) / std[c].
+ * Refused as pd_image_preprocess refuses, plus C out of range (PD_ERR_ARG) and null mean / std with y_f32 (PD_ERR_ARG).  A workgroup stages
+ * whole source rows at the pixel stride given (span_x * pixel_stride + 4 bytes a row, span_x up to ~1060 columns at a 32 x horizontal
+ * down-scale), so a view into wide pixels (pixel_stride above ~45 at that scale) is refused with "tile does not fit the LDS budget"
+ * (PD_ERR_SHAPE) where the same bands stored densely run: pass a dense copy then (ImagePreprocessor does). */
+typedef struct {
+  int N, H, W, C, OH, OW, out_slots;
+  long long image_stride, row_stride; int pixel_stride;
+  int ksize_x, ksize_y;
+  const unsigned char* x;
+  const int* coef_x; const int* bounds_x; const int* coef_y; const int* bounds_y;
+  const int* out_index; const unsigned char* flips;
+  const float* mean; const float* std;
+  float* y_f32; unsigned char* y_u8;
+} pd_image_preprocess_bands_args;
+int pd_image_preprocess_bands(const pd_image_preprocess_bands_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_train_sample (added under ABI 8): the per-step sampling of perform_training_epoch (utils_training.py:244-256) on the device, one launch:

@@ -36,6 +36,7 @@ def library_is_current() -> bool:
 
 
 PD_F32, PD_BF16, PD_F16 = 0, 1, 2
+PD_ERR_SHAPE = -2      # pd_status: a shape the entry point refuses before it launches anything
 PD_PRED = {"epsilon": 0, "sample": 1, "v_prediction": 2}
 PD_OUT_NHWC, PD_OUT_NCHW_F32, PD_OUT_QKV_HEADS = 0, 1, 2
 ABI_VERSION = 8
@@ -325,6 +326,13 @@ class ImagePreprocessArgs(C.Structure):
                 ("std0", C.c_float), ("std1", C.c_float), ("std2", C.c_float), ("y_f32", vp), ("y_u8", vp)]
 
 
+class ImagePreprocessBandsArgs(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("OH", C.c_int), ("OW", C.c_int),
+                ("out_slots", C.c_int), ("image_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_int),
+                ("ksize_x", C.c_int), ("ksize_y", C.c_int), ("x", vp), ("coef_x", vp), ("bounds_x", vp), ("coef_y", vp),
+                ("bounds_y", vp), ("out_index", vp), ("flips", vp), ("mean", vp), ("std", vp), ("y_f32", vp), ("y_u8", vp)]
+
+
 class TrainSampleArgs(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("rank", C.c_int), ("purpose", C.c_int), ("B", C.c_int64),
                 ("per_sample", C.c_int64), ("elem_base", C.c_uint64), ("N", C.c_int), ("clean", vp), ("sqrt_acp", vp),
@@ -425,6 +433,7 @@ SYMBOLS = {
     "pd_pool2d": (C.c_int, [C.POINTER(Pool2dArgs), vp]),
     "pd_fc_f32": (C.c_int, [C.POINTER(FcF32Args), vp]),
     "pd_image_preprocess": (C.c_int, [C.POINTER(ImagePreprocessArgs), vp]),
+    "pd_image_preprocess_bands": (C.c_int, [C.POINTER(ImagePreprocessBandsArgs), vp]),
     "pd_train_sample": (C.c_int, [C.POINTER(TrainSampleArgs), vp]),
     "pd_sample_stats": (C.c_int, [C.POINTER(SampleStatsArgs), vp]),
     "pd_sample_stats_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),

@@ -1,6 +1,7 @@
 // Image preprocessing: decoded uint8 images -> the engine's float32 NCHW input (and the uint8 "raw" twin of the metric reference sets).
 //   pd_image_preprocess   Resize(BILINEAR) -> ToTensor -> Normalize [-> RandomHorizontalFlip -> RandomVerticalFlip] of
 //                         src/utils_dataset.py:104-127 and src/utils_Img2Img.py:197-206, which the reference runs per image in PIL on the host.
+//   pd_image_preprocess_bands   the same transform for stacks of 1..32 independent bands (C in, C out); both kernels call ip_resample_tile.
 // The resize is Pillow's 8-bit bilinear resample restated in the same integer arithmetic (ImagingResample: separable, antialiasing support
 // max(scale, 1), 22-bit fixed-point coefficients, accumulator 1 << 21, >> 22, clamp; horizontal pass first INTO uint8, then the vertical
 // pass; an axis whose size does not change is skipped, not run through an identity table), so the output is held to bit equality.  The
@@ -47,10 +48,15 @@ __device__ __forceinline__ unsigned char clip8(uint32_t acc) {
   return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-template <int CI>
-__global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_image_preprocess_args a, const ip_plan P) {
-#pragma clang fp contract(off)      // ToTensor / Normalize are separate fp32 div, sub, div torch ops: keep them separate IEEE operations
-  extern __shared__ __align__(16) unsigned char smem[];
+// The resample of one 8 x 32 output tile of image `n`, shared by the two entry points so that they cannot drift: channels
+// [cbase, cbase + ci) of every source pixel, each one an independent 8-bit band, through the horizontal and then the vertical pass.
+// `A` is either args struct (the geometry and table fields carry the same names).  CI > 0: the channel count at compile time (the
+// RGB / grey entry), CI == 0: `ci_rt` channels (the band entry).  Returns the tile in LDS, [th][P.irow] bytes with byte ox * ci + c of
+// a row = channel cbase + c of output column ox0 + ox; ends with a barrier.
+template <int CI, typename A>
+__device__ __forceinline__ const unsigned char* ip_resample_tile(const A& a, const ip_plan& P, unsigned char* smem, int n, int cbase, int ci_rt,
+                                                                 int ox0, int oy0, int tw, int th) {
+  const int ci = CI ? CI : ci_rt;
   int* const cx = (int*)smem;
   int* const cy = (int*)(smem + P.off_cy);
   int* const bx = (int*)(smem + P.off_bnd);          // [IP_TOW][2]: first source column relative to the tile's x0, count
@@ -59,11 +65,7 @@ __global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_i
   unsigned char* const stage = smem + P.off_stage;
   unsigned char* const outt = smem + P.off_out;
 
-  const int tid = threadIdx.x, n = blockIdx.z;
-  const int slot = a.out_index ? a.out_index[n] : n;
-  if (slot < 0 || slot >= a.out_slots) return;       // (uniform over the workgroup)
-  const int ox0 = blockIdx.x * IP_TOW, oy0 = blockIdx.y * IP_TOH;
-  const int tw = min(IP_TOW, a.OW - ox0), th = min(IP_TOH, a.OH - oy0);
+  const int tid = threadIdx.x;
   const bool rx = a.W != a.OW, ry = a.H != a.OH;
   const int ps = a.pixel_stride;
 
@@ -102,8 +104,8 @@ __global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_i
   }
 
   // ---- source rows -> LDS -> horizontal pass -> intermediate, R rows at a time
-  const unsigned char* img = a.x + (size_t)n * (size_t)a.image_stride + (size_t)x0 * ps;
-  const int seg = x1 > x0 ? (x1 - x0 - 1) * ps + CI : 0;     // bytes of a row this tile reads: up to the last channel it uses
+  const unsigned char* img = a.x + (size_t)n * (size_t)a.image_stride + (size_t)x0 * ps + cbase;
+  const int seg = x1 > x0 ? (x1 - x0 - 1) * ps + ci : 0;     // bytes of a row this tile reads: up to the last channel it uses
   const int ndw = P.lrow >> 2;
   for (int r0 = y0; r0 < y1; r0 += P.chunk_rows) {
     const int rows = min(P.chunk_rows, y1 - r0);
@@ -125,10 +127,10 @@ __global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_i
       }
     }
     __syncthreads();
-    const int per_row = tw * CI;
+    const int per_row = tw * ci;
     for (int idx = tid; idx < rows * per_row; idx += IP_THREADS) {
       const int r = idx / per_row, j = idx - r * per_row;
-      const int ox = j / CI, c = j - ox * CI;
+      const int ox = j / ci, c = j - ox * ci;
       const unsigned char* g = img + (size_t)(r0 + r) * (size_t)a.row_stride;
       const unsigned char* s = stage + r * P.lrow + (int)((uintptr_t)g & 3) + c;
       unsigned char v;
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_i
 
   // ---- vertical pass over the intermediate
   {
-    const int per_row = tw * CI;
+    const int per_row = tw * ci;
     for (int idx = tid; idx < th * per_row; idx += IP_THREADS) {
       const int oy = idx / per_row, j = idx - oy * per_row;
       unsigned char v;
@@ -167,6 +169,19 @@ __global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_i
     }
   }
   __syncthreads();
+  return outt;
+}
+
+template <int CI>
+__global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_image_preprocess_args a, const ip_plan P) {
+#pragma clang fp contract(off)      // ToTensor / Normalize are separate fp32 div, sub, div torch ops: keep them separate IEEE operations
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, n = blockIdx.z;
+  const int slot = a.out_index ? a.out_index[n] : n;
+  if (slot < 0 || slot >= a.out_slots) return;       // (uniform over the workgroup)
+  const int ox0 = blockIdx.x * IP_TOW, oy0 = blockIdx.y * IP_TOH;
+  const int tw = min(IP_TOW, a.OW - ox0), th = min(IP_TOH, a.OH - oy0);
+  const unsigned char* const outt = ip_resample_tile<CI>(a, P, smem, n, 0, CI, ox0, oy0, tw, th);
 
   // ---- outputs
   if (a.y_u8) {                      // uint8 NHWC: each tile row is tw * 3 contiguous bytes
@@ -194,6 +209,44 @@ __global__ __launch_bounds__(IP_THREADS) void image_preprocess_kernel(const pd_i
   }
 }
 
+// pd_image_preprocess_bands: C independent bands in, C bands out.  A workgroup owns one tile of one GROUP of `cg` consecutive bands of one
+// image (blockIdx.z = image * groups + group): the intermediate of a tile grows with the bands it carries, and the host picks the widest
+// group that fits the LDS budget (all C bands at the shapes of the RGB entry; fewer for many bands under a steep down-scale).
+__global__ __launch_bounds__(IP_THREADS) void image_preprocess_bands_kernel(const pd_image_preprocess_bands_args a, const ip_plan P, const int cg,
+                                                                            const int groups) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, n = blockIdx.z / groups, cbase = (blockIdx.z - n * groups) * cg;
+  const int slot = a.out_index ? a.out_index[n] : n;
+  if (slot < 0 || slot >= a.out_slots) return;       // (uniform over the workgroup)
+  const int ci = min(cg, a.C - cbase);
+  const int ox0 = blockIdx.x * IP_TOW, oy0 = blockIdx.y * IP_TOH;
+  const int tw = min(IP_TOW, a.OW - ox0), th = min(IP_TOH, a.OH - oy0);
+  const unsigned char* const outt = ip_resample_tile<0>(a, P, smem, n, cbase, ci, ox0, oy0, tw, th);
+
+  if (a.y_u8) {                      // uint8 NHWC [slot][OH][OW][C]: this group's ci bytes of every pixel of the tile
+    const int per_row = tw * ci;
+    for (int idx = tid; idx < th * per_row; idx += IP_THREADS) {
+      const int oy = idx / per_row, j = idx - oy * per_row;
+      const int ox = j / ci, c = j - ox * ci;
+      a.y_u8[(((size_t)slot * a.OH + (oy0 + oy)) * a.OW + (ox0 + ox)) * a.C + cbase + c] = outt[oy * P.irow + j];
+    }
+  }
+  if (a.y_f32) {                     // float32 NCHW [slot][C][OH][OW], mirrored per flips[n]
+    const int flip = a.flips ? a.flips[n] : 0;
+    const int per_ch = th * tw;
+    for (int idx = tid; idx < ci * per_ch; idx += IP_THREADS) {
+      const int c = idx / per_ch, rem = idx - c * per_ch;
+      const int oy = rem / tw, ox = rem - oy * tw;
+      const unsigned char v = outt[oy * P.irow + ox * ci + c];
+      const float f = ((float)v / 255.0f - a.mean[cbase + c]) / a.std[cbase + c];
+      const int dx = (flip & 1) ? a.OW - 1 - (ox0 + ox) : ox0 + ox;
+      const int dy = (flip & 2) ? a.OH - 1 - (oy0 + oy) : oy0 + oy;
+      a.y_f32[(((size_t)slot * a.C + cbase + c) * a.OH + dy) * a.OW + dx] = f;
+    }
+  }
+}
+
 // Pillow's kernel size of one axis: 2 * ceil(support) + 1 with support = max(in / out, 1)
 static int ip_ksize(int in, int out) {
   const double scale = (double)in / (double)out;
@@ -215,45 +268,13 @@ static int ip_span(int in, int out, int tile) {
 
 static inline int round4(int v) { return (v + 3) & ~3; }
 
-}  // namespace pd
-
-using namespace pd;
-
-extern "C" int pd_image_preprocess(const pd_image_preprocess_args* a, void* stream) {
-  PD_CHECK(a != nullptr && a->x && (a->y_f32 || a->y_u8), PD_ERR_ARG, "pd_image_preprocess: null pointer (x, and at least one of y_f32 / y_u8)");
-  PD_CHECK(a->Cin == 1 || a->Cin == 3, PD_ERR_ARG, "pd_image_preprocess: Cin must be 1 or 3 (got %d)", a->Cin);
-  PD_CHECK(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0 && a->out_slots > 0, PD_ERR_SHAPE,
-           "pd_image_preprocess: N, H, W, OH, OW and out_slots must be positive");
-  PD_CHECK((long long)a->H <= 32ll * a->OH && (long long)a->W <= 32ll * a->OW, PD_ERR_SHAPE,
-           "pd_image_preprocess: down-scale factor above 32 (%d x %d -> %d x %d)", a->H, a->W, a->OH, a->OW);
-  PD_CHECK(a->pixel_stride >= a->Cin && a->pixel_stride <= 8, PD_ERR_SHAPE, "pd_image_preprocess: pixel_stride must be in [Cin, 8]");
-  const long long row_bytes = (long long)a->W * a->pixel_stride;
-  PD_CHECK(a->row_stride >= row_bytes, PD_ERR_SHAPE, "pd_image_preprocess: row_stride smaller than W * pixel_stride");
-  const long long image_bytes = (long long)(a->H - 1) * a->row_stride + row_bytes;
-  const long long istride = a->N == 1 ? 0 : a->image_stride;       // (not read for a single image)
-  PD_CHECK(a->N == 1 || istride >= image_bytes, PD_ERR_SHAPE, "pd_image_preprocess: image_stride smaller than one image");
-  PD_CHECK(a->row_stride < (1ll << 32) && image_bytes < (1ll << 32) && istride < (1ll << 32) &&
-               (long long)(a->N - 1) * istride + image_bytes < (1ll << 32),
-           PD_ERR_SHAPE, "pd_image_preprocess: source beyond 32-bit byte offsets in one launch");
-  const long long out_elems = (long long)a->out_slots * 3 * a->OH * a->OW;
-  PD_CHECK((long long)a->OH * a->OW < (1ll << 30) && out_elems * (a->y_f32 ? 4 : 1) < (1ll << 32), PD_ERR_SHAPE,
-           "pd_image_preprocess: output beyond 32-bit byte offsets in one launch");
-  const bool rx = a->W != a->OW, ry = a->H != a->OH;
-  PD_CHECK((!rx || (a->coef_x && a->bounds_x)) && (!ry || (a->coef_y && a->bounds_y)), PD_ERR_ARG,
-           "pd_image_preprocess: null table of a resized axis");
-  PD_CHECK((!rx || (a->ksize_x == ip_ksize(a->W, a->OW) && a->ksize_x <= IP_MAX_KSIZE)) &&
-               (!ry || (a->ksize_y == ip_ksize(a->H, a->OH) && a->ksize_y <= IP_MAX_KSIZE)),
-           PD_ERR_SHAPE, "pd_image_preprocess: ksize must be 2 * ceil(max(in / out, 1)) + 1");
-  const int tiles_x = (a->OW + IP_TOW - 1) / IP_TOW, tiles_y = (a->OH + IP_TOH - 1) / IP_TOH;
-  PD_CHECK(a->N <= 65535 && tiles_y <= 65535, PD_ERR_SHAPE, "pd_image_preprocess: more than 65535 images or row tiles in one launch");
-
+// The LDS layout of a workgroup that carries `ci` channels per pixel; false when it does not fit the 64 KiB ceiling.
+static bool ip_make_plan(int H, int W, int OH, int OW, int pixel_stride, int ci, int kx, int ky, ip_plan* out) {
   ip_plan P;
-  const int ci = a->Cin;
-  P.span_x = ip_span(a->W, a->OW, IP_TOW);
-  P.span_y = ip_span(a->H, a->OH, IP_TOH);
-  P.lrow = round4(P.span_x * a->pixel_stride + 4);
+  P.span_x = ip_span(W, OW, IP_TOW);
+  P.span_y = ip_span(H, OH, IP_TOH);
+  P.lrow = round4(P.span_x * pixel_stride + 4);
   P.irow = round4(IP_TOW * ci);
-  const int kx = rx ? a->ksize_x : 0, ky = ry ? a->ksize_y : 0;
   P.off_cy = IP_TOW * kx * 4;
   P.off_bnd = P.off_cy + IP_TOH * ky * 4;
   P.off_inter = P.off_bnd + (IP_TOW + IP_TOH) * 2 * 4;
@@ -263,15 +284,87 @@ extern "C" int pd_image_preprocess(const pd_image_preprocess_args* a, void* stre
   if (R < 4) R = (IP_LDS_MAX - P.off_stage) / P.lrow;
   if (R > 64) R = 64;
   if (R > P.span_y) R = P.span_y;
-  PD_CHECK(R >= 1, PD_ERR_SHAPE, "pd_image_preprocess: tile does not fit the LDS budget");
+  if (R < 1) return false;
   P.chunk_rows = R;
   P.lds_bytes = P.off_stage + R * P.lrow;
-  PD_CHECK(P.lds_bytes <= IP_LDS_MAX, PD_ERR_SHAPE, "pd_image_preprocess: tile does not fit the LDS budget");
+  if (P.lds_bytes > IP_LDS_MAX) return false;
+  *out = P;
+  return true;
+}
 
-  const dim3 grid((unsigned)tiles_x, (unsigned)tiles_y, (unsigned)a->N);
+// The refusals the two entry points share (`A`: either args struct; `cin`: channels read per pixel, `cout`: channels written per pixel).
+template <typename A>
+static int ip_check(const A* a, const char* name, const char* cname, int cin, int cout, int max_pixel_stride) {
+  PD_CHECK(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0 && a->out_slots > 0, PD_ERR_SHAPE,
+           "%s: N, H, W, OH, OW and out_slots must be positive", name);
+  PD_CHECK((long long)a->H <= 32ll * a->OH && (long long)a->W <= 32ll * a->OW, PD_ERR_SHAPE,
+           "%s: down-scale factor above 32 (%d x %d -> %d x %d)", name, a->H, a->W, a->OH, a->OW);
+  PD_CHECK(a->pixel_stride >= cin && a->pixel_stride <= max_pixel_stride, PD_ERR_SHAPE, "%s: pixel_stride must be in [%s, %d]", name, cname,
+           max_pixel_stride);
+  const long long row_bytes = (long long)a->W * a->pixel_stride;
+  PD_CHECK(a->row_stride >= row_bytes, PD_ERR_SHAPE, "%s: row_stride smaller than W * pixel_stride", name);
+  const long long image_bytes = (long long)(a->H - 1) * a->row_stride + row_bytes;
+  const long long istride = a->N == 1 ? 0 : a->image_stride;       // (not read for a single image)
+  PD_CHECK(a->N == 1 || istride >= image_bytes, PD_ERR_SHAPE, "%s: image_stride smaller than one image", name);
+  PD_CHECK(a->row_stride < (1ll << 32) && image_bytes < (1ll << 32) && istride < (1ll << 32) &&
+               (long long)(a->N - 1) * istride + image_bytes < (1ll << 32),
+           PD_ERR_SHAPE, "%s: source beyond 32-bit byte offsets in one launch", name);
+  const long long out_elems = (long long)a->out_slots * cout * a->OH * a->OW;
+  PD_CHECK((long long)a->OH * a->OW < (1ll << 30) && out_elems * (a->y_f32 ? 4 : 1) < (1ll << 32), PD_ERR_SHAPE,
+           "%s: output beyond 32-bit byte offsets in one launch", name);
+  const bool rx = a->W != a->OW, ry = a->H != a->OH;
+  PD_CHECK((!rx || (a->coef_x && a->bounds_x)) && (!ry || (a->coef_y && a->bounds_y)), PD_ERR_ARG, "%s: null table of a resized axis", name);
+  PD_CHECK((!rx || (a->ksize_x == ip_ksize(a->W, a->OW) && a->ksize_x <= IP_MAX_KSIZE)) &&
+               (!ry || (a->ksize_y == ip_ksize(a->H, a->OH) && a->ksize_y <= IP_MAX_KSIZE)),
+           PD_ERR_SHAPE, "%s: ksize must be 2 * ceil(max(in / out, 1)) + 1", name);
+  PD_CHECK(a->N <= 65535 && (a->OH + IP_TOH - 1) / IP_TOH <= 65535, PD_ERR_SHAPE, "%s: more than 65535 images or row tiles in one launch", name);
+  return PD_OK;
+}
+
+}  // namespace pd
+
+using namespace pd;
+
+extern "C" int pd_image_preprocess(const pd_image_preprocess_args* a, void* stream) {
+  PD_CHECK(a != nullptr && a->x && (a->y_f32 || a->y_u8), PD_ERR_ARG, "pd_image_preprocess: null pointer (x, and at least one of y_f32 / y_u8)");
+  PD_CHECK(a->Cin == 1 || a->Cin == 3, PD_ERR_ARG, "pd_image_preprocess: Cin must be 1 or 3 (got %d)", a->Cin);
+  const int rc = ip_check(a, "pd_image_preprocess", "Cin", a->Cin, 3, 8);
+  if (rc != PD_OK) return rc;
+  const bool rx = a->W != a->OW, ry = a->H != a->OH;
+  ip_plan P;
+  PD_CHECK(ip_make_plan(a->H, a->W, a->OH, a->OW, a->pixel_stride, a->Cin, rx ? a->ksize_x : 0, ry ? a->ksize_y : 0, &P), PD_ERR_SHAPE,
+           "pd_image_preprocess: tile does not fit the LDS budget");
+  const dim3 grid((unsigned)((a->OW + IP_TOW - 1) / IP_TOW), (unsigned)((a->OH + IP_TOH - 1) / IP_TOH), (unsigned)a->N);
   hipStream_t st = (hipStream_t)stream;
-  if (ci == 3) hipLaunchKernelGGL(image_preprocess_kernel<3>, grid, dim3(IP_THREADS), P.lds_bytes, st, *a, P);
+  if (a->Cin == 3) hipLaunchKernelGGL(image_preprocess_kernel<3>, grid, dim3(IP_THREADS), P.lds_bytes, st, *a, P);
   else hipLaunchKernelGGL(image_preprocess_kernel<1>, grid, dim3(IP_THREADS), P.lds_bytes, st, *a, P);
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
+
+extern "C" int pd_image_preprocess_bands(const pd_image_preprocess_bands_args* a, void* stream) {
+  PD_CHECK(a != nullptr && a->x && (a->y_f32 || a->y_u8), PD_ERR_ARG,
+           "pd_image_preprocess_bands: null pointer (x, and at least one of y_f32 / y_u8)");
+  PD_CHECK(a->C >= 1 && a->C <= 32, PD_ERR_ARG, "pd_image_preprocess_bands: C must be in 1..32 (got %d)", a->C);
+  PD_CHECK(!a->y_f32 || (a->mean && a->std), PD_ERR_ARG, "pd_image_preprocess_bands: null mean / std (fp32 [C]) with y_f32");
+  const int rc = ip_check(a, "pd_image_preprocess_bands", "C", a->C, a->C, 64);
+  if (rc != PD_OK) return rc;
+  const bool rx = a->W != a->OW, ry = a->H != a->OH;
+  const int kx = rx ? a->ksize_x : 0, ky = ry ? a->ksize_y : 0;
+  // the widest band group whose workgroup keeps the 40 KiB target with chunks of >= 4 rows; failing that, the widest one that fits at all
+  ip_plan P;
+  int cg = 0;
+  for (int c = a->C; c >= 1 && !cg; --c)
+    if (ip_make_plan(a->H, a->W, a->OH, a->OW, a->pixel_stride, c, kx, ky, &P) && P.lds_bytes <= IP_LDS_TARGET && P.chunk_rows >= (P.span_y < 4 ? P.span_y : 4))
+      cg = c;
+  for (int c = a->C; c >= 1 && !cg; --c)
+    if (ip_make_plan(a->H, a->W, a->OH, a->OW, a->pixel_stride, c, kx, ky, &P)) cg = c;
+  PD_CHECK(cg > 0, PD_ERR_SHAPE, "pd_image_preprocess_bands: tile does not fit the LDS budget");
+  const int groups = (a->C + cg - 1) / cg;
+  PD_CHECK((long long)a->N * groups <= 65535, PD_ERR_SHAPE, "pd_image_preprocess_bands: more than 65535 (image, band group) pairs in one launch");
+  const dim3 grid((unsigned)((a->OW + IP_TOW - 1) / IP_TOW), (unsigned)((a->OH + IP_TOH - 1) / IP_TOH), (unsigned)(a->N * groups));
+  hipLaunchKernelGGL(image_preprocess_bands_kernel, grid, dim3(IP_THREADS), P.lds_bytes, (hipStream_t)stream, *a, P, cg, groups);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+

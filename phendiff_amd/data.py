@@ -26,6 +26,8 @@ from . import _lib as L
 
 PRECISION_BITS = 32 - 8 - 2          # Pillow's 8-bit resample: 22-bit fixed-point coefficients
 MAX_DOWNSCALE = 32                   # per axis; pd_image_preprocess refuses more (ksize <= 65)
+MAX_BANDS = 32                       # pd_image_preprocess_bands: bands per pixel (what the pixel UNet's conv_in takes)
+MAX_BAND_PIXEL_STRIDE = 64           # ... and the widest pixel stride it reads in place
 
 
 def resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -87,8 +89,8 @@ def draw_flips(n: int, generator: Optional[torch.Generator] = None, p: float = 0
 class _Plan:
     """Device tables of one (H, W) -> (OH, OW) resize and the argument struct that carries them."""
 
-    def __init__(self, H, W, OH, OW, device):
-        self.args = L.ImagePreprocessArgs(H=H, W=W, OH=OH, OW=OW)
+    def __init__(self, H, W, OH, OW, device, bands=False):
+        self.args = (L.ImagePreprocessBandsArgs if bands else L.ImagePreprocessArgs)(H=H, W=W, OH=OH, OW=OW)
         self.keep = []
         for axis, (i, o) in (("x", (W, OW)), ("y", (H, OH))):
             if i == o:
@@ -101,8 +103,11 @@ class _Plan:
             setattr(self.args, f"ksize_{axis}", coef.shape[1])
 
 
-def _as_uint8_array(img):
-    """One image of a list -> a uint8 torch tensor (H, W) or (H, W, 1 | 3 | 4); PIL images of other modes go through convert("RGB")."""
+def _as_uint8_array(img, channels=None):
+    """One image of a list -> a uint8 torch tensor (H, W) or (H, W, 1 | 3 | 4); PIL images of other modes go through convert("RGB").
+    ``channels``: a band stack instead, (H, W, channels) (or (H, W) for one band); PIL holds no such image and is refused."""
+    if channels is not None and hasattr(img, "mode") and hasattr(img, "convert"):
+        raise TypeError(f"images: a {channels}-band stack is a uint8 tensor or array (H, W, {channels}), not a PIL image")
     if isinstance(img, torch.Tensor):
         t = img
     elif isinstance(img, np.ndarray):
@@ -115,6 +120,10 @@ def _as_uint8_array(img):
         raise TypeError(f"images: expected uint8 tensors, arrays or PIL images, got {type(img).__name__}")
     if t.dtype != torch.uint8:
         raise TypeError(f"images must be uint8, got {t.dtype}")
+    if channels is not None:
+        if not ((t.dim() == 3 and t.shape[2] == channels) or (t.dim() == 2 and channels == 1)):
+            raise ValueError(f"an image must have shape (H, W, {channels}), got {tuple(t.shape)}")
+        return t
     if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] not in (1, 3, 4)):
         raise ValueError(f"an image must have shape (H, W) or (H, W, 1 | 3 | 4), got {tuple(t.shape)}")
     return t
@@ -126,6 +135,12 @@ class ImagePreprocessor:
     definition            ``(h, w)``, or an ``int``: the short edge, aspect ratio kept (:func:`resized_output_size`)
     mean, std             a float or three floats (per channel)
     data_aug_on_the_fly   draw flip codes with :func:`draw_flips` when ``__call__`` gets none
+    channels              None: RGB output as described below.  ``C`` in 1..32: a stack of C independent bands (Cell Painting stains,
+                          multiplexed immunofluorescence) through ``pd_image_preprocess_bands`` -- C bands in, C bands out, each resampled
+                          as a mode-L image.  ``images`` is then a uint8 ``(N, H, W, C)`` tensor / array (``(N, H, W)`` for C = 1) or a
+                          list of ``(H, W, C)`` items (no PIL images), ``mean`` / ``std`` take one value or C, and the outputs are
+                          ``(n, C, OH, OW)`` and, with ``return_raw``, ``(n, OH, OW, C)``.  Flips, slots, strided device views and
+                          capture work as without it.
 
     ``__call__(images, flips=None, generator=None, return_raw=False)`` returns the float32 NCHW tensor, or with ``return_raw`` the pair
     ``(tensor, raw)`` where ``raw`` is the resized uint8 NHWC batch (never flipped: the reference's raw twin has no flips) in the layout
@@ -136,7 +151,7 @@ class ImagePreprocessor:
     device-resident ``images`` and ``flips`` the call enqueues nothing but the kernel, so it can be captured in a graph once the plan of its
     shape exists (call once before capturing)."""
 
-    def __init__(self, definition, mean=0.5, std=0.5, data_aug_on_the_fly: bool = False, device="cuda:0"):
+    def __init__(self, definition, mean=0.5, std=0.5, data_aug_on_the_fly: bool = False, device="cuda:0", channels: Optional[int] = None):
         if isinstance(definition, (int, np.integer)):
             self.definition = int(definition)
         else:
@@ -145,7 +160,12 @@ class ImagePreprocessor:
                 self.definition = self.definition[0]
             elif len(self.definition) != 2:
                 raise ValueError(f"definition must be an int or (h, w), got {definition}")
-        self.mean, self.std = self._three(mean, "mean"), self._three(std, "std")
+        if channels is not None and not (isinstance(channels, (int, np.integer)) and 1 <= channels <= MAX_BANDS):
+            raise ValueError(f"channels must be None or an int in 1..{MAX_BANDS}, got {channels}")
+        self.channels = None if channels is None else int(channels)
+        k = self.channels or 3
+        self.mean, self.std = self._per_channel(mean, "mean", k), self._per_channel(std, "std", k)
+        self._mean_std = None      # (device fp32 [C], device fp32 [C]) of the band entry, built on first use
         if any(s == 0.0 for s in self.std):
             raise ValueError("std must be non-zero")
         self.data_aug_on_the_fly = bool(data_aug_on_the_fly)
@@ -153,16 +173,16 @@ class ImagePreprocessor:
         self._plans = {}
 
     @staticmethod
-    def _three(v, what):
+    def _per_channel(v, what, k):
         if isinstance(v, torch.Tensor):
             v = v.flatten().tolist()
         if isinstance(v, (int, float)):
             v = [v]
         v = [float(x) for x in v]
         if len(v) == 1:
-            v = v * 3
-        if len(v) != 3:
-            raise ValueError(f"{what}: one value or three, got {len(v)}")
+            v = v * k
+        if len(v) != k:
+            raise ValueError(f"{what}: one value or {'three' if k == 3 else k}, got {len(v)}")
         return v
 
     # ---- input handling --------------------------------------------------------------------------------------------------------------
@@ -172,12 +192,16 @@ class ImagePreprocessor:
             t = torch.from_numpy(images) if isinstance(images, np.ndarray) else images
             if t.dtype != torch.uint8:
                 raise TypeError(f"images must be uint8, got {t.dtype}")
-            if t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[3] not in (1, 3, 4)):
+            ch = self.channels
+            if ch is not None:
+                if not ((t.dim() == 4 and t.shape[3] == ch) or (t.dim() == 3 and ch == 1)):
+                    raise ValueError(f"images must have shape (N, H, W, {ch}) with channels={ch}, got {tuple(t.shape)}")
+            elif t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[3] not in (1, 3, 4)):
                 raise ValueError(f"images must have shape (N, H, W) or (N, H, W, 1 | 3 | 4), got {tuple(t.shape)}")
             if t.shape[0] == 0:
                 raise ValueError("images: empty batch")
             return t.shape[0], [(t, None)]
-        items = [_as_uint8_array(i) for i in images]
+        items = [_as_uint8_array(i, self.channels) for i in images]
         if not items:
             raise ValueError("images: empty list")
         by_shape = {}
@@ -196,7 +220,7 @@ class ImagePreprocessor:
         key = (H, W, OH, OW)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = _Plan(H, W, OH, OW, self.device)
+            plan = self._plans[key] = _Plan(H, W, OH, OW, self.device, bands=self.channels is not None)
         return plan
 
     def _strided(self, t):
@@ -206,9 +230,9 @@ class ImagePreprocessor:
         if t.dim() == 3:
             t = t.unsqueeze(3)
         n, h, w, c = t.shape
-        cin = 1 if c == 1 else 3
+        cin = self.channels or (1 if c == 1 else 3)
         s = t.stride()
-        ok = (c == 1 or s[3] == 1) and cin <= s[2] <= 8 and s[1] >= w * s[2] and (n == 1 or s[0] >= (h - 1) * s[1] + w * s[2])
+        ok = (c == 1 or s[3] == 1) and cin <= s[2] <= (8 if self.channels is None else MAX_BAND_PIXEL_STRIDE) and s[1] >= w * s[2] and (n == 1 or s[0] >= (h - 1) * s[1] + w * s[2])
         if not ok:
             t = t.contiguous()
             s = t.stride()
@@ -238,8 +262,13 @@ class ImagePreprocessor:
         dev = self.device
         if flips is not None:
             flips = flips.to(dev).contiguous()
-        y = torch.empty((n, 3, OH, OW), dtype=torch.float32, device=dev)
-        raw = torch.empty((n, OH, OW, 3), dtype=torch.uint8, device=dev) if return_raw else None
+        bands = self.channels is not None
+        cout = self.channels or 3
+        if bands and self._mean_std is None:
+            self._mean_std = (torch.tensor(self.mean, dtype=torch.float32, device=dev), torch.tensor(self.std, dtype=torch.float32, device=dev))
+        fn, what = (lib.pd_image_preprocess_bands, "pd_image_preprocess_bands") if bands else (lib.pd_image_preprocess, "pd_image_preprocess")
+        y = torch.empty((n, cout, OH, OW), dtype=torch.float32, device=dev)
+        raw = torch.empty((n, OH, OW, cout), dtype=torch.uint8, device=dev) if return_raw else None
         keep = []
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
@@ -247,7 +276,12 @@ class ImagePreprocessor:
                 t, s_img, s_row, s_pix, cin = self._strided(batch)
                 plan = self._plan(t.shape[1], t.shape[2], OH, OW)
                 a = plan.args
-                a.N, a.Cin, a.out_slots = t.shape[0], cin, n
+                a.N, a.out_slots = t.shape[0], n
+                if bands:
+                    a.C, a.mean, a.std = cin, self._mean_std[0].data_ptr(), self._mean_std[1].data_ptr()
+                else:
+                    a.Cin = cin
+                    (a.mean0, a.mean1, a.mean2), (a.std0, a.std1, a.std2) = self.mean, self.std
                 a.image_stride, a.row_stride, a.pixel_stride = s_img, s_row, s_pix
                 a.x = t.data_ptr()
                 a.out_index = a.flips = None
@@ -259,9 +293,16 @@ class ImagePreprocessor:
                     f = flips if slots is None else flips[torch.tensor(slots, device=dev)]
                     a.flips = f.data_ptr()
                     keep.append(f)
-                (a.mean0, a.mean1, a.mean2), (a.std0, a.std1, a.std2) = self.mean, self.std
                 a.y_f32, a.y_u8 = y.data_ptr(), L.ptr(raw)
-                L.check(lib.pd_image_preprocess(C.byref(a), st), "pd_image_preprocess")
+                rc = fn(C.byref(a), st)
+                if rc == L.PD_ERR_SHAPE and bands and s_pix > cin:
+                    # a view into wider pixels stages whole source rows at ITS pixel stride; under a steep horizontal down-scale such a
+                    # row may not fit the LDS budget where the same bands, dense, do (refused before launch): read a dense copy instead
+                    t = t.contiguous()
+                    a.image_stride, a.row_stride, a.pixel_stride = t.stride()[:3]
+                    a.x = t.data_ptr()
+                    rc = fn(C.byref(a), st)
+                L.check(rc, what)
                 keep.append(t)
         del keep            # temporaries were allocated on the launch stream: the allocator reuses them only behind the kernel
         return (y, raw) if return_raw else y

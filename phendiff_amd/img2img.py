@@ -19,7 +19,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib as L
-from .pipeline import ConditionalDDIMPipeline
+from .pipeline import ConditionalDDIMPipeline, require_pil_channels
 from .schedulers import DDIMInverseScheduler, randn_tensor
 
 
@@ -70,6 +70,7 @@ def ddib(pipe, clean_images, orig_class_labels, target_class_labels, num_inferen
     if isinstance(pipe, CustomStableDiffusionImg2ImgPipeline):
         clean_images, [orig_class_cond] = LDM_preprocess(pipe, clean_images, [orig_class_labels], generator)
     elif isinstance(pipe, ConditionalDDIMPipeline):
+        require_pil_channels(clean_images.shape[1], output_type)      # (before the inversion: half of the trajectory)
         orig_class_cond = orig_class_labels
     else:
         raise NotImplementedError(type(pipe))
@@ -207,6 +208,8 @@ def linear_interp_custom_guidance_inverted_start(pipe, clean_images, orig_class_
     from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
     ldm = isinstance(pipe, CustomStableDiffusionImg2ImgPipeline)
     target_cond = target_class_labels
+    if not ldm:
+        require_pil_channels(clean_images.shape[1], output_type)
     if ldm:      # :663-671: images -> latents, both label tensors -> 77-token class embeddings
         clean_images, (orig_class_labels, target_cond) = LDM_preprocess(pipe, clean_images, [orig_class_labels, target_class_labels], generator)
     inverted = inversion(pipe, clean_images, orig_class_labels, num_inference_steps, None, variant)

@@ -36,6 +36,12 @@ def numpy_to_pil(images: np.ndarray):
     return [Image.fromarray(im) for im in images]
 
 
+def require_pil_channels(channels: int, output_type: Optional[str]) -> None:
+    """PIL holds 1 (L), 3 (RGB) or 4 (RGBA) bands: refuse ``output_type="pil"`` for any other count before work is spent."""
+    if output_type == "pil" and channels not in (1, 3, 4):
+        raise ValueError(f'output_type="pil" cannot hold {channels}-channel images (PIL takes 1, 3 or 4): pass output_type="numpy"')
+
+
 class ConditionalDDIMPipeline:
     def __init__(self, unet, scheduler):
         # pipeline_conditionial_ddim.py:44-47: always converted to a DDIM scheduler
@@ -121,6 +127,7 @@ class ConditionalDDIMPipeline:
                  add_forward_noise_to_image: bool = True, frac_diffusion_skipped: Optional[float] = None,
                  guidance_eqn: Literal["imagen", "CFG"] = "imagen") -> Union[ImagePipelineOutput, Tuple]:
         self.check_inputs(class_labels, class_emb, w, generator, frac_diffusion_skipped, start_image)
+        require_pil_channels(self.unet.config.in_channels, output_type)
         if num_inference_steps is None:
             num_inference_steps = DEFAULT_NUM_INFERENCE_STEPS
         if guidance_eqn not in ("imagen", "CFG"):

@@ -26,6 +26,9 @@ from .weight_layout import WeightSet
 # fp16 storage + MFMA, fp32 accumulate / statistics / softmax; since round 5 it trains too (unet_train.UNetTrainer under training.LossScaler)
 _DT = {"f32": (L.PD_F32, torch.float32), "bf16": (L.PD_BF16, torch.bfloat16), "fp16": (L.PD_F16, torch.float16)}
 
+IM2COL_MAX_CHANNELS = 3     # conv_in over up to this many channels is the im2col form (9 C taps in 32 virtual channels)
+MAX_IMAGE_CHANNELS = 32     # above it: the NHWC buffer zero-padded to this many channels, then a plain 3x3 pd_conv
+
 
 class UNet2DOutput(SimpleNamespace):
     """``diffusers.models.unet_2d.UNet2DOutput`` stand-in: ``.sample``."""
@@ -157,6 +160,11 @@ class CustomCondUNet2DModel(nn.Module):
             raise NotImplementedError("block_out_channels must be multiples of 32 on the HIP path")
         if compute_dtype not in _DT:
             raise ValueError("compute_dtype must be 'bf16', 'fp16' or 'f32'")
+        # conv_in reads <= 3 channels through the im2col form and 4..32 through a 32-channel zero-padded NHWC buffer; conv_out
+        # writes one 32-lane output tile
+        for key in ("in_channels", "out_channels"):
+            if not 1 <= getattr(c, key) <= MAX_IMAGE_CHANNELS:
+                raise NotImplementedError(f"{key} = {getattr(c, key)}: the HIP path takes 1..{MAX_IMAGE_CHANNELS} image channels")
         self.compute_dtype = compute_dtype
         self.sample_size = c.sample_size
         tdim = boc[0] * 4
@@ -312,7 +320,9 @@ class CustomCondUNet2DModel(nn.Module):
         cemb = class_emb.to(device=dev, dtype=torch.float32).contiguous() if class_emb is not None else None
         stream = torch.cuda.current_stream(dev).cuda_stream
         temb = plan.temb_rows(ts, labels, cemb, stream)
-        out = torch.empty_like(x)
+        if x.shape[1] != self.config.in_channels:
+            raise ValueError(f"sample has {x.shape[1]} channels, the model takes in_channels = {self.config.in_channels}")
+        out = torch.empty((B, self.config.out_channels, x.shape[2], x.shape[3]), dtype=torch.float32, device=dev)
         plan.run(x.data_ptr(), temb.data_ptr(), out.data_ptr(), stream)
         plan.keepalive = (x, ts, labels, cemb)
         if not return_dict:
@@ -354,7 +364,13 @@ class _PackedWeights(WeightSet):
         super().__init__(device, tdt)
         f32 = self.f32
         self.conv_in_w, self.conv_in_b = f32(m.conv_in.weight), f32(m.conv_in.bias)
-        self.conv_in_wv = self.im2col_conv_in(m.conv_in)
+        # one of the two forms exists (the other attribute is None): im2col for <= 3 channels, else the weight zero-padded to 32 input
+        # channels -- its bias is conv_in_b, the parameter itself
+        self.conv_in_wv = self.conv_in_wp = None
+        if m.conv_in.weight.shape[1] <= IM2COL_MAX_CHANNELS:
+            self.conv_in_wv = self.im2col_conv_in(m.conv_in)
+        else:
+            self.conv_in_wp, _ = self.padded(m.conv_in, m.conv_in.weight.shape[0], MAX_IMAGE_CHANNELS)
         self.time_mlp_and_conv_out(m)
         self.class_table = f32(m.class_embedding.weight) if isinstance(m.class_embedding, nn.Embedding) else None
         # class_embed_type: "timestep" = a second TimestepEmbedding over the sinusoid of the labels; "identity" = rows given as is
@@ -719,7 +735,7 @@ class UNetPlan:
                                     num_classes=(c.num_class_embeds or 0), w1=w.w1T.data_ptr(), b1=w.b1.data_ptr(),
                                     w2=w.w2T.data_ptr(), b2=w.b2.data_ptr(), class_table=L.ptr(w.class_table),
                                     wp=w.wpT.data_ptr(), bp=w.bp.data_ptr())
-        # conv_in (cond_unet_2d.py:127-129,313): NCHW fp32 sample -> NHWC, MFMA 1x1 conv over 32 im2col channels
+        # conv_in (cond_unet_2d.py:127-129,313), up to 3 channels: NCHW fp32 sample -> NHWC, MFMA 1x1 conv over 32 im2col channels
         self._in_field = "x0"
         centered = None
         if c.center_input_sample:      # cond_unet_2d.py:272-273: sample = 2 * sample - 1.0 (before conv_in's zero padding)
@@ -730,17 +746,31 @@ class UNetPlan:
             ca = L.AddNoiseArgs(numel=centered.numel(), per_sample=centered[0].numel(), velocity=0, x=None, noise=ones.data_ptr(),
                                 sa=two.data_ptr(), sb=neg.data_ptr(), out=centered.data_ptr())
             self._emit(self.lib.pd_add_noise, ca, "center", 0.0, 2.0 * centered.numel() * 4)
-        a0, conv_in_args = self._conv(None, None, w.conv_in_wv, w.conv_in_b, boc[0], ksize=1, pad=0,
-                                      im2col3=c.in_channels, src_shape=(B, H, W, 32))
-        if centered is not None:
-            conv_in_args.x0 = centered.data_ptr()
-            self._in_args, self._in_field = ca, "x"
+        if c.in_channels <= IM2COL_MAX_CHANNELS:
+            a0, conv_in_args = self._conv(None, None, w.conv_in_wv, w.conv_in_b, boc[0], ksize=1, pad=0,
+                                          im2col3=c.in_channels, src_shape=(B, H, W, 32))
+            if centered is not None:
+                conv_in_args.x0 = centered.data_ptr()
+                self._in_args, self._in_field = ca, "x"
+            else:
+                self._in_args = conv_in_args
+            self.tape.append(SimpleNamespace(kind="conv_in", out=a0))
         else:
-            self._in_args = conv_in_args
+            # 4..32 channels: NCHW fp32 -> NHWC zero-padded to 32 channels, then a plain 3x3 conv over zero-padded weights (the latent
+            # tier's conv_in).  The transpose writes all 32 channels on every run, so the padding holds zeros whatever the buffer held
+            xp = self._act(H, W, MAX_IMAGE_CHANNELS)
+            ta = L.NchwToNhwcArgs(dtype=self.code, B=B, C=c.in_channels, HW=H * W, Cpad=MAX_IMAGE_CHANNELS, x=None, out=xp.data_ptr())
+            self._emit(self.lib.pd_nchw_to_nhwc, ta, "nchw_to_nhwc", 0.0, B * H * W * c.in_channels * 4.0)
+            if centered is not None:
+                ta.x = centered.data_ptr()
+                self._in_args, self._in_field = ca, "x"
+            else:
+                self._in_args, self._in_field = ta, "x"
+            a0, _ = self._conv(xp, None, w.conv_in_wp, w.conv_in_b, boc[0])
+            self.tape.append(SimpleNamespace(kind="conv_in_padded", x=xp, out=a0))
         self.ops[-1].what = "conv_in"
         self.ops[-1].flops = 2.0 * B * H * W * boc[0] * c.in_channels * 9
         self.ops[-1].bytes = B * H * W * (c.in_channels * 4 + boc[0] * self._esz())
-        self.tape.append(SimpleNamespace(kind="conv_in", out=a0))
         h = a0
         skips = [a0]
         for i, blk in enumerate(m.down_blocks):

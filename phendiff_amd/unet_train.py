@@ -99,7 +99,8 @@ class TrainWeights(WeightSet):
                 self.samplers[name] = self.sampler(mod, phases=".upsamplers." in name)
         co, c0, ci = m.conv_out.weight.shape[0], m.conv_out.weight.shape[1], m.conv_in.weight.shape[1]
         self.conv_out_d = self.padded(m.conv_out, pad32(co), c0)      # 32 (3 real) output-gradient channels -> block_out_channels[0]
-        # conv_in's input gradient (the image gradient of the guided transfer): block_out_channels[0] -> 3 channels (pad 32)
+        # conv_in's input gradient (the image gradient of the guided transfer): block_out_channels[0] -> in_channels (pad 32), for the im2col
+        # and the padded conv_in alike
         self.conv_in_d = self.padded(m.conv_in, m.conv_in.weight.shape[0], pad32(ci))
 
 
@@ -498,7 +499,7 @@ class UNetTrainPlan(UNetPlan):
                 gx[1] = True
                 self._drop_fused_sums(gx[0])
                 self._emit(self.lib.pd_pool2x2_sum, a, "pool2x2", 0.0, du.numel() * self._esz() * 1.25)
-        elif k == "conv_in":
+        elif k in ("conv_in", "conv_in_padded"):
             dout = self._g(rec.out)[0]
             if self.input_grad:
                 self._conv(dout, None, tw.conv_in_d, self._zero_bias, c.in_channels, out_mode=L.PD_OUT_NCHW_F32,
@@ -512,7 +513,13 @@ class UNetTrainPlan(UNetPlan):
                     self._emit(self.lib.pd_add_noise, sa, "center_bwd", 0.0, 2.0 * self.dsample.numel() * 4)
             if not self.param_grads:
                 return
-            self._im2col_wgrad(dout, "conv_in")
+            if k == "conv_in":
+                self._im2col_wgrad(dout, "conv_in")
+            else:
+                # the 3x3 weight gradient over the padded NHWC buffer (already centred under center_input_sample); the pad channels'
+                # gradient is not written (cin_valid)
+                self._bias_grad(dout, "conv_in.bias")
+                self._wgrad(rec.x, None, None, 0, dout, "conv_in.weight", cin_valid=c.in_channels)
         else:
             raise NotImplementedError(f"backward of tape record {k!r}")
 
@@ -763,7 +770,10 @@ class _Repacker(Repacker):
         super().__init__(w.code, m.conv_in.weight.device)
         c0, ci = m.conv_in.weight.shape[:2]
         co, cc = m.conv_out.weight.shape[:2]
-        self.job(w.conv_in_wv, m.conv_in.weight, c0, ci * 9, 1, cin_pad=32)
+        if w.conv_in_wv is not None:
+            self.job(w.conv_in_wv, m.conv_in.weight, c0, ci * 9, 1, cin_pad=32)
+        else:             # (4..32 channels: the 3x3 weight zero-padded to 32 input channels; its dgrad copy is the job below)
+            self.job(w.conv_in_wp, m.conv_in.weight, c0, ci, 3, cin_pad=32)
         res = []
         for name, mod in m.named_modules():
             if isinstance(mod, _Resnet):
@@ -902,7 +912,7 @@ class UNetTrainer:
         labels = class_labels.to(device=self.device, dtype=torch.int64).contiguous() if class_labels is not None else None
         cemb = class_emb.to(device=self.device, dtype=torch.float32).contiguous() if class_emb is not None else None
         self._cond = labels is not None        # the class table has a gradient only when the labels went through it
-        out = torch.empty_like(x)
+        out = torch.empty((B, self.model.config.out_channels, H, W), dtype=torch.float32, device=x.device)
         plan.forward(x, ts, labels, cemb, out, st)
         loss, dout = self.loss_fn(out, clean, noise, timesteps, grad_scale=self.opt.scaler.scale if self.opt.scaler is not None else 1.0)
         plan.backward(dout, st, after_op=after_op)
