@@ -1,0 +1,667 @@
+"""The transfers of ``img2img.py`` as captured trajectories: one hipGraph per (method, batch shape), replayed per batch -- no host round trip,
+no Python launch cost (~120 launches x 2*S per batch otherwise).  Same arithmetic as the eager functions, bit for bit.
+
+  * :class:`_TrajectoryRunner` owns the mechanics: the runner's stream, one capture, one replay, ``join``, the graph's teardown;
+  * :class:`_PixelTrajectory` / :class:`_LatentTrajectory` name the phases of a trajectory in image space (``ConditionalDDIMPipeline``) and
+    in latent space (``CustomStableDiffusionImg2ImgPipeline``) once: their buffers and argument structs, and the launches of each phase;
+  * :class:`_ClassRows` (class conditioning of the pixel UNet) and :class:`_GuidedSteps` (the gradient-guided half) are phases both kinds use;
+  * the runners -- :class:`DDIBGraph`, :class:`CFGForwardStartGraph`, :class:`GuidedTransferGraph`, :class:`SDDDIBGraph`,
+    :class:`SDGuidedTransferGraph` -- say in ``_enqueue`` which phases they string together.
+
+Inside a capture every torch call is a device-to-device operation between pre-allocated buffers on the runner's stream; nothing allocates.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+from . import img2img as E
+from .img2img import GUIDANCE_MIN_GRAD_SCALE, _LpGuidance, _check_lp_exponent
+from .pipeline import ConditionalDDIMPipeline
+from .schedulers import DDIMInverseScheduler, randn_tensor
+
+
+def _identity_rows(cond: torch.Tensor, B: int, tdim: int, device) -> torch.Tensor:
+    """``class_embed_type="identity"``: a batch's conditioning IS its fp32 embedding rows -> (B, time_embed_dim)."""
+    rows = cond.to(device=device, dtype=torch.float32)
+    if rows.numel() != B * tdim:
+        raise ValueError(f"class_embed_type='identity': pass the (B, time_embed_dim) embedding rows, got {tuple(cond.shape)}")
+    return rows.view(B, tdim)
+
+
+class _ClassRows:
+    """Per-(step, image) class conditioning of a captured trajectory, for every ``class_embed_type`` (cond_unet_2d.py:146-153,
+    295-309).  The graph captures ONE ``pd_temb`` over all rows (+ one more for the class MLP of "timestep"); what changes between
+    replays is the CONTENT of static buffers, filled by ``fill`` on the runner's stream before the replay:
+      * nn.Embedding table (every shipped config) or no class conditioning: one int64 label per row;
+      * "identity": the rows ARE the fp32 embedding vectors, [rows][time_embed_dim];
+      * "timestep": the labels as fp32 go through the class MLP inside the graph (pre-allocated rows / scratch: a capture must not
+        allocate), whose output rows the main ``pd_temb`` adds."""
+
+    def __init__(self, plan, rows: int, device):
+        self.plan, self.rows = plan, rows
+        self.mode = getattr(plan.w, "class_mode", None)
+        tdim = plan.m.time_embed_dim
+        self.labels = torch.zeros((rows,), dtype=torch.int64, device=device) if self.mode is None else None
+        self.emb = torch.zeros((rows, tdim), dtype=torch.float32, device=device) if self.mode in ("identity", "timestep") else None
+        if self.mode == "timestep":
+            self.vals = torch.zeros((rows,), dtype=torch.float32, device=device)
+            self.scratch = torch.empty((rows, plan.w.proj_dim), dtype=torch.float32, device=device)
+
+    def fill(self, sl: slice, steps: int, B: int, cond: torch.Tensor):
+        """Rows ``sl`` (= ``steps`` x ``B``) <- the batch's conditioning repeated for every step."""
+        dev = self.plan.device
+        if self.mode is None:
+            self.labels[sl].view(steps, B).copy_(cond.to(device=dev, dtype=torch.int64).view(1, B).expand(steps, B))
+        elif self.mode == "identity":
+            self.emb[sl].view(steps, B, -1).copy_(_identity_rows(cond, B, self.emb.shape[1], dev).expand(steps, B, -1))
+        else:
+            self.vals[sl].view(steps, B).copy_(cond.to(device=dev, dtype=torch.float32).view(1, B).expand(steps, B))
+
+    def temb(self, ts_rows, st, out):
+        """The launches that turn the rows into the [rows][proj_dim] projection table (captured)."""
+        plan = self.plan
+        if self.mode == "timestep":
+            plan._class_rows_timestep(None, self.rows, st, emb=self.emb, scratch=self.scratch, vals=self.vals)
+        plan.temb_rows(ts_rows, self.labels, self.emb, st, rows=self.rows, out=out)
+
+
+def _sample_hw(unet, height, width):
+    ss = unet.config.sample_size
+    return height or (ss if isinstance(ss, int) else ss[0]), width or (ss if isinstance(ss, int) else ss[1])
+
+
+def _check_shape(what: torch.Tensor, static: torch.Tensor):
+    if tuple(what.shape) != tuple(static.shape):
+        raise ValueError(f"expected images of shape {tuple(static.shape)}, got {tuple(what.shape)}")
+
+
+def _schedules(pipe, S: int, variant: str, gen_timesteps=lambda fwd: fwd.timesteps, **set_kw):
+    """(inverse scheduler, the pipeline's forward scheduler, inversion timesteps, generation timesteps) at ``S`` steps: host tables, the
+    timesteps as Python ints.  ``gen_timesteps(fwd)``: the forward timesteps the method keeps (default: all of them)."""
+    inv = DDIMInverseScheduler.from_config(pipe.scheduler.config, variant=variant)
+    inv.set_timesteps(S)
+    fwd = pipe.scheduler
+    fwd.set_timesteps(S, **set_kw)
+    return inv, fwd, [int(t) for t in inv.timesteps], [int(t) for t in gen_timesteps(fwd)]
+
+
+class _TrajectoryRunner:
+    """What the captured trajectories share: the runner's stream, one capture, one replay, ``join`` and the graph's teardown.  A subclass
+    lays out its plan, static buffers and argument tables, then calls ``_capture()``; it supplies ``_enqueue(st)`` (the trajectory as
+    launches on ``st``, the runner's stream, which is also torch's current one) and ``_fill(*inputs)`` (a batch copied into the static
+    buffers, on the runner's stream)."""
+
+    def __init__(self, unet, batch_size: int, num_inference_steps: int, height, width, device, use_graph: bool, stream=None):
+        self.device = torch.device(device) if device is not None else unet.device
+        self.H, self.W = _sample_hw(unet, height, width)
+        self.B, self.S = batch_size, num_inference_steps
+        self.lib = L.lib()
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
+        self.graph = C.c_void_p(None)
+        self.use_graph = use_graph
+
+    def _capture(self):
+        if not self.use_graph:
+            return
+        st = self.stream.cuda_stream
+        torch.cuda.synchronize(self.device)
+        L.check(self.lib.pd_graph_begin(st), "pd_graph_begin")
+        try:
+            with torch.cuda.stream(self.stream):
+                self._enqueue(st)
+        finally:
+            rc = self.lib.pd_graph_end(st, C.byref(self.graph))
+        L.check(rc, "pd_graph_end")
+
+    @torch.no_grad()
+    def _replay(self, join: bool, *inputs):
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self._fill(*inputs)
+            self._launch()
+        return self.join() if join else self
+
+    def _launch(self):
+        """The trajectory once more over what the static buffers hold (on the runner's stream, which the caller made current)."""
+        if self.use_graph:
+            L.check(self.lib.pd_graph_launch(self.graph, self.stream.cuda_stream), "pd_graph_launch")
+        else:
+            self._enqueue(self.stream.cuda_stream)
+
+    def join(self):
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return self
+
+    def __del__(self):
+        try:
+            if self.graph:
+                self.lib.pd_graph_destroy(self.graph)
+        except Exception:
+            pass
+
+
+def _check_guided_request(pipe, pipe_type, p):
+    """What a guided runner refuses before it packs a weight or builds a plan."""
+    _check_lp_exponent(p)
+    if not isinstance(pipe, pipe_type):
+        raise NotImplementedError(f"{type(pipe).__name__}: this runner drives a {pipe_type.__name__}")
+    if pipe.unet.device.type != "cuda":
+        raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the pipeline to 'cuda'")
+
+
+class _GuidedSteps:
+    """The guided half of a captured trajectory: per step the input-gradient plan's forward, ``pd_lp_guidance`` (fp16:
+    ``pd_lp_guidance_scaled``), the plan's backward and ``pd_guided_step`` -- the launches of ``custom_guided_generation`` with its
+    per-step host decision moved to the device.  fp16: the gradient scale is a one-element device tensor the two kernels read and
+    ``overflow`` a device int ``pd_guided_step`` sets; :meth:`settle` reads it once per trajectory.
+
+    ``x``: the working buffer (updated in place), ``target``: the inverted start the Lp loss pulls towards, ``forward(i, ts, st)``: the
+    plan's forward of step ``i`` (``ts``: its (B,) timesteps) from ``x`` into ``model_out``."""
+
+    def __init__(self, lib, unet, plan, sched, timesteps, x, model_out, target, p, guidance_loss_scale, forward):
+        self.lib, self.plan, self.forward = lib, plan, forward
+        dev, B = x.device, x.shape[0]
+        self.fp16 = getattr(unet, "compute_dtype", None) == "fp16"
+        self.grad_scale = float(E.GUIDANCE_GRAD_SCALE) if self.fp16 else 1.0
+        self.scale_dev = torch.tensor([self.grad_scale], dtype=torch.float32, device=dev) if self.fp16 else None
+        self.overflow = torch.zeros((1,), dtype=torch.int32, device=dev) if self.fp16 else None
+        self.lp = lp = _LpGuidance(sched, x, model_out, target, p)
+        self.ts_rows = torch.tensor(timesteps, dtype=torch.float32).repeat_interleave(B).to(dev)
+        self.losses = torch.zeros((len(timesteps), B), dtype=torch.float32, device=dev)
+        self.lp_args = [lp.args(t, x, self.losses[i]) for i, t in enumerate(timesteps)]
+        self.step_args = []
+        for t in timesteps:
+            sa, sb, sap, dirc, _ = sched.step_coefficients(t)
+            self.step_args.append(L.GuidedStepArgs(use_clipped_model_output=0, sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc,
+                                                   guidance_scale=float(guidance_loss_scale), grad_scale=L.ptr(self.scale_dev),
+                                                   sample=x.data_ptr(), g_direct=lp.d_direct.data_ptr(), g_unet=plan.dsample.data_ptr(),
+                                                   model_out=model_out.data_ptr(), prev_sample=x.data_ptr(), pushed=None,
+                                                   overflow=L.ptr(self.overflow), **lp.common))
+        plan._side_streams(torch.cuda.current_stream(dev).cuda_stream)      # (anything the backward creates lazily exists before a capture)
+
+    def enqueue(self, st):
+        lib, B = self.lib, self.losses.shape[1]
+        for i, (lp, step) in enumerate(zip(self.lp_args, self.step_args)):
+            self.forward(i, self.ts_rows[i * B:(i + 1) * B], st)
+            if self.fp16:
+                L.check(lib.pd_lp_guidance_scaled(C.byref(lp), self.scale_dev.data_ptr(), st), "pd_lp_guidance_scaled")
+            else:
+                L.check(lib.pd_lp_guidance(C.byref(lp), st), "pd_lp_guidance")
+            # after_op given: the backward keeps every launch on `st` (one chain in the capture, no second stream)
+            self.plan.backward(self.lp.d_out, st, after_op={})
+            L.check(lib.pd_guided_step(C.byref(step), st), "pd_guided_step")
+
+    def reset(self):
+        if self.fp16:
+            self.overflow.zero_()
+
+    def settle(self, runner):
+        """fp16: the one host read of a trajectory.  A gradient that was not finite anywhere along it halves the scale and runs the whole
+        trajectory again from the inputs the runner kept (a step cannot be redone alone: the launches after it have already consumed
+        its result); the scale reached stays for the runs that follow."""
+        if not self.fp16:
+            return
+        with torch.cuda.stream(runner.stream):
+            while bool(self.overflow.item()):
+                if self.grad_scale * 0.5 < GUIDANCE_MIN_GRAD_SCALE:
+                    raise FloatingPointError("gradient-guided transfer (fp16): the UNet input gradient is not finite at any scale")
+                self.grad_scale *= 0.5
+                self.scale_dev.mul_(0.5)
+                self.overflow.zero_()
+                runner._launch()
+
+
+class _PixelTrajectory(_TrajectoryRunner):
+    """A trajectory in image space on one launch plan of the pixel UNet: the working buffer ``x`` (every step updates it in place),
+    ``model_out``, the image outputs with their ``pd_postproc``, and the phases the pixel runners enqueue.  ``input_grad``: also the
+    UNet's input-gradient plan (``gplan``: a guided half runs on it); ``keeps_input``: the batch stays in ``clean`` (the trajectory
+    starts from something made of it); ``inverts``: the trajectory leaves the end of an inversion in ``inverted``."""
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size, num_inference_steps, height, width, device, use_graph,
+                 private_plan=False, input_grad=False, keeps_input=False, inverts=False):
+        self.pipe = pipe
+        unet = pipe.unet
+        super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, H, W, dev = self.B, self.H, self.W, self.device
+        if B > unet.max_batch(H, W):
+            raise ValueError(f"batch_size {B} exceeds what one launch plan holds at {H}x{W} ({unet.max_batch(H, W)} images)")
+        self.plan = unet.new_plan(B, H, W, dev) if private_plan else unet.plan_for(B, H, W, dev)
+        self.gplan = unet.input_grad_plan(B, H, W, dev) if input_grad else None
+        # (both plans before any buffer: which freed block a later allocation reuses follows this order, and scripts/trajectory_signature.py
+        # compares the aliasing of pointers across revisions)
+        self.x = torch.empty((B, unet.config.in_channels, H, W), dtype=torch.float32, device=dev)
+        self.clean = torch.empty_like(self.x) if keeps_input else None
+        self.model_out = torch.empty_like(self.x)
+        self.inverted = torch.empty_like(self.x) if inverts else None
+        self._image_outputs()
+        self.post_args = L.PostprocArgs(B=B, C=self.x.shape[1], H=H, W=W, x=self.x.data_ptr(), out_f32=self.images.data_ptr(),
+                                        out_u8=self.images_u8.data_ptr())
+
+    def _image_outputs(self):
+        """``.images`` (NHWC float in [0, 1]) and ``.images_u8`` of the whole batch."""
+        shape = (self.B, self.H, self.W, self.pipe.unet.config.in_channels)
+        self.images = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self.images_u8 = torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def _class_table(self, timesteps):
+        """The static conditioning of a run of steps: per (step, image) row its timestep and class (``_fill`` writes the classes), and
+        the projection table ``temb`` one captured ``pd_temb`` makes of them."""
+        rows = len(timesteps) * self.B
+        self.ts_rows = torch.tensor(timesteps, dtype=torch.float32).repeat_interleave(self.B).to(self.device)
+        self.class_rows = _ClassRows(self.plan, rows, self.device)
+        self.temb = torch.empty((rows, self.plan.w.proj_dim), dtype=torch.float32, device=self.device)
+
+    def _inverted_snapshot(self):
+        """The device-to-device snapshot of ``x`` into ``inverted`` as one launch of the add_noise kernel: 1*x + 0*x."""
+        x = self.x
+        self._ones = torch.ones((self.B,), dtype=torch.float32, device=self.device)
+        self._zeros = torch.zeros((self.B,), dtype=torch.float32, device=self.device)
+        self.snapshot_args = L.AddNoiseArgs(numel=x.numel(), per_sample=x[0].numel(), velocity=0, x=x.data_ptr(), noise=x.data_ptr(),
+                                            sa=self._ones.data_ptr(), sb=self._zeros.data_ptr(), out=self.inverted.data_ptr())
+
+    def _snapshot(self, st):
+        L.check(self.lib.pd_add_noise(C.byref(self.snapshot_args), st), "pd_add_noise")
+
+    def _ddim_steps(self, st, step_args, first: int = 0, uncond=None):
+        """Per entry of ``step_args``: the UNet from ``x`` into ``model_out`` under row block ``first + i`` of ``temb``, then its
+        ``pd_ddim_step``.  ``uncond = (table, out)``: a second evaluation under the same row block of another table before the update."""
+        plan, step_bytes = self.plan, self.B * self.plan.w.proj_dim * 4
+        for i, a in enumerate(step_args, first):
+            plan.run(self.x.data_ptr(), self.temb.data_ptr() + i * step_bytes, self.model_out.data_ptr(), st)
+            if uncond is not None:
+                plan.run(self.x.data_ptr(), uncond[0].data_ptr() + i * step_bytes, uncond[1].data_ptr(), st)
+            L.check(self.lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
+
+    def _postproc(self, st):
+        L.check(self.lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
+
+
+class DDIBGraph(_PixelTrajectory):
+    """One hipGraph for the whole invert -> class-swap -> denoise trajectory of a batch.
+
+    ``run(images, orig_labels, target_labels)`` copies the batch into static buffers, replays the graph and
+    returns the float NHWC ``[0,1]`` images on the device (``.images``), the inverted latents (``.inverted``)
+    and optionally the uint8 quantisation."""
+
+    def __new__(cls, pipe, batch_size, num_inference_steps, height=None, width=None, *args, **kw):
+        if cls is DDIBGraph and batch_size > pipe.unet.max_batch(*_sample_hw(pipe.unet, height, width)):
+            cls = _SlicedDDIBGraph
+        return super().__new__(cls)
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, height: int = None,
+                 width: int = None, variant: str = "0.18.2", device=None, use_graph: bool = True, private_plan: bool = False):
+        super().__init__(pipe, batch_size, num_inference_steps, height, width, device, use_graph, private_plan, inverts=True)
+        # pipeline __call__ with frac_diffusion_skipped=0: timesteps <= N*(1-0) => all of them (:250-258)
+        self.inv, fwd, self.inv_ts, self.gen_ts = _schedules(
+            pipe, self.S, variant, lambda fwd: fwd.timesteps[fwd.timesteps <= fwd.config.num_train_timesteps * (1 - 0)])
+        self._class_table(self.inv_ts + self.gen_ts)
+        self.inv_args = [self.inv.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.inv_ts]
+        self.gen_args = [fwd.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.gen_ts]
+        self._inverted_snapshot()
+        self._capture()
+
+    def _enqueue(self, st):
+        self.class_rows.temb(self.ts_rows, st, self.temb)
+        self._ddim_steps(st, self.inv_args)
+        self._snapshot(st)
+        self._ddim_steps(st, self.gen_args, first=len(self.inv_args))
+        self._postproc(st)
+
+    def _fill(self, clean_images, orig_class_labels, target_class_labels):
+        B, n_inv, n_gen = self.B, len(self.inv_ts), len(self.gen_ts)
+        self.x.copy_(clean_images, non_blocking=True)
+        self.class_rows.fill(slice(0, n_inv * B), n_inv, B, orig_class_labels)
+        self.class_rows.fill(slice(n_inv * B, (n_inv + n_gen) * B), n_gen, B, target_class_labels)
+
+    def run(self, clean_images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor,
+            join: bool = True):
+        """``join=False`` leaves the caller's stream un-joined (call ``self.join()`` before reading the outputs), so several
+        runners can replay concurrently on their own streams."""
+        _check_shape(clean_images, self.x)
+        return self._replay(join, clean_images, orig_class_labels, target_class_labels)
+
+
+class _SlicedDDIBGraph(DDIBGraph):
+    """What ``DDIBGraph(...)`` builds for a batch beyond ``unet.max_batch``: one launch plan addresses each tensor with 32-bit byte offsets
+    (< 2 GiB: 127 images of 256 x 256 x 64 bf16 channels), so a larger batch (SURVEY 8(d) sweeps batch_size up to 128) is replayed as even
+    slices -- the samples of a batch are independent (utils_Img2Img.py:566-612: no cross-sample op anywhere on the path).  Slices of equal
+    size share ONE single-plan runner, hence one captured graph; the outputs are gathered into buffers of the whole batch."""
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, height: int = None,
+                 width: int = None, variant: str = "0.18.2", device=None, use_graph: bool = True, private_plan: bool = False):
+        self.pipe = pipe
+        unet = pipe.unet
+        B, S = batch_size, num_inference_steps
+        H, W = _sample_hw(unet, height, width)
+        dev = torch.device(device) if device is not None else unet.device
+        n_sl = -(-B // unet.max_batch(H, W))
+        step = -(-B // n_sl)
+        self._bounds = [(b0, min(B, b0 + step)) for b0 in range(0, B, step)]
+        self._runners = {}
+        for b0, b1 in self._bounds:
+            if b1 - b0 not in self._runners:
+                self._runners[b1 - b0] = DDIBGraph(pipe, b1 - b0, S, H, W, variant, dev, use_graph, private_plan)
+        first = self._runners[self._bounds[0][1] - self._bounds[0][0]]
+        # no graph of its own (the slices' runners own the graphs); the first slice runner's stream and plan
+        _TrajectoryRunner.__init__(self, unet, B, S, H, W, dev, use_graph, stream=first.stream)
+        self.plan, self.inv_ts, self.gen_ts = first.plan, first.inv_ts, first.gen_ts
+        self.inverted = torch.empty((B,) + tuple(first.x.shape[1:]), dtype=torch.float32, device=dev)
+        self._image_outputs()
+
+    @torch.no_grad()
+    def run(self, clean_images, orig_class_labels, target_class_labels, join: bool = True):
+        _check_shape(clean_images, self.inverted)
+        for b0, b1 in self._bounds:
+            r = self._runners[b1 - b0]
+            r.run(clean_images[b0:b1], orig_class_labels[b0:b1], target_class_labels[b0:b1], join=False)
+            with torch.cuda.stream(r.stream):      # stream-ordered before the runner's next replay overwrites its outputs
+                self.images[b0:b1].copy_(r.images, non_blocking=True)
+                self.images_u8[b0:b1].copy_(r.images_u8, non_blocking=True)
+                self.inverted[b0:b1].copy_(r.inverted, non_blocking=True)
+        return self.join() if join else self
+
+    def join(self):
+        for r in self._runners.values():
+            r.join()
+        return self
+
+
+class CFGForwardStartGraph(_PixelTrajectory):
+    """hipGraph form of the CFG forward-start transfer (utils_Img2Img.py:615-648 +
+    pipeline_conditionial_ddim.py:248-347): ``add_noise`` to the first kept timestep, then per step a conditional
+    and an unconditional UNet evaluation (``class_emb = 0``, pipeline :310-317) feeding ONE fused
+    guidance-combine + DDIM update; post-processing; all captured once and replayed per batch.
+
+    ``run(clean_images, target_labels, noise)``: the forward noise is an input (the reference draws it from the
+    caller's generator, ``randn_tensor``), so results are reproducible against the eager pipeline / the oracle."""
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, guidance_scale: float = 2.5,
+                 frac_diffusion_skipped: float = 0.5, guidance_eqn: str = "imagen", height: int = None, width: int = None,
+                 device=None, use_graph: bool = True):
+        if guidance_eqn not in ("imagen", "CFG"):
+            raise ValueError(f"Unknown guidance equation '{guidance_eqn}'; should be 'imagen' or 'CFG'")
+        super().__init__(pipe, batch_size, num_inference_steps, height, width, device, use_graph, keeps_input=True)
+        B, dev = self.B, self.device
+        sch = pipe.scheduler
+        sch.set_timesteps(self.S)
+        init_t = sch.config.num_train_timesteps * (1 - frac_diffusion_skipped)   # pipeline :252-258
+        self.ts = [int(t) for t in sch.timesteps[sch.timesteps <= init_t]]
+        w = guidance_scale
+        do_cfg = (guidance_eqn == "imagen" and w > 1) or (guidance_eqn == "CFG" and w > 0)   # :272-284
+        self.noise = torch.empty_like(self.x)
+        self._class_table(self.ts)
+        # the unconditional evaluation of a step: the same timestep rows under a zero class embedding, into its own output
+        self.zero_emb = torch.zeros((len(self.ts) * B, pipe.unet.time_embed_dim), dtype=torch.float32, device=dev)
+        self.uncond = (torch.empty_like(self.temb), torch.empty_like(self.x)) if do_cfg else None
+        self.w_dev = torch.tensor([float(w)], dtype=torch.float32, device=dev)
+        sa, sb = sch._per_sample_coefs(torch.tensor([self.ts[0]] * B), dev)
+        self._sa, self._sb = sa, sb
+        self.noise_args = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0,
+                                         x=self.clean.data_ptr(), noise=self.noise.data_ptr(), sa=sa.data_ptr(),
+                                         sb=sb.data_ptr(), out=self.x.data_ptr())
+        self.step_args = [sch.ddim_step_args(t, self.x, self.model_out, self.x, self.uncond[1] if do_cfg else None, self.w_dev,
+                                             guidance_cfg=guidance_eqn == "CFG") for t in self.ts]
+        self._capture()
+
+    def _enqueue(self, st):
+        self.class_rows.temb(self.ts_rows, st, self.temb)
+        if self.uncond is not None:
+            self.plan.temb_rows(self.ts_rows, None, self.zero_emb, st, rows=self.ts_rows.numel(), out=self.uncond[0])
+        L.check(self.lib.pd_add_noise(C.byref(self.noise_args), st), "pd_add_noise")
+        self._ddim_steps(st, self.step_args, uncond=self.uncond)
+        self._postproc(st)
+
+    def _fill(self, clean_images, target_class_labels, noise):
+        n, B = len(self.ts), self.B
+        self.clean.copy_(clean_images, non_blocking=True)
+        self.noise.copy_(noise, non_blocking=True)
+        self.class_rows.fill(slice(0, n * B), n, B, target_class_labels)
+
+    def run(self, clean_images: torch.Tensor, target_class_labels: torch.Tensor, noise: torch.Tensor):
+        _check_shape(clean_images, self.clean)
+        _check_shape(noise, self.noise)
+        return self._replay(True, clean_images, target_class_labels, noise)
+
+
+class GuidedTransferGraph(_PixelTrajectory):
+    """One hipGraph for the gradient-guided transfer (``_linear_interp_custom_guidance_inverted_start``, utils_Img2Img.py:651-760) with a
+    ``ConditionalDDIMPipeline``: S inversion steps under the original class, then S guided steps under the target class -- UNet
+    forward, Lp loss gradient, input-gradient backward, push + scheduler update -- and the post-processing; what
+    ``linear_interp_custom_guidance_inverted_start`` computes, bit for bit.
+
+    ``run(images, orig_labels, target_labels)`` leaves ``.images`` (NHWC float in [0, 1]), ``.images_u8``, ``.guided`` (the [-1, 1] NCHW
+    tensor of ``output_type="pt"``), ``.inverted``, ``.losses`` ((S, B): the Lp loss of every step) and ``.grad_scale``.
+
+    fp16 engine: the gradient scale lives on the device and starts at :data:`~phendiff_amd.img2img.GUIDANCE_GRAD_SCALE`; a trajectory
+    whose UNet input gradient was not finite somewhere is replayed at half the scale (one host read per trajectory instead of one per
+    step), down to 2^-10, and the scale reached is kept.
+
+    The inversion half runs on the model's inference plan (the one ``inversion`` uses: the same bits, no statistics kept), the guided
+    half on its input-gradient plan: both plans' activations are resident, the price of an inversion at inference speed."""
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, p: float, guidance_loss_scale: float,
+                 height: int = None, width: int = None, variant: str = "0.18.2", device=None, use_graph: bool = True):
+        _check_guided_request(pipe, ConditionalDDIMPipeline, p)
+        super().__init__(pipe, batch_size, num_inference_steps, height, width, device, use_graph, input_grad=True, keeps_input=True,
+                         inverts=True)
+        unet, B, dev = pipe.unet, self.B, self.device
+        self.inv, fwd, self.inv_ts, self.gen_ts = _schedules(pipe, self.S, variant)
+        self.guided = self.x
+        self._class_table(self.inv_ts)
+        self.inv_args = [self.inv.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.inv_ts]
+        # the target class of the guided half, in the form the input-gradient plan's forward takes without converting (a capture must
+        # not allocate): int64 ids (class table), fp32 values ("timestep") or the fp32 embedding rows themselves ("identity")
+        self.class_mode = getattr(self.gplan.w, "class_mode", None)
+        if self.class_mode == "identity":
+            self.g_labels, self.g_emb = None, torch.zeros((B, unet.time_embed_dim), dtype=torch.float32, device=dev)
+        else:
+            self.g_labels, self.g_emb = torch.zeros((B,), dtype=torch.int64 if self.class_mode is None else torch.float32, device=dev), None
+        self.steps = _GuidedSteps(self.lib, unet, self.gplan, fwd, self.gen_ts, self.x, self.model_out, self.inverted, p, guidance_loss_scale,
+                                  lambda i, ts, st: self.gplan.forward(self.x, ts, self.g_labels, self.g_emb, self.model_out, st))
+        self.losses = self.steps.losses
+        self._inverted_snapshot()
+        self._capture()
+
+    @property
+    def grad_scale(self) -> float:
+        return self.steps.grad_scale
+
+    def _enqueue(self, st):
+        self.x.copy_(self.clean)             # the trajectory works in place: the batch itself stays for a replay at another scale
+        self.class_rows.temb(self.ts_rows, st, self.temb)
+        self._ddim_steps(st, self.inv_args)
+        self._snapshot(st)
+        self.steps.enqueue(st)
+        self._postproc(st)
+
+    def _fill(self, clean_images, orig_class_labels, target_class_labels):
+        B, n_inv, dev = self.B, len(self.inv_ts), self.device
+        self.clean.copy_(clean_images, non_blocking=True)
+        self.class_rows.fill(slice(0, n_inv * B), n_inv, B, orig_class_labels)
+        if self.class_mode == "identity":
+            self.g_emb.copy_(_identity_rows(target_class_labels, B, self.g_emb.shape[1], dev))
+        else:
+            self.g_labels.copy_(target_class_labels.to(device=dev).view(B))
+        self.steps.reset()
+
+    def run(self, clean_images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor, join: bool = True):
+        """``join=False`` leaves the caller's stream un-joined (``self.join()`` before reading the outputs).  fp16: returns after the one
+        host read of the overflow flag, that is with the trajectory finished."""
+        _check_shape(clean_images, self.x)
+        self._replay(False, clean_images, orig_class_labels, target_class_labels)
+        self.steps.settle(self)
+        return self.join() if join else self
+
+
+class _LatentTrajectory(_TrajectoryRunner):
+    """A trajectory in the latent space of a ``CustomStableDiffusionImg2ImgPipeline``: VAE encode -> posterior sample (x
+    ``scaling_factor``) into ``latents`` (every step updates them in place) -> DDIM phases on the SD UNet's inference plan, each under one
+    (B, 77, D) class embedding -> VAE decode into ``decoded``; the buffers, and the launches of each phase.  ``input_grad``: also the
+    UNet's input-gradient plan (``gplan``: a guided half runs on it)."""
+
+    def __init__(self, pipe, batch_size, num_inference_steps, height, width, device, use_graph, input_grad=False):
+        self.pipe = pipe
+        unet, vae = pipe.unet, pipe.vae
+        super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, H, W, dev = self.B, self.H, self.W, self.device
+        sf = 1 << (len(vae.config.block_out_channels) - 1)
+        h, w = H // sf, W // sf
+        lc = vae.config.latent_channels
+
+        # the VAE runs in sub-batches of what one of its launch plans addresses (32-bit byte offsets), like vae.encode / .decode
+        def chunks(kind, ph, pw):
+            step = vae._max_batch(H, W, kind)
+            return [(b0, min(step, B - b0), vae._plan(kind, min(step, B - b0), ph, pw, dev)) for b0 in range(0, B, step)]
+        self.enc_chunks, self.dec_chunks = chunks("enc", H, W), chunks("dec", h, w)
+        self.plan = unet.plan_for(B, h, w, 77, dev)
+        self.gplan = unet.input_grad_plan(B, h, w, 77, dev) if input_grad else None
+        f32 =lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self.x, self.moments, self.noise = f32(B, 3, H, W), f32(B, 2 * lc, h, w), f32(B, lc, h, w)
+        self.latents, self.model_out, self.inverted, self.dec_in = f32(B, lc, h, w), f32(B, lc, h, w), f32(B, lc, h, w), f32(B, lc, h, w)
+        self.decoded = f32(B, 3, H, W)
+        D = unet.config.cross_attention_dim
+        self.ehs_orig, self.ehs_target = f32(B, 77, D), f32(B, 77, D)
+        self.scaling = float(vae.config.scaling_factor)
+        self.sample_args = L.LatentSampleArgs(B=B, C=lc, HW=h * w, scale=self.scaling, moments=self.moments.data_ptr(),
+                                              noise=self.noise.data_ptr(), out=self.latents.data_ptr())
+
+    def _timestep_rows(self, timesteps):
+        self.ts_rows = torch.tensor(timesteps, dtype=torch.float32).repeat_interleave(self.B).to(self.device)
+
+    def _encode(self, st):
+        for b0, nb, plan_ in self.enc_chunks:
+            plan_.run(self.x[b0:b0 + nb].data_ptr(), self.moments[b0:b0 + nb].data_ptr(), st)
+        L.check(self.lib.pd_latent_sample(C.byref(self.sample_args), st), "pd_latent_sample")
+
+    def _ddim_phase(self, st, ehs, step_args, first: int = 0):
+        """One class's run of steps (``first``: the row block of ``ts_rows`` it starts at).  The class conditioning goes (B, 77, D) fp32
+        -> the plan's compute-dtype buffer once; per step ``pd_temb`` into the plan's own table, the UNet, ``pd_ddim_step``."""
+        lib, plan, B = self.lib, self.plan, self.B
+        plan.ehs.view(B, 77, -1).copy_(ehs)
+        ta = plan.temb_args
+        for i, a in enumerate(step_args, first):
+            ta.rows = B
+            ta.timesteps, ta.labels, ta.class_emb = self.ts_rows.data_ptr() + 4 * i * B, None, None
+            ta.emb, ta.proj = plan.temb_emb.data_ptr(), plan.temb_table.data_ptr()
+            L.check(lib.pd_temb(C.byref(ta), st), "pd_temb")
+            # the cross-attention k / v projections only on the first step of a phase (the context is the phase's class): round 6
+            plan.run(self.latents.data_ptr(), plan.temb_table.data_ptr(), self.model_out.data_ptr(), st, context=(i == first))
+            L.check(lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
+
+    def _decode(self, st):
+        torch.div(self.latents, self.scaling, out=self.dec_in)        # vae.decode(latents / scaling_factor), custom_pipeline...:709
+        for b0, nb, plan_ in self.dec_chunks:
+            plan_.run(self.dec_in[b0:b0 + nb].data_ptr(), self.decoded[b0:b0 + nb].data_ptr(), st)
+
+    def _fill(self, clean_images, noise, ehs_orig, ehs_target):
+        self.x.copy_(clean_images, non_blocking=True)
+        self.noise.copy_(noise, non_blocking=True)
+        self.ehs_orig.copy_(ehs_orig)
+        self.ehs_target.copy_(ehs_target)
+
+    @torch.no_grad()
+    def _inputs(self, clean_images, orig_class_labels, target_class_labels, generator, noise):
+        """What ``_fill`` takes for a batch: the posterior noise (drawn from ``generator`` outside the graph, like
+        ``latent_dist.sample(generator)``) and both classes' (B, 77, D) embeddings."""
+        from .sd_pipeline import hack_class_embedding
+        _check_shape(clean_images, self.x)
+        pipe, dev = self.pipe, self.device
+        if noise is None:
+            noise = randn_tensor(tuple(self.noise.shape), generator, dev)
+        eo = hack_class_embedding(pipe._encode_class(class_labels=orig_class_labels, device=dev, do_classifier_free_guidance=False))
+        et = hack_class_embedding(pipe._encode_class(class_labels=target_class_labels, device=dev, do_classifier_free_guidance=False))
+        # the trajectory leaves ITS context in the shared inference plan's `ehs` and k / v buffers, replayed or enqueued: an eager forward
+        # that comes back with the tensor it projected before this run must project it again
+        self.plan.forget_context()
+        return clean_images, noise, eo, et
+
+
+class SDDDIBGraph(_LatentTrajectory):
+    """One hipGraph for the latent-diffusion DDIB transfer -- ``_ddib`` with a ``CustomStableDiffusionImg2ImgPipeline``
+    (utils_Img2Img.py:566-612; custom_pipeline_stable_diffusion_img2img.py:667-711): VAE encode -> posterior sample (x
+    ``scaling_factor``) -> S inversion steps under the original class -> class swap -> S denoising steps -> VAE decode ->
+    ``(x / 2 + .5).clamp(0, 1)`` NHWC.  ~360 launches x 2S steps are captured once and replayed per batch; the result is the eager
+    ``ddib(pipe, ...)`` bit for bit.  ``run(images, orig_labels, target_labels, generator=None, noise=None)``: the posterior noise is an
+    input (drawn from ``generator`` outside the graph, like ``latent_dist.sample(generator)``)."""
+
+    def __init__(self, pipe, batch_size: int, num_inference_steps: int, height: int, width: int, variant: str = "0.18.2",
+                 device=None, use_graph: bool = True):
+        super().__init__(pipe, batch_size, num_inference_steps, height, width, device, use_graph)
+        B, S, H, W, dev = self.B, self.S, self.H, self.W, self.device
+        # strength = 1: all S steps (custom_pipeline...:375-382)
+        self.inv, fwd, self.inv_ts, self.gen_ts = _schedules(pipe, S, variant, lambda fwd: pipe.get_timesteps(S, 1.0, dev)[0], device=dev)
+        self._timestep_rows(self.inv_ts + self.gen_ts)
+        self.inv_args = [self.inv.ddim_step_args(t, self.latents, self.model_out, self.latents) for t in self.inv_ts]
+        self.gen_args = [fwd.ddim_step_args(t, self.latents, self.model_out, self.latents) for t in self.gen_ts]
+        self.images = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+        self.post_args = L.PostprocArgs(B=B, C=3, H=H, W=W, x=self.decoded.data_ptr(), out_f32=self.images.data_ptr(), out_u8=None)
+        self._capture()
+
+    def _enqueue(self, st):
+        self._encode(st)
+        self._ddim_phase(st, self.ehs_orig, self.inv_args)
+        self.inverted.copy_(self.latents)
+        self._ddim_phase(st, self.ehs_target, self.gen_args, first=len(self.inv_args))
+        self._decode(st)
+        L.check(self.lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
+
+    def run(self, clean_images, orig_class_labels, target_class_labels, generator=None, noise=None):
+        return self._replay(True, *self._inputs(clean_images, orig_class_labels, target_class_labels, generator, noise))
+
+
+class SDGuidedTransferGraph(_LatentTrajectory):
+    """One hipGraph for the gradient-guided transfer with a ``CustomStableDiffusionImg2ImgPipeline`` (utils_Img2Img.py:651-760, latent
+    branch): VAE encode -> posterior sample (x ``scaling_factor``) -> S inversion steps on the latents under the original class -> S
+    guided steps through the SD UNet's input-gradient plan under the target class embeddings -> VAE decode.  The reference's min-max
+    renormalisation (:689-695: two reductions over the whole batch) runs after the replay, outside the capture.
+
+    ``run(images, orig_labels, target_labels, generator=None, noise=None)`` (the posterior noise is an input, as for
+    :class:`SDDDIBGraph`) leaves ``.guided`` (renormalised [-1, 1] NCHW, ``output_type="pt"``), ``.images`` (NHWC float in [0, 1]),
+    ``.guided_latents``, ``.inverted``, ``.losses`` and ``.grad_scale``; fp16 as in :class:`GuidedTransferGraph`.  The inversion half
+    runs on the inference plan, like there."""
+
+    def __init__(self, pipe, batch_size: int, num_inference_steps: int, p: float, guidance_loss_scale: float, height: int, width: int,
+                 variant: str = "0.18.2", device=None, use_graph: bool = True):
+        from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
+        _check_guided_request(pipe, CustomStableDiffusionImg2ImgPipeline, p)
+        super().__init__(pipe, batch_size, num_inference_steps, height, width, device, use_graph, input_grad=True)
+        self.inv, fwd, self.inv_ts, self.gen_ts = _schedules(pipe, self.S, variant)
+        self._timestep_rows(self.inv_ts)
+        self.inv_args = [self.inv.ddim_step_args(t, self.latents, self.model_out, self.latents) for t in self.inv_ts]
+        self.guided_latents = self.latents
+        self.guided = self.images = None
+        self.steps = _GuidedSteps(self.lib, pipe.unet, self.gplan, fwd, self.gen_ts, self.latents, self.model_out, self.inverted, p,
+                                  guidance_loss_scale,
+                                  lambda i, ts, st: self.gplan.forward(self.latents, ts, self.ehs_target, self.model_out, st))
+        self.losses = self.steps.losses
+        self._capture()
+
+    @property
+    def grad_scale(self) -> float:
+        return self.steps.grad_scale
+
+    def _enqueue(self, st):
+        self._encode(st)
+        self._ddim_phase(st, self.ehs_orig, self.inv_args)
+        self.inverted.copy_(self.latents)
+        self.steps.enqueue(st)
+        self._decode(st)
+
+    def _fill(self, *inputs):
+        super()._fill(*inputs)
+        self.steps.reset()
+
+    @torch.no_grad()
+    def run(self, clean_images, orig_class_labels, target_class_labels, generator=None, noise=None, join: bool = True):
+        self._replay(False, *self._inputs(clean_images, orig_class_labels, target_class_labels, generator, noise))
+        self.steps.settle(self)
+        with torch.cuda.stream(self.stream):      # :689-695, outside the capture: two reductions over the whole batch
+            image = self.decoded - self.decoded.min()
+            image = image / image.max()
+            self.guided = image * 2 - 1
+            self.images = (self.guided / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).contiguous()
+        return self.join() if join else self

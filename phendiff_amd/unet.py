@@ -851,7 +851,7 @@ class UNetPlan:
         """``class_embedding(time_proj(class_labels))`` through ``pd_temb`` with the class MLP's weights: its ``emb`` output is the
         row block the main call adds (the projections it also computes land in a scratch table).  ``emb`` / ``scratch`` / ``vals``:
         pre-allocated buffers ([rows][time_embed_dim], [rows][proj_dim], the labels as fp32 [rows]) -- a hipGraph capture must not
-        allocate (img2img._ClassRows)."""
+        allocate (trajectories._ClassRows)."""
         w, c = self.w, self.m.config
         if emb is None:
             emb = torch.empty((rows, self.m.time_embed_dim), dtype=torch.float32, device=self.device)

@@ -1,9 +1,13 @@
-"""Signature of what the captured-trajectory runners (``DDIBGraph``, ``CFGForwardStartGraph``, ``SDDDIBGraph``) enqueue: every call into the
-HIP library, in order, argument for argument, from the construction of the model to the end of two ``run`` calls, plus the sha256 of the
-runners' outputs.  Two revisions enqueue the same program iff their outputs are byte-identical:
+"""Signature of what the captured-trajectory runners (``DDIBGraph``, ``CFGForwardStartGraph``, ``SDDDIBGraph``, ``GuidedTransferGraph``,
+``SDGuidedTransferGraph``) enqueue: every call into the HIP library, in order, argument for argument, from the construction of the model
+to the end of two ``run`` calls, plus the sha256 of the runners' outputs.  Two revisions enqueue the same program iff their outputs are
+byte-identical:
 
-   python scripts/trajectory_signature.py > head.txt        (and the same file, unchanged, on a checkout of the other revision)
+   python scripts/trajectory_signature.py > head.txt
+   python scripts/trajectory_signature.py --tree <export of the other revision, holding a built library> > parent.txt
    cmp parent.txt head.txt
+
+``--tree``: the directory to import ``phendiff_amd`` from (default: this checkout), so that one script file signs both revisions.
 
 A recording proxy stands in for the loaded library (``phendiff_amd._lib._lib``) before any model, plan or runner exists, so every entry
 point a plan stores or a runner calls goes through it.  Every runner is built with ``use_graph=False`` (the launches a capture would
@@ -11,6 +15,7 @@ record, enqueued on the runner's stream) and run twice, the second time with oth
 argument the ctypes struct's type name with every field in ``_fields_`` order.  Pointers (fields, streams, handles) are recorded as null or
 a canonical ordinal (the first distinct address met in a case is 0, the next 1, ...), as ``plan_signature.py`` does: the aliasing structure
 is compared, allocator addresses are not.  Tiny seeded models and inputs; a few seconds on the GPU."""
+import argparse
 import ctypes as C
 import hashlib
 import json
@@ -20,7 +25,9 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+_ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+_ap.add_argument("--tree", default=ROOT, help="directory to import phendiff_amd from (default: this checkout)")
+sys.path.insert(0, os.path.abspath(_ap.parse_args().tree))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import phendiff_amd as P  # noqa: E402
 import phendiff_amd._lib as L  # noqa: E402
@@ -80,7 +87,7 @@ def emit(name, rec, runner=None):
     for c in rec.calls:
         print(json.dumps(c, separators=(",", ":")))
     if runner is not None:
-        for attr in ("images", "inverted", "images_u8"):
+        for attr in ("images", "inverted", "images_u8", "guided", "guided_latents", "losses"):
             if getattr(runner, attr, None) is not None:
                 print(f"sha256 {attr} {sha(getattr(runner, attr))}")
     rec.calls = []
@@ -140,9 +147,21 @@ def cfg_case(name, rec, eqn, w):
         emit(f"{name} run {i}", rec, runner)
 
 
-def sd_case(name, rec, mode):
-    from make_golden import SD_SCHED, SD_TINY_UNET, SD_TINY_VAE, sd_tiny_pipe
+def guided_case(name, rec, mode, **over):
+    """fp16 takes the device-scale path (``pd_lp_guidance_scaled``, the overflow flag of ``pd_guided_step``) and ``settle``."""
     rec.reset()
+    pipe = pixel_pipe(mode, **over)
+    B = 3
+    runner = P.GuidedTransferGraph(pipe, B, 2, 2, 0.5, height=32, width=32, use_graph=False)
+    emit(f"{name} construct", rec)
+    orig, target = conditioning(over.get("class_embed_type"), B, pipe.unet.time_embed_dim, 61)
+    for i, cond in enumerate(((orig, target), (target, orig))):
+        runner.run(images(B, 1 + i), *cond)
+        emit(f"{name} run {i}", rec, runner)
+
+
+def sd_pipe(mode):
+    from make_golden import SD_SCHED, SD_TINY_UNET, SD_TINY_VAE, sd_tiny_pipe
     ref = sd_tiny_pipe()
     unet = P.SDUNet2DConditionModel(compute_dtype=mode, **SD_TINY_UNET)
     unet.load_state_dict(ref.unet.state_dict())
@@ -150,9 +169,17 @@ def sd_case(name, rec, mode):
     vae.load_state_dict(ref.vae.state_dict())
     emb = P.CustomEmbedding(2, SD_TINY_UNET["cross_attention_dim"])
     emb.load_state_dict(ref.class_embedding.state_dict())
-    pipe = P.CustomStableDiffusionImg2ImgPipeline(vae.to(DEV), unet.to(DEV), P.DDIMScheduler(**SD_SCHED), emb.to(DEV))
+    return P.CustomStableDiffusionImg2ImgPipeline(vae.to(DEV), unet.to(DEV), P.DDIMScheduler(**SD_SCHED), emb.to(DEV))
+
+
+def sd_case(name, rec, mode, guided=False):
+    rec.reset()
+    pipe = sd_pipe(mode)
     B = 2
-    runner = P.SDDDIBGraph(pipe, batch_size=B, num_inference_steps=2, height=32, width=32, use_graph=False)
+    if guided:
+        runner = P.SDGuidedTransferGraph(pipe, B, 2, 2, 0.5, 32, 32, use_graph=False)
+    else:
+        runner = P.SDDDIBGraph(pipe, batch_size=B, num_inference_steps=2, height=32, width=32, use_graph=False)
     emit(f"{name} construct", rec)
     orig, target = conditioning(None, B, 0, 41)
     for i, cond in enumerate(((orig, target), (target, orig))):
@@ -162,6 +189,7 @@ def sd_case(name, rec, mode):
 
 
 def main():
+    print(f"phendiff_amd from {os.path.dirname(P.__file__)}", file=sys.stderr)
     rec = RecordingLib(L.lib())
     L._lib = rec
     ddib_case("ddib_f32", rec, "f32", 3)
@@ -174,6 +202,12 @@ def main():
     cfg_case("cfg_CFG_w2.5", rec, "CFG", 2.5)
     sd_case("sd_ddib_f32", rec, "f32")
     sd_case("sd_ddib_bf16", rec, "bf16")
+    guided_case("guided_f32", rec, "f32")
+    guided_case("guided_fp16", rec, "fp16")
+    guided_case("guided_f32_class_identity", rec, "f32", class_embed_type="identity", num_class_embeds=None)
+    guided_case("guided_f32_class_timestep", rec, "f32", class_embed_type="timestep")
+    sd_case("sd_guided_f32", rec, "f32", guided=True)
+    sd_case("sd_guided_bf16", rec, "bf16", guided=True)
 
 
 if __name__ == "__main__":
