@@ -38,7 +38,8 @@ extern "C" {
  * pd_token_wgrad_args.stage / pd_wgrad_args.stage.  Entry points added since without a change to any existing struct keep 8 (a caller built
  * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample, pd_sample_stats
  * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace), pd_lp_guidance_scaled, pd_guided_step
- * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args). */
+ * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args), pd_image_preprocess_bands16, pd_band_histogram16,
+ * pd_postproc_bands16 (+ their args structs). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -851,6 +852,62 @@ typedef struct {
   float* y_f32; unsigned char* y_u8;
 } pd_image_preprocess_bands_args;
 int pd_image_preprocess_bands(const pd_image_preprocess_bands_args* a, void* stream);
+
+/* pd_image_preprocess_bands16 (added under ABI 8): pd_image_preprocess_bands for 16-bit sources (plate-reader / sCMOS TIFFs): C interleaved
+ * uint16 bands in, C bands out, every band resampled as Pillow resamples a mode I;16 image (its 16bpc path), bit for bit.
+ * csrc/data16_kernels.hip; host side phendiff_amd/data.py (resample_tables_f64 builds the tables).  Fields as in
+ * pd_image_preprocess_bands_args, except:
+ *   x: uint16, 2-byte aligned; the strides stay BYTE strides and must be even; 2 * C <= pixel_stride <= 128.
+ *   coef_x double [OW][ksize_x], coef_y double [OH][ksize_y]: the float64 triangle-filter weights, normalised by the row sum, NOT rounded to
+ *      fixed point (zero past each row's count); bounds_* and ksize_* as in the 8-bit entries.
+ *      per output: ss = 0.0; ss = ss + (double)src[first + k] * coef[k] for k in order (product and sum rounded separately: no FMA);
+ *      out = clamp((int)(ss + 0.5), 0, 65535).  Horizontal pass first INTO uint16, then the vertical pass; an unchanged axis is skipped.
+ *   y_u16 (may be null): uint16 NHWC [out_slots][OH][OW][C], the resized samples (never flipped).
+ *   y_f32 (may be null): float32 NCHW [out_slots][C][OH][OW]: f = ((float)v - lo[c]) / (hi[c] - lo[c]); f = min(max(f, 0), 1) (a NaN stays
+ *      one); y = (f - mean[c]) / std[c] -- five IEEE fp32 operations, no reciprocal, no contraction; mirrored per flips[n].
+ *   lo, hi, mean, std: device float32 [C], read only when y_f32 is given (lo = 0, hi = 65535: the v / 65535 analogue of ToTensor).
+ * Refused as pd_image_preprocess_bands refuses, plus odd strides or an odd x (PD_ERR_SHAPE / PD_ERR_ARG) and null lo / hi with y_f32
+ * (PD_ERR_ARG).  A workgroup stages whole source rows at the pixel stride given: a view into wide pixels under a steep horizontal down-scale
+ * is refused with "tile does not fit the LDS budget" (PD_ERR_SHAPE) where the same bands stored densely run. */
+typedef struct {
+  int N, H, W, C, OH, OW, out_slots;
+  long long image_stride, row_stride; int pixel_stride;
+  int ksize_x, ksize_y;
+  const unsigned short* x;
+  const double* coef_x; const int* bounds_x; const double* coef_y; const int* bounds_y;
+  const int* out_index; const unsigned char* flips;
+  const float* lo; const float* hi; const float* mean; const float* std;
+  float* y_f32; unsigned short* y_u16;
+} pd_image_preprocess_bands16_args;
+int pd_image_preprocess_bands16(const pd_image_preprocess_bands16_args* a, void* stream);
+
+/* pd_band_histogram16 (added under ABI 8): exact per-band value counts of uint16 stacks, counts[c][v] += number of samples of band c equal to
+ * v -- what an intensity window (percentiles) is read from.  The source is addressed as in pd_image_preprocess_bands16 (N images of H x W
+ * pixels, C in 1..32 bands read from each, even byte strides, 2 * C <= pixel_stride; no upper limit on pixel_stride here).
+ *   counts: device unsigned int [C][65536].  The caller zeroes it; launches ACCUMULATE (a list of mixed sizes sums over its groups).
+ * Integer counting only: the result does not depend on scheduling and is bitwise reproducible.  A workgroup counts one band of a chunk of
+ * at most 65535 pixels into a whole 65536-bin histogram of 16-bit counters in LDS (128 KiB) and adds its non-zero bins to `counts`.
+ * Refused: N * H * W >= 2^32, odd or too small strides (PD_ERR_SHAPE); null pointers, an odd x, C out of range (PD_ERR_ARG). */
+typedef struct {
+  int N, H, W, C;
+  long long image_stride, row_stride; int pixel_stride;
+  const unsigned short* x;
+  unsigned int* counts;
+} pd_band_histogram16_args;
+int pd_band_histogram16(const pd_band_histogram16_args* a, void* stream);
+
+/* pd_postproc_bands16 (added under ABI 8): the way back from the engine's float32 NCHW tensors to uint16 stacks in the source's range (the
+ * inverse of pd_image_preprocess_bands16's float tail), element-wise:
+ *   f = x * std[c] + mean[c] (two roundings); f = clamp(f, 0, 1), NaN -> 0; r = f * (hi[c] - lo[c]) + lo[c] (two roundings);
+ *   y = clamp(rintf(r), 0, 65535) (round half to even; NaN -> 0).
+ *   x float32 NCHW [N][C][H][W]; y uint16 NHWC [N][H][W][C]; lo, hi, mean, std device float32 [C]. */
+typedef struct {
+  int N, C, H, W;
+  const float* x;
+  const float* lo; const float* hi; const float* mean; const float* std;
+  unsigned short* y;
+} pd_postproc_bands16_args;
+int pd_postproc_bands16(const pd_postproc_bands16_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_train_sample (added under ABI 8): the per-step sampling of perform_training_epoch (utils_training.py:244-256) on the device, one launch:

@@ -333,6 +333,24 @@ class ImagePreprocessBandsArgs(C.Structure):
                 ("bounds_y", vp), ("out_index", vp), ("flips", vp), ("mean", vp), ("std", vp), ("y_f32", vp), ("y_u8", vp)]
 
 
+class ImagePreprocessBands16Args(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("OH", C.c_int), ("OW", C.c_int),
+                ("out_slots", C.c_int), ("image_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_int),
+                ("ksize_x", C.c_int), ("ksize_y", C.c_int), ("x", vp), ("coef_x", vp), ("bounds_x", vp), ("coef_y", vp),
+                ("bounds_y", vp), ("out_index", vp), ("flips", vp), ("lo", vp), ("hi", vp), ("mean", vp), ("std", vp),
+                ("y_f32", vp), ("y_u16", vp)]
+
+
+class BandHistogram16Args(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("image_stride", C.c_longlong),
+                ("row_stride", C.c_longlong), ("pixel_stride", C.c_int), ("x", vp), ("counts", vp)]
+
+
+class PostprocBands16Args(C.Structure):
+    _fields_ = [("N", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("x", vp), ("lo", vp), ("hi", vp), ("mean", vp),
+                ("std", vp), ("y", vp)]
+
+
 class TrainSampleArgs(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("rank", C.c_int), ("purpose", C.c_int), ("B", C.c_int64),
                 ("per_sample", C.c_int64), ("elem_base", C.c_uint64), ("N", C.c_int), ("clean", vp), ("sqrt_acp", vp),
@@ -434,6 +452,9 @@ SYMBOLS = {
     "pd_fc_f32": (C.c_int, [C.POINTER(FcF32Args), vp]),
     "pd_image_preprocess": (C.c_int, [C.POINTER(ImagePreprocessArgs), vp]),
     "pd_image_preprocess_bands": (C.c_int, [C.POINTER(ImagePreprocessBandsArgs), vp]),
+    "pd_image_preprocess_bands16": (C.c_int, [C.POINTER(ImagePreprocessBands16Args), vp]),
+    "pd_band_histogram16": (C.c_int, [C.POINTER(BandHistogram16Args), vp]),
+    "pd_postproc_bands16": (C.c_int, [C.POINTER(PostprocBands16Args), vp]),
     "pd_train_sample": (C.c_int, [C.POINTER(TrainSampleArgs), vp]),
     "pd_sample_stats": (C.c_int, [C.POINTER(SampleStatsArgs), vp]),
     "pd_sample_stats_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
