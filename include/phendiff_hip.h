@@ -832,8 +832,8 @@ int pd_image_preprocess(const pd_image_preprocess_args* a, void* stream);
 
 /* pd_image_preprocess_bands (added under ABI 8): the same transform for image stacks that are not RGB (Cell Painting's five stains, multiplexed
  * immunofluorescence): C interleaved uint8 bands in, C bands out -- no replication, no dropped channel.  Every band is an independent mode-L
- * image: the tables, the 22-bit fixed point and the horizontal-then-vertical order are those of pd_image_preprocess (one device function
- * serves both kernels).  Fields as in pd_image_preprocess_args, except:
+ * image: the tables, the 22-bit fixed point and the horizontal-then-vertical order are those of pd_image_preprocess (one tiled
+ * resampler, csrc/pd_resample.h, serves this kernel, that one and the 16-bit entry below).  Fields as in pd_image_preprocess_args, except:
  *   C in 1..32 channels are read from every pixel (C <= pixel_stride <= 64: a wider stride reads a strided view and skips the rest);
  *   mean, std: device float32 [C] (read only when y_f32 is given);
  *   y_u8 uint8 NHWC [out_slots][OH][OW][C]; y_f32 float32 NCHW [out_slots][C][OH][OW] = ((float)u8 / 255.f - mean[c]) / std[c].
@@ -855,7 +855,7 @@ int pd_image_preprocess_bands(const pd_image_preprocess_bands_args* a, void* str
 
 /* pd_image_preprocess_bands16 (added under ABI 8): pd_image_preprocess_bands for 16-bit sources (plate-reader / sCMOS TIFFs): C interleaved
  * uint16 bands in, C bands out, every band resampled as Pillow resamples a mode I;16 image (its 16bpc path), bit for bit.
- * csrc/data16_kernels.hip; host side phendiff_amd/data.py (resample_tables_f64 builds the tables).  Fields as in
+ * csrc/data16_kernels.hip over the resampler, checks and band kernel of csrc/pd_resample.h; host side phendiff_amd/data.py (resample_tables_f64 builds the tables).  Fields as in
  * pd_image_preprocess_bands_args, except:
  *   x: uint16, 2-byte aligned; the strides stay BYTE strides and must be even; 2 * C <= pixel_stride <= 128.
  *   coef_x double [OW][ksize_x], coef_y double [OH][ksize_y]: the float64 triangle-filter weights, normalised by the row sum, NOT rounded to

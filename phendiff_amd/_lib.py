@@ -318,27 +318,26 @@ class FcF32Args(C.Structure):
     _fields_ = [("rows", C.c_int), ("in_dim", C.c_int), ("out_dim", C.c_int), ("x", vp), ("wt", vp), ("bias", vp), ("y", vp)]
 
 
+def _image_geometry_fields(channels):
+    """The 19 leading fields the three image-preprocessing structs share (geometry, strides, tables, slots, flips); the fourth is named
+    ``Cin`` in the RGB / grey struct and ``C`` in the band structs."""
+    return [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), (channels, C.c_int), ("OH", C.c_int), ("OW", C.c_int),
+            ("out_slots", C.c_int), ("image_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_int),
+            ("ksize_x", C.c_int), ("ksize_y", C.c_int), ("x", vp), ("coef_x", vp), ("bounds_x", vp), ("coef_y", vp),
+            ("bounds_y", vp), ("out_index", vp), ("flips", vp)]
+
+
 class ImagePreprocessArgs(C.Structure):
-    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("OH", C.c_int), ("OW", C.c_int),
-                ("out_slots", C.c_int), ("image_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_int),
-                ("ksize_x", C.c_int), ("ksize_y", C.c_int), ("x", vp), ("coef_x", vp), ("bounds_x", vp), ("coef_y", vp),
-                ("bounds_y", vp), ("out_index", vp), ("flips", vp), ("mean0", C.c_float), ("mean1", C.c_float), ("mean2", C.c_float),
-                ("std0", C.c_float), ("std1", C.c_float), ("std2", C.c_float), ("y_f32", vp), ("y_u8", vp)]
+    _fields_ = _image_geometry_fields("Cin") + [("mean0", C.c_float), ("mean1", C.c_float), ("mean2", C.c_float), ("std0", C.c_float),
+                                                ("std1", C.c_float), ("std2", C.c_float), ("y_f32", vp), ("y_u8", vp)]
 
 
 class ImagePreprocessBandsArgs(C.Structure):
-    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("OH", C.c_int), ("OW", C.c_int),
-                ("out_slots", C.c_int), ("image_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_int),
-                ("ksize_x", C.c_int), ("ksize_y", C.c_int), ("x", vp), ("coef_x", vp), ("bounds_x", vp), ("coef_y", vp),
-                ("bounds_y", vp), ("out_index", vp), ("flips", vp), ("mean", vp), ("std", vp), ("y_f32", vp), ("y_u8", vp)]
+    _fields_ = _image_geometry_fields("C") + [("mean", vp), ("std", vp), ("y_f32", vp), ("y_u8", vp)]
 
 
 class ImagePreprocessBands16Args(C.Structure):
-    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("OH", C.c_int), ("OW", C.c_int),
-                ("out_slots", C.c_int), ("image_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pixel_stride", C.c_int),
-                ("ksize_x", C.c_int), ("ksize_y", C.c_int), ("x", vp), ("coef_x", vp), ("bounds_x", vp), ("coef_y", vp),
-                ("bounds_y", vp), ("out_index", vp), ("flips", vp), ("lo", vp), ("hi", vp), ("mean", vp), ("std", vp),
-                ("y_f32", vp), ("y_u16", vp)]
+    _fields_ = _image_geometry_fields("C") + [("lo", vp), ("hi", vp), ("mean", vp), ("std", vp), ("y_f32", vp), ("y_u16", vp)]
 
 
 class BandHistogram16Args(C.Structure):

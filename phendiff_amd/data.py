@@ -391,13 +391,17 @@ class ImagePreprocessor:
             flips = flips.to(dev).contiguous()
         bands = self.channels is not None
         cout = self.channels or 3
-        if bands:
-            self._mean_std_vectors()
-        if bits == 16:
-            fn, what = lib.pd_image_preprocess_bands16, "pd_image_preprocess_bands16"
-            lo, hi = self._window_vectors()
+        # the path of this call, chosen once: its entry point, the struct fields that name the channel count and the raw output, and the
+        # fields of the float tail, which are the same for every group
+        if not bands:
+            what, chan_field, raw_field = "pd_image_preprocess", "Cin", "y_u8"
+            tail = dict(zip(("mean0", "mean1", "mean2", "std0", "std1", "std2"), self.mean + self.std))
         else:
-            fn, what = (lib.pd_image_preprocess_bands, "pd_image_preprocess_bands") if bands else (lib.pd_image_preprocess, "pd_image_preprocess")
+            what, chan_field, raw_field = ("pd_image_preprocess_bands16", "C", "y_u16") if bits == 16 else ("pd_image_preprocess_bands", "C", "y_u8")
+            tail = dict(zip(("mean", "std"), (v.data_ptr() for v in self._mean_std_vectors())))
+            if bits == 16:
+                tail.update(zip(("lo", "hi"), (v.data_ptr() for v in self._window_vectors())))
+        fn = getattr(lib, what)
         esz = bits // 8
         y = torch.empty((n, cout, OH, OW), dtype=torch.float32, device=dev)
         raw = torch.empty((n, OH, OW, cout), dtype=torch.uint16 if bits == 16 else torch.uint8, device=dev) if return_raw else None
@@ -409,14 +413,8 @@ class ImagePreprocessor:
                 plan = self._plan(t.shape[1], t.shape[2], OH, OW, bits)
                 a = plan.args
                 a.N, a.out_slots = t.shape[0], n
-                if bits == 16:
-                    a.C, a.mean, a.std = cin, self._mean_std[0].data_ptr(), self._mean_std[1].data_ptr()
-                    a.lo, a.hi = lo.data_ptr(), hi.data_ptr()
-                elif bands:
-                    a.C, a.mean, a.std = cin, self._mean_std[0].data_ptr(), self._mean_std[1].data_ptr()
-                else:
-                    a.Cin = cin
-                    (a.mean0, a.mean1, a.mean2), (a.std0, a.std1, a.std2) = self.mean, self.std
+                for field, value in ((chan_field, cin), (raw_field, L.ptr(raw)), *tail.items()):
+                    setattr(a, field, value)
                 a.image_stride, a.row_stride, a.pixel_stride = s_img, s_row, s_pix
                 a.x = t.data_ptr()
                 a.out_index = a.flips = None
@@ -429,10 +427,6 @@ class ImagePreprocessor:
                     a.flips = f.data_ptr()
                     keep.append(f)
                 a.y_f32 = y.data_ptr()
-                if bits == 16:
-                    a.y_u16 = L.ptr(raw)
-                else:
-                    a.y_u8 = L.ptr(raw)
                 rc = fn(C.byref(a), st)
                 if rc == L.PD_ERR_SHAPE and bands and s_pix > cin * esz:
                     # a view into wider pixels stages whole source rows at ITS pixel stride; under a steep horizontal down-scale such a

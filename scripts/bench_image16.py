@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The 16-bit image kernels at a plate's size: N stacks of H x W x C uint16 -> OUT x OUT (docs/LAB_r17.md).  GPU only.
+"""The 16-bit image kernels at a plate's size: N stacks of H x W x C uint16 -> OUT x OUT (docs/LAB_r17.md, docs/LAB_r18.md).  GPU only.
     python scripts/bench_image16.py [N H W C OUT]          (default 32 1080 1080 5 256)
-pd_image_preprocess_bands16 beside pd_image_preprocess_bands (the same tiling on the high bytes of the same data: half the bytes, integer
+pd_image_preprocess_bands16 beside pd_image_preprocess_bands (the same tiled resampler on the high bytes of the same data: half the bytes, integer
 instead of float64 arithmetic), the two alternated in ONE process over ROUNDS rounds of ITERS launches between device events; then
 pd_band_histogram16 on the same batch, on its 12-bit version and on an all-equal batch, as bytes read per second.  Prints one JSON line."""
 import ctypes as C, json, os, statistics, sys

@@ -107,6 +107,24 @@ def test_struct_matches_header_and_is_bound():
     assert P.data.ImagePreprocessor is P.ImagePreprocessor
 
 
+def test_the_three_structs_keep_their_abi_8_layout():
+    """The three image structs are built from one shared list of leading fields: their sizes and offsets are pinned to what the C
+    structs of ABI 8 have (ints, two long longs, pointers and floats under the x86-64 rules)."""
+    import phendiff_amd._lib as L
+    rgb, bands, bands16 = L.ImagePreprocessArgs, L.ImagePreprocessBandsArgs, L.ImagePreprocessBands16Args
+    assert [C.sizeof(s) for s in (rgb, bands, bands16)] == [160, 152, 168]
+    shared = [f[0] for f in rgb._fields_[:19]]
+    assert shared[3] == "Cin" and shared[-1] == "flips"
+    for s in (bands, bands16):
+        assert [f[0] for f in s._fields_[:19]] == shared[:3] + ["C"] + shared[4:]
+    for s in (rgb, bands, bands16):
+        assert [getattr(s, f).offset for f in ("N", "OH", "image_stride", "pixel_stride", "x", "flips")] == [0, 16, 32, 48, 64, 112]
+        assert getattr(s, s._fields_[3][0]).offset == 12
+    assert [getattr(rgb, f).offset for f in ("mean0", "std0", "y_f32", "y_u8")] == [120, 132, 144, 152]
+    assert [getattr(bands, f).offset for f in ("mean", "std", "y_f32", "y_u8")] == [120, 128, 136, 144]
+    assert [getattr(bands16, f).offset for f in ("lo", "hi", "mean", "std", "y_f32", "y_u16")] == [120, 128, 136, 144, 152, 160]
+
+
 def _args(**kw):
     """Well-formed arguments of a 64 x 64 x 3 -> 32 x 32 call (the pointers are never dereferenced: validation comes first)."""
     import phendiff_amd._lib as L
