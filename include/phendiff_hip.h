@@ -39,7 +39,8 @@ extern "C" {
  * against the older header passes nothing shorter): pd_latent_chain_bwd, pd_image_preprocess, pd_attn_hd_bwd, pd_train_sample, pd_sample_stats
  * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace), pd_lp_guidance_scaled, pd_guided_step
  * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args), pd_image_preprocess_bands16, pd_band_histogram16,
- * pd_postproc_bands16 (+ their args structs). */
+ * pd_postproc_bands16 (+ their args structs), pd_abs_quantile (+ pd_abs_quantile_workspace), pd_ddim_raw_x0, pd_ddim_step_threshold (+ their
+ * args structs). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -758,6 +759,75 @@ typedef struct {
   int* overflow;                              /* device, or NULL: set to 1 if any g_unet element is not finite */
 } pd_guided_step_args;
 int pd_guided_step(const pd_guided_step_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Dynamic thresholding (added under ABI 8): DDIMScheduler(thresholding=True), diffusers' _threshold_sample on the fp32 x0 of a step
+ *     s = clamp(quantile(|x0|, ratio, per sample), min = 1, max = sample_max_value);   x0 = clamp(x0, -s, s) / s
+ * as three entry points (csrc/threshold_kernels.hip; host side phendiff_amd.schedulers.DDIMScheduler.threshold_step):
+ *     pd_ddim_raw_x0 -> pd_abs_quantile -> pd_ddim_step_threshold
+ *
+ * pd_abs_quantile: out[b] = lerp(a_(rank_lo), a_(rank_hi), weight), a_(k) the k-th smallest (0-based) of |x[b][0..n)| -- torch.quantile's
+ * 'linear' interpolation once the host has turned (n, q) into (rank_lo, rank_hi, weight) in fp32 (phendiff_amd.schedulers.quantile_rank);
+ * lerp(a, b, w) = a + w * (b - a) for w < 0.5, else b - (b - a) * (1 - w), each operation rounded on its own.
+ *   x: fp32 [B][n], dense rows; 16-byte aligned when n % 4 == 0 (16-byte loads), 4-byte aligned otherwise (element loads).
+ *   Exact selection: the bit pattern of |v| orders like the value for everything that is not a NaN, so a most-significant-digit radix select
+ *   over its 31 bits (11 + 10 + 10) finds the order statistic itself.  Per digit one histogram launch over (chunk, row) -- a workgroup
+ *   counts PD_ABS_QUANTILE_CHUNK elements of one row into LDS (integer atomics; a wave whose lanes hold one bin adds once) and adds its
+ *   non-zero bins to the row's histogram in the workspace with global integer atomics -- and one launch that finds, per row, the bin
+ *   holding each of the two ranks.  The two ranks are followed separately (two prefixes, two histograms once they part), so both order
+ *   statistics are exact wherever they fall.  Integer counting only: the result does not depend on B, on scheduling or on the replay.
+ *   -0 counts as +0; an infinity is the largest value and goes through the lerp as it is; a row that holds a NaN gives NaN and touches
+ *   no other row.
+ *   workspace: pd_abs_quantile_workspace(B, n) bytes (0 for sizes the call refuses), 4-byte aligned, contents irrelevant before and after:
+ *   the entry zeroes it on the stream, with a kernel of its own.  Launches: seven kernels for every (B, n); no host read, no allocation,
+ *   capturable.
+ *   Refused before any launch: null args / x / out / workspace, ranks outside 0 <= rank_lo <= rank_hi <= n - 1 or more than 1 apart, a
+ *   weight outside [0, 1), a misaligned x / out / workspace (PD_ERR_ARG); B, n < 1, n >= 2^31 (32-bit counters), B > 65535 (the grid's
+ *   second dimension) (PD_ERR_SHAPE). */
+#define PD_ABS_QUANTILE_CHUNK 8192
+typedef struct {
+  int64_t B, n;
+  int64_t rank_lo, rank_hi;
+  float weight;
+  const float* x;
+  float* out;
+  void* workspace;
+} pd_abs_quantile_args;
+size_t pd_abs_quantile_workspace(int64_t B, int64_t n);
+int pd_abs_quantile(const pd_abs_quantile_args* a, void* stream);
+
+/* pd_ddim_step_threshold: pd_ddim_step with the static clamp replaced by the dynamic one,
+ *     s = min(max(quantile[b], 1), sample_max_value);   x0 = min(max(x0, -s), s) / s     (IEEE division; a NaN quantile makes the row NaN)
+ * the guidance combine (both equations), the three prediction types, use_clipped_model_output (eps from the thresholded x0), in-place
+ * prev_sample == sample and the optional pred_x0 (the thresholded one) as there.  The struct is pd_ddim_step_args less clip / clip_range,
+ * in that struct's order, plus the two trailing fields.
+ * pd_ddim_raw_x0(a, x0): the unclamped x0 of the same arguments into x0 [numel] (what pd_abs_quantile reads); a->prev_sample, a->pred_x0
+ * and a->quantile are not looked at.  pd_ddim_step_threshold RECOMPUTES x0 from sample / model_out through the same inline function under
+ * the same contraction setting (csrc/pd_guided.h: ddim_x0_eps), so the x0 it thresholds is bit for bit the one whose quantile was taken --
+ * which is why the raw pass must run before an in-place update overwrites sample.
+ * Refused before any launch: null args / sample / model_out / prev_sample (x0) / quantile, guidance without weights, a prediction type
+ * outside the three, tensors that are not 16-byte aligned, a quantile that is not 4-byte aligned, sample_max_value that is not positive
+ * (PD_ERR_ARG); numel < 1, per_sample < 1 or not a divisor of numel, numel >= 2^41 (the grid) (PD_ERR_SHAPE). */
+typedef struct {
+  int64_t numel;            /* B*C*H*W */
+  int64_t per_sample;       /* C*H*W: element i belongs to row i / per_sample of quantile (and of per-sample guidance weights) */
+  int pred_type;            /* pd_pred_type */
+  int use_clipped_model_output;
+  float sqrt_a, sqrt_b;     /* as pd_ddim_step */
+  float sqrt_ap, dir_coef;
+  const float* sample;
+  const float* model_out;
+  const float* uncond_out;  /* NULL: no guidance */
+  const float* w;
+  int w_per_sample;
+  int guidance_cfg;
+  float* prev_sample;       /* out (may alias sample) */
+  float* pred_x0;           /* out or NULL: the thresholded x0 */
+  const float* quantile;    /* [numel / per_sample]: pd_abs_quantile's out, before the clamp to [1, sample_max_value] */
+  float sample_max_value;
+} pd_ddim_step_threshold_args;
+int pd_ddim_raw_x0(const pd_ddim_step_threshold_args* a, float* x0, void* stream);
+int pd_ddim_step_threshold(const pd_ddim_step_threshold_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stream capture helpers (hipGraph): the S-step sampling loop is captured once and replayed.

@@ -257,6 +257,18 @@ class GuidedStepArgs(C.Structure):
                 ("model_out", vp), ("prev_sample", vp), ("pushed", vp), ("overflow", vp)]
 
 
+class AbsQuantileArgs(C.Structure):
+    _fields_ = [("B", C.c_int64), ("n", C.c_int64), ("rank_lo", C.c_int64), ("rank_hi", C.c_int64), ("weight", C.c_float),
+                ("x", vp), ("out", vp), ("workspace", vp)]
+
+
+class DdimStepThresholdArgs(C.Structure):
+    _fields_ = [("numel", C.c_int64), ("per_sample", C.c_int64), ("pred_type", C.c_int), ("use_clipped_model_output", C.c_int),
+                ("sqrt_a", C.c_float), ("sqrt_b", C.c_float), ("sqrt_ap", C.c_float), ("dir_coef", C.c_float),
+                ("sample", vp), ("model_out", vp), ("uncond_out", vp), ("w", vp), ("w_per_sample", C.c_int),
+                ("guidance_cfg", C.c_int), ("prev_sample", vp), ("pred_x0", vp), ("quantile", vp), ("sample_max_value", C.c_float)]
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("heads", C.c_int), ("N", C.c_int), ("q", vp), ("k", vp), ("v", vp),
                 ("o", vp), ("dout", vp), ("lse", vp), ("delta", vp), ("dqkv", vp), ("slab", vp), ("slab_bytes", C.c_size_t)]
@@ -442,6 +454,10 @@ SYMBOLS = {
     "pd_guidance_apply": (C.c_int, [C.POINTER(GuidanceApplyArgs), vp]),
     "pd_lp_guidance_scaled": (C.c_int, [C.POINTER(LpGuidanceArgs), vp, vp]),
     "pd_guided_step": (C.c_int, [C.POINTER(GuidedStepArgs), vp]),
+    "pd_abs_quantile": (C.c_int, [C.POINTER(AbsQuantileArgs), vp]),
+    "pd_abs_quantile_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "pd_ddim_raw_x0": (C.c_int, [C.POINTER(DdimStepThresholdArgs), vp, vp]),
+    "pd_ddim_step_threshold": (C.c_int, [C.POINTER(DdimStepThresholdArgs), vp]),
     "pd_diffusion_loss": (C.c_int, [C.POINTER(LossArgs), vp]),
     "pd_grad_norm": (C.c_int, [vp, C.c_int64, vp, C.c_float, vp, vp, vp]),
     "pd_adamw_ema": (C.c_int, [C.POINTER(AdamWEmaArgs), vp]),

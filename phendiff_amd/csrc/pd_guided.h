@@ -13,16 +13,28 @@ namespace pd {
 // and epsilon-prediction divides by sqrt(alpha_bar) ~ 1e-5 near t = N, which amplifies a fused-vs-separate rounding
 // difference of the numerator by 1e5.  With contraction off every op is the same IEEE operation the CPU performs.
 // `A`: pd_ddim_step_args or pd_guided_step_args (the same eight fields).  Returns prev_sample; `x0` = pred_original_sample.
+// The update in its two halves, around whatever limits x0 (the static clamp below; the dynamic threshold of threshold_kernels.hip, whose
+// struct carries the same fields less clip / clip_range): the unclamped x0 with the predicted noise, and prev_sample from a limited x0.
+template <typename A>
+__device__ __forceinline__ void ddim_x0_eps(const A& a, float x, float out, float& x0, float& eps) {
+#pragma clang fp contract(off)
+  if (a.pred_type == PD_PRED_EPSILON) { x0 = (x - a.sqrt_b * out) / a.sqrt_a; eps = out; }
+  else if (a.pred_type == PD_PRED_SAMPLE) { x0 = out; eps = (x - a.sqrt_a * x0) / a.sqrt_b; }
+  else { x0 = a.sqrt_a * x - a.sqrt_b * out; eps = a.sqrt_a * out + a.sqrt_b * x; }
+}
+template <typename A>
+__device__ __forceinline__ float ddim_prev(const A& a, float x, float x0, float eps) {
+#pragma clang fp contract(off)
+  if (a.use_clipped_model_output) eps = (x - a.sqrt_a * x0) / a.sqrt_b;
+  return a.sqrt_ap * x0 + a.dir_coef * eps;
+}
 template <typename A>
 __device__ __forceinline__ float ddim_step_elem(const A& a, float x, float out, float& x0) {
 #pragma clang fp contract(off)
   float eps;
-  if (a.pred_type == PD_PRED_EPSILON) { x0 = (x - a.sqrt_b * out) / a.sqrt_a; eps = out; }
-  else if (a.pred_type == PD_PRED_SAMPLE) { x0 = out; eps = (x - a.sqrt_a * x0) / a.sqrt_b; }
-  else { x0 = a.sqrt_a * x - a.sqrt_b * out; eps = a.sqrt_a * out + a.sqrt_b * x; }
+  ddim_x0_eps(a, x, out, x0, eps);
   if (a.clip) x0 = fminf(fmaxf(x0, -a.clip_range), a.clip_range);
-  if (a.use_clipped_model_output) eps = (x - a.sqrt_a * x0) / a.sqrt_b;
-  return a.sqrt_ap * x0 + a.dir_coef * eps;
+  return ddim_prev(a, x, x0, eps);
 }
 
 // images - guidance_loss_scale * guidance_grad (utils_Img2Img.py:747-751).  The sum rounds once, then ONE fused multiply-add: the form

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as L
 from .pipeline import ConditionalDDIMPipeline, require_pil_channels
-from .schedulers import DDIMInverseScheduler
+from .schedulers import THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT, DDIMInverseScheduler, refuse_thresholding
 
 
 @torch.no_grad()
@@ -67,6 +67,7 @@ def ddib(pipe, clean_images, orig_class_labels, target_class_labels, num_inferen
     latent-diffusion branch (the reference draws it unseeded)."""
     from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
     if isinstance(pipe, CustomStableDiffusionImg2ImgPipeline):
+        refuse_thresholding(pipe.scheduler, "ddib with a latent-diffusion pipeline", THRESHOLDING_NOT_LATENT)      # (before the VAE encodes)
         clean_images, [orig_class_cond] = LDM_preprocess(pipe, clean_images, [orig_class_labels], generator)
     elif isinstance(pipe, ConditionalDDIMPipeline):
         require_pil_channels(clean_images.shape[1], output_type)      # (before the inversion: half of the trajectory)
@@ -160,6 +161,7 @@ def custom_guided_generation(pipe, input_images: torch.Tensor, target_class_labe
     ldm = isinstance(pipe, CustomStableDiffusionImg2ImgPipeline)
     if not ldm and not isinstance(pipe, ConditionalDDIMPipeline):
         raise NotImplementedError(type(pipe))
+    refuse_thresholding(pipe.scheduler, "custom_guided_generation", THRESHOLDING_NOT_GUIDED)
     if not input_images.is_cuda:
         raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the inputs to 'cuda'")
     _check_lp_exponent(p)
@@ -229,6 +231,7 @@ def linear_interp_custom_guidance_inverted_start(pipe, clean_images, orig_class_
     from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
     ldm = isinstance(pipe, CustomStableDiffusionImg2ImgPipeline)
     target_cond = target_class_labels
+    refuse_thresholding(pipe.scheduler, "the gradient-guided transfer", THRESHOLDING_NOT_GUIDED)      # (before the inversion half)
     if not ldm:
         require_pil_channels(clean_images.shape[1], output_type)
     if ldm:      # :663-671: images -> latents, both label tensors -> 77-token class embeddings

@@ -6,6 +6,15 @@ Host side (this file): the noise tables (``alphas_cumprod``), the int64 timestep
 published algorithm) and the four fp32 coefficients of one update, computed with 0-dim fp32 CPU tensors in the
 same op order as the reference so that they round identically.  Device side: ``pd_ddim_step`` /
 ``pd_add_noise`` (one fused elementwise launch per update instead of ~10).
+
+``DDIMScheduler(thresholding=True)`` (diffusers' ``_threshold_sample``, Imagen's dynamic thresholding) replaces the static clamp of a
+step by ``s = clamp(quantile(|x0|, dynamic_thresholding_ratio, per sample), 1, sample_max_value)``, ``x0 = clamp(x0, -s, s) / s``.  The
+quantile is an exact order statistic taken on the device (``pd_abs_quantile``: a radix select, no host read), so the step stays inside a
+captured trajectory: :meth:`DDIMScheduler.threshold_step` builds the launches of one such step -- ``pd_ddim_raw_x0``,
+``pd_abs_quantile``, ``pd_ddim_step_threshold`` -- and is what the eager ``step`` and the trajectories both enqueue; the host's part is
+:func:`quantile_rank`.  With the default ``sample_max_value=1.0`` s is always 1 and thresholding equals clipping to [-1, 1].
+``DDIMInverseScheduler`` does not threshold (diffusers' has ``clip_sample`` only).  ``trained_betas`` (a sequence of floats) replaces the
+named beta schedule in both.
 """
 from __future__ import annotations
 
@@ -56,7 +65,65 @@ def enforce_zero_terminal_snr(betas: torch.Tensor) -> torch.Tensor:
     return 1 - alphas
 
 
+def quantile_rank(n: int, q: float):
+    """``torch.quantile(x, q)`` ('linear') over ``n`` fp32 values as ``(lo, hi, w)``: the value is ``lerp(sorted[lo], sorted[hi], w)``.
+    torch computes the rank in the input's dtype: ``r = float32(q) * float32(n - 1)``, ``lo = floor(r)``, ``hi = ceil(r)``, ``w = r - lo``
+    (fp32).  Pure host arithmetic."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"quantile() q values must be in the range [0, 1], got {q}")
+    if not 1 <= n <= 16_000_000:
+        raise ValueError(f"quantile() over {n} elements: torch.quantile takes 1 to 16 000 000")
+    r = np.float32(q) * np.float32(n - 1)
+    lo, hi = int(np.floor(r)), int(np.ceil(r))
+    return lo, hi, float(np.float32(r - np.float32(lo)))
+
+
 _PRED = L.PD_PRED
+
+
+class ThresholdStep:
+    """The launches of one dynamically thresholded DDIM update (:meth:`DDIMScheduler.threshold_step` builds it): the argument structs,
+    and :meth:`enqueue`, the one place where the sequence is written down.  It holds the three scratch tensors the structs point at
+    (``x0_raw``, ``quant``, ``workspace``): a captured graph keeps launching into them for as long as its runner keeps this object,
+    whatever becomes of the scheduler that made it.  ``stream``: the stream the scratch set belongs to."""
+
+    def __init__(self, step: "L.DdimStepThresholdArgs", quantile: "L.AbsQuantileArgs", x0_raw: torch.Tensor, quant: torch.Tensor,
+                 workspace: torch.Tensor, stream: int):
+        self.step, self.quantile, self.stream = step, quantile, stream
+        self.x0_raw, self.quant, self.workspace = x0_raw, quant, workspace
+        assert (quantile.x, quantile.out, quantile.workspace, step.quantile) == (x0_raw.data_ptr(), quant.data_ptr(), workspace.data_ptr(),
+                                                                                 quant.data_ptr()), "the structs point at the tensors held"
+
+    def enqueue(self, st: int):
+        """The three launches on ``st``, which must be the stream the step was built for (its scratch set is that stream's own)."""
+        if int(st) != self.stream:
+            raise ValueError(f"ThresholdStep built for stream {self.stream:#x} enqueued on stream {int(st):#x}")
+        lib = L.lib()
+        L.check(lib.pd_ddim_raw_x0(C.byref(self.step), self.x0_raw.data_ptr(), st), "pd_ddim_raw_x0")      # before an in-place update
+        L.check(lib.pd_abs_quantile(C.byref(self.quantile), st), "pd_abs_quantile")
+        L.check(lib.pd_ddim_step_threshold(C.byref(self.step), st), "pd_ddim_step_threshold")
+
+
+THRESHOLD_SCRATCH_SETS = 4      # scratch sets (x0, quantiles, workspace) a scheduler keeps for re-use, by last use
+
+THRESHOLDING_NOT_GUIDED = ("the gradient-guided transfer differentiates the Lp loss of x0, and the reference defines no derivative through "
+                           "the per-sample threshold s")
+THRESHOLDING_NOT_LATENT = ("dynamic thresholding is a pixel-space method (diffusers documents it as unsuitable for latent-space models "
+                           "such as Stable Diffusion)")
+
+
+def refuse_thresholding(scheduler, who: str, why: str) -> None:
+    """What does not run a ``thresholding=True`` scheduler says so, and why, before it packs or launches anything."""
+    cfg = getattr(scheduler, "config", None)
+    if cfg.get("thresholding", False) if isinstance(cfg, dict) else getattr(cfg, "thresholding", False):
+        raise ValueError(f"{who} does not run a scheduler with thresholding=True: {why}")
+
+
+def _beta_list(trained_betas):
+    """``trained_betas`` as the config keeps it: None, or a plain list of floats (what a JSON config round-trips)."""
+    if trained_betas is None:
+        return None
+    return [float(b) for b in (trained_betas.tolist() if hasattr(trained_betas, "tolist") else trained_betas)]
 
 
 class _SchedulerBase:
@@ -69,7 +136,12 @@ class _SchedulerBase:
         c = self.config
         if c.prediction_type not in _PRED:
             raise ValueError(f"prediction_type {c.prediction_type}")
-        betas = make_betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps)
+        if c.trained_betas is not None:      # diffusers: torch.tensor(trained_betas, dtype=torch.float32), whatever beta_schedule names
+            betas = torch.tensor(c.trained_betas, dtype=torch.float32)
+            if betas.ndim != 1 or betas.numel() != c.num_train_timesteps:
+                raise ValueError(f"trained_betas: expected {c.num_train_timesteps} values, got shape {tuple(betas.shape)}")
+        else:
+            betas = make_betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps)
         if rescale:
             betas = enforce_zero_terminal_snr(betas)
         self.betas = betas
@@ -77,6 +149,7 @@ class _SchedulerBase:
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self.num_inference_steps = None
         self._coef_dev = {}
+        self._threshold_buffers = {}
 
     @classmethod
     def from_config(cls, config, **overrides):
@@ -124,6 +197,8 @@ class _SchedulerBase:
         coefficients from :meth:`step_coefficients`.  Buffers are dense fp32 tensors or raw device pointers (ints); ``numel`` /
         ``per_sample`` default to ``sample``'s and ``w_per_sample`` to "``w`` holds more than one weight", so raw pointers need them
         spelled out.  ``uncond_out`` + ``w``: the guidance combine runs inside the update (``guidance_cfg``: the "CFG" equation)."""
+        if getattr(self.config, "thresholding", False):
+            raise ValueError("this scheduler thresholds dynamically: a step is DDIMScheduler.threshold_step's launches, not one pd_ddim_step")
         sa, sb, sap, dirc, _ = self.step_coefficients(timestep, eta)
         ptr = lambda b: b.data_ptr() if torch.is_tensor(b) else b
         if numel is None:
@@ -151,9 +226,12 @@ class _SchedulerBase:
         if uncond_output is not None:
             uo = uncond_output.contiguous().float()      # the kernel reads dense fp32, as it does model_output
             wt = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
-        a = self.ddim_step_args(timestep, x, mo, prev, uo, wt, guidance_cfg, use_clipped_model_output, x0, eta)
         st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.lib().pd_ddim_step(C.byref(a), st), "pd_ddim_step")
+        if getattr(self.config, "thresholding", False):
+            self.threshold_step(timestep, x, mo, prev, st, uo, wt, guidance_cfg, use_clipped_model_output, x0, eta).enqueue(st)
+        else:
+            a = self.ddim_step_args(timestep, x, mo, prev, uo, wt, guidance_cfg, use_clipped_model_output, x0, eta)
+            L.check(L.lib().pd_ddim_step(C.byref(a), st), "pd_ddim_step")
         if eta > 0:
             if variance_noise is None:
                 variance_noise = randn_tensor(mo.shape, generator, mo.device, mo.dtype)
@@ -200,12 +278,14 @@ class DDIMScheduler(_SchedulerBase):
                  prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
                  clip_sample_range=1.0, sample_max_value=1.0, timestep_spacing="leading",
                  rescale_betas_zero_snr=False, **ignored):
-        if trained_betas is not None or thresholding:
-            raise NotImplementedError("trained_betas / dynamic thresholding are not used by PhenDiff's configs")
+        if thresholding:
+            quantile_rank(1, dynamic_thresholding_ratio)      # (a ratio outside [0, 1] is refused here, not at the first step)
+            if not float(sample_max_value) > 0:
+                raise ValueError(f"sample_max_value must be positive, got {sample_max_value}")
         cfg = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                   beta_schedule=beta_schedule, trained_betas=None, clip_sample=clip_sample,
+                   beta_schedule=beta_schedule, trained_betas=_beta_list(trained_betas), clip_sample=clip_sample,
                    set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset, prediction_type=prediction_type,
-                   thresholding=False, dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                   thresholding=bool(thresholding), dynamic_thresholding_ratio=dynamic_thresholding_ratio,
                    clip_sample_range=clip_sample_range, sample_max_value=sample_max_value,
                    timestep_spacing=timestep_spacing, rescale_betas_zero_snr=rescale_betas_zero_snr)
         self._finish_init(cfg, rescale_betas_zero_snr)
@@ -240,6 +320,42 @@ class DDIMScheduler(_SchedulerBase):
             sigma = eta * variance ** 0.5
         return a, ap, sigma
 
+    def threshold_step(self, timestep, sample, model_out, prev_sample, stream: int, uncond_out=None, w=None, guidance_cfg=False,
+                       use_clipped_model_output=False, pred_x0=None, eta=0.0) -> ThresholdStep:
+        """One dynamically thresholded update at ``timestep`` as a :class:`ThresholdStep` (``.enqueue(stream)`` launches it):
+        the raw x0 of the step into a scratch buffer, its per-sample quantile of ``|x0|`` at ``dynamic_thresholding_ratio``, then the
+        update with ``s = clamp(quantile, 1, sample_max_value)`` in the clamp's place (``prev_sample`` may be ``sample``).  ``sample``
+        is a dense fp32 (B, ...) tensor; the other buffers are such tensors or raw device pointers, as for :meth:`ddim_step_args`.
+        The scratch x0, the (B,) quantiles and the select's workspace come from the scheduler, one set per (B, n, device, stream): a
+        capture finds them allocated, and runners that replay on their own streams do not share them.  The scheduler keeps the
+        :data:`THRESHOLD_SCRATCH_SETS` sets used last (4 (B n + B) + 24 640 B bytes each) and lets older ones go; the returned step
+        holds its set itself, so whoever keeps the step (a runner's captured graph) keeps the memory it launches into."""
+        c = self.config
+        B, n = sample.shape[0], sample[0].numel()
+        key = (B, n, sample.device, int(stream))
+        bufs = self._threshold_buffers.pop(key, None)
+        if bufs is None:
+            ws = L.lib().pd_abs_quantile_workspace(B, n)
+            if ws == 0:
+                raise ValueError(f"dynamic thresholding: no per-sample quantile over a ({B}, {n}) batch")
+            bufs = (torch.empty((B, n), dtype=torch.float32, device=sample.device), torch.empty((B,), dtype=torch.float32, device=sample.device),
+                    torch.empty((ws,), dtype=torch.uint8, device=sample.device))
+        self._threshold_buffers[key] = bufs                     # (re-inserted: the dict's order is the order of last use)
+        while len(self._threshold_buffers) > THRESHOLD_SCRATCH_SETS:
+            del self._threshold_buffers[next(iter(self._threshold_buffers))]
+        x0_raw, quant, workspace = bufs
+        sa, sb, sap, dirc, _ = self.step_coefficients(timestep, eta)
+        ptr = lambda b: b.data_ptr() if torch.is_tensor(b) else b
+        step = L.DdimStepThresholdArgs(
+            numel=B * n, per_sample=n, pred_type=_PRED[c.prediction_type], use_clipped_model_output=int(bool(use_clipped_model_output)),
+            sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=ptr(sample), model_out=ptr(model_out), uncond_out=ptr(uncond_out),
+            w=ptr(w), w_per_sample=int(torch.is_tensor(w) and w.numel() > 1), guidance_cfg=int(guidance_cfg), prev_sample=ptr(prev_sample),
+            pred_x0=ptr(pred_x0), quantile=quant.data_ptr(), sample_max_value=float(c.sample_max_value))
+        lo, hi, wgt = quantile_rank(n, float(c.dynamic_thresholding_ratio))
+        q = L.AbsQuantileArgs(B=B, n=n, rank_lo=lo, rank_hi=hi, weight=wgt, x=x0_raw.data_ptr(), out=quant.data_ptr(),
+                              workspace=workspace.data_ptr())
+        return ThresholdStep(step, q, x0_raw, quant, workspace, int(stream))
+
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False,
              generator=None, variance_noise=None, return_dict: bool = True):
         prev, x0 = self._device_step(model_output, timestep, sample, eta, use_clipped_model_output, generator, variance_noise)
@@ -262,11 +378,9 @@ class DDIMInverseScheduler(_SchedulerBase):
             set_alpha_to_zero = kwargs["set_alpha_to_one"]
         if variant not in ("0.18.2", "0.20+"):
             raise ValueError("variant must be '0.18.2' or '0.20+'")
-        if trained_betas is not None:
-            raise NotImplementedError("trained_betas")
         self.variant = variant
         cfg = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                   beta_schedule=beta_schedule, trained_betas=None, clip_sample=clip_sample,
+                   beta_schedule=beta_schedule, trained_betas=_beta_list(trained_betas), clip_sample=clip_sample,
                    set_alpha_to_zero=set_alpha_to_zero, steps_offset=steps_offset, prediction_type=prediction_type,
                    clip_sample_range=clip_sample_range, timestep_spacing=timestep_spacing,
                    rescale_betas_zero_snr=rescale_betas_zero_snr)

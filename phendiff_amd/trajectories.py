@@ -20,7 +20,8 @@ from . import _lib as L
 from . import img2img as E
 from .img2img import GUIDANCE_MIN_GRAD_SCALE, _LpGuidance, _check_lp_exponent
 from .pipeline import ConditionalDDIMPipeline
-from .schedulers import DDIMInverseScheduler, randn_tensor
+from .schedulers import (THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT, DDIMInverseScheduler, ThresholdStep, randn_tensor,
+                         refuse_thresholding)
 
 
 def _identity_rows(cond: torch.Tensor, B: int, tdim: int, device) -> torch.Tensor:
@@ -149,6 +150,7 @@ def _check_guided_request(pipe, pipe_type, p):
     _check_lp_exponent(p)
     if not isinstance(pipe, pipe_type):
         raise NotImplementedError(f"{type(pipe).__name__}: this runner drives a {pipe_type.__name__}")
+    refuse_thresholding(pipe.scheduler, "the gradient-guided transfer", THRESHOLDING_NOT_GUIDED)
     if pipe.unet.device.type != "cuda":
         raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the pipeline to 'cuda'")
 
@@ -266,15 +268,26 @@ class _PixelTrajectory(_TrajectoryRunner):
     def _snapshot(self, st):
         L.check(self.lib.pd_add_noise(C.byref(self.snapshot_args), st), "pd_add_noise")
 
+    def _forward_step_args(self, sched, t, uncond_out=None, w=None, guidance_cfg=False):
+        """The in-place update of ``x`` at ``t`` under the forward scheduler: ``pd_ddim_step``'s arguments, or -- ``thresholding=True`` --
+        the scheduler's :class:`~phendiff_amd.schedulers.ThresholdStep` on the runner's stream (its buffers exist before the capture)."""
+        if sched.config.thresholding:
+            return sched.threshold_step(t, self.x, self.model_out, self.x, self.stream.cuda_stream, uncond_out, w, guidance_cfg)
+        return sched.ddim_step_args(t, self.x, self.model_out, self.x, uncond_out, w, guidance_cfg)
+
     def _ddim_steps(self, st, step_args, first: int = 0, uncond=None):
         """Per entry of ``step_args``: the UNet from ``x`` into ``model_out`` under row block ``first + i`` of ``temb``, then its
-        ``pd_ddim_step``.  ``uncond = (table, out)``: a second evaluation under the same row block of another table before the update."""
+        ``pd_ddim_step`` (or the launches of its thresholded form, the ones the eager ``step`` enqueues).  ``uncond = (table, out)``: a
+        second evaluation under the same row block of another table before the update."""
         plan, step_bytes = self.plan, self.B * self.plan.w.proj_dim * 4
         for i, a in enumerate(step_args, first):
             plan.run(self.x.data_ptr(), self.temb.data_ptr() + i * step_bytes, self.model_out.data_ptr(), st)
             if uncond is not None:
                 plan.run(self.x.data_ptr(), uncond[0].data_ptr() + i * step_bytes, uncond[1].data_ptr(), st)
-            L.check(self.lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
+            if isinstance(a, ThresholdStep):
+                a.enqueue(st)
+            else:
+                L.check(self.lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
 
     def _postproc(self, st):
         L.check(self.lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
@@ -300,7 +313,7 @@ class DDIBGraph(_PixelTrajectory):
             pipe, self.S, variant, lambda fwd: fwd.timesteps[fwd.timesteps <= fwd.config.num_train_timesteps * (1 - 0)])
         self._class_table(self.inv_ts + self.gen_ts)
         self.inv_args = [self.inv.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.inv_ts]
-        self.gen_args = [fwd.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.gen_ts]
+        self.gen_args = [self._forward_step_args(fwd, t) for t in self.gen_ts]
         self._inverted_snapshot()
         self._capture()
 
@@ -403,8 +416,8 @@ class CFGForwardStartGraph(_PixelTrajectory):
         self.noise_args = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0,
                                          x=self.clean.data_ptr(), noise=self.noise.data_ptr(), sa=sa.data_ptr(),
                                          sb=sb.data_ptr(), out=self.x.data_ptr())
-        self.step_args = [sch.ddim_step_args(t, self.x, self.model_out, self.x, self.uncond[1] if do_cfg else None, self.w_dev,
-                                             guidance_cfg=guidance_eqn == "CFG") for t in self.ts]
+        self.step_args = [self._forward_step_args(sch, t, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
+                          for t in self.ts]
         self._capture()
 
     def _enqueue(self, st):
@@ -504,6 +517,7 @@ class _LatentTrajectory(_TrajectoryRunner):
     UNet's input-gradient plan (``gplan``: a guided half runs on it)."""
 
     def __init__(self, pipe, batch_size, num_inference_steps, height, width, device, use_graph, input_grad=False):
+        refuse_thresholding(pipe.scheduler, type(self).__name__, THRESHOLDING_NOT_LATENT)
         self.pipe = pipe
         unet, vae = pipe.unet, pipe.vae
         super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
