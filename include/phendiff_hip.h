@@ -40,7 +40,7 @@ extern "C" {
  * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace), pd_lp_guidance_scaled, pd_guided_step
  * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args), pd_image_preprocess_bands16, pd_band_histogram16,
  * pd_postproc_bands16 (+ their args structs), pd_abs_quantile (+ pd_abs_quantile_workspace), pd_ddim_raw_x0, pd_ddim_step_threshold (+ their
- * args structs). */
+ * args structs), pd_tile_gather, pd_tile_blend (+ their args structs). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -828,6 +828,47 @@ typedef struct {
 } pd_ddim_step_threshold_args;
 int pd_ddim_raw_x0(const pd_ddim_step_threshold_args* a, float* x0, void* stream);
 int pd_ddim_step_threshold(const pd_ddim_step_threshold_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Tiled trajectories (added under ABI 8; csrc/tile_kernels.hip, host side phendiff_amd.tiling): the working sample is a canvas
+ * (B, C, Hc, Wc), the UNet evaluates overlapping th x tw tiles, their outputs are blended into one canvas-sized model output.  fp32 NCHW.
+ * The grid is a tensor product of two axes; per axis with canvas extent L, tile extent t and stride s = t - overlap (1 <= s <= t):
+ *     n = ceil((L - t) / s) + 1 tiles,   tile k starts at min(k * s, L - t)   (the last one flush with the edge)
+ * so any number of tiles may cover a position.  Tile order everywhere: image b, then ky, then kx; T = B * nty * ntx.
+ *
+ * pd_tile_gather: tiles [first, first + count) of the canvas -> tiles [count][C][th][tw], a copy (bit for bit).
+ * pd_tile_blend: writes EVERY element of out [B][C][Hc][Wc] from the T tile outputs and the per-axis weight tables wy [nty][th],
+ * wx [ntx][tw] (phendiff_amd.tiling.TileGrid: normalised so that the weights of a position sum to one on each axis):
+ *     out(b, c, y, x) = sum over the covering tiles, ky ascending then kx ascending, of (wy[ky][y - y0] * wx[kx][x - x0]) * tile(...)
+ * with the weight product, each term and each addition rounded to fp32 on their own, the first term taken as it is.  Gather form: one
+ * thread per output position (or 4 of a row) reads the tiles that cover it -- no atomics, no cleared memory, a function of the inputs alone.
+ * Both take 16 bytes per lane where every origin along x, Wc and tw are multiples of 4 and the pointers are 16-byte aligned, 4 bytes
+ * otherwise.  One launch each; no host read, no allocation, capturable.
+ * Refused before any launch: null args / pointers, pointers that are not 4-byte aligned (PD_ERR_ARG); a size < 1, a tile larger than the
+ * canvas, a stride outside [1, tile], tile counts that are not the grid's, first < 0, count < 1, first + count > T, a canvas or a tile batch
+ * of 2^31 elements or more (32-bit offsets) (PD_ERR_SHAPE). */
+typedef struct {
+  int B, C, Hc, Wc;         /* canvas */
+  int th, tw;               /* tile extent */
+  int nty, ntx;             /* tiles per axis */
+  int sy, sx;               /* stride per axis: tile - overlap */
+  int first, count;         /* tiles [first, first + count) of T */
+  const float* canvas;      /* [B][C][Hc][Wc] */
+  float* tiles;             /* out [count][C][th][tw] */
+} pd_tile_gather_args;
+int pd_tile_gather(const pd_tile_gather_args* a, void* stream);
+
+typedef struct {
+  int B, C, Hc, Wc;
+  int th, tw;
+  int nty, ntx;
+  int sy, sx;
+  const float* tiles;       /* [T][C][th][tw] */
+  const float* wy;          /* [nty][th] */
+  const float* wx;          /* [ntx][tw] */
+  float* out;               /* [B][C][Hc][Wc] */
+} pd_tile_blend_args;
+int pd_tile_blend(const pd_tile_blend_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stream capture helpers (hipGraph): the S-step sampling loop is captured once and replayed.

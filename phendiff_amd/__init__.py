@@ -11,8 +11,11 @@ from .schedulers import DDIMScheduler, DDIMInverseScheduler, quantile_rank  # no
 from .pipeline import ConditionalDDIMPipeline, ImagePipelineOutput  # noqa: F401
 from .img2img import (inversion, ddib, inverted_regeneration, classifier_free_guidance_forward_start,  # noqa: F401
                       shard_batches, swap_binary_labels, custom_guided_generation,
-                      linear_interp_custom_guidance_inverted_start, encode_to_latents, decode_to_images, LDM_preprocess, tensor_to_PIL)
-from .trajectories import DDIBGraph, CFGForwardStartGraph, SDDDIBGraph, GuidedTransferGraph, SDGuidedTransferGraph  # noqa: F401
+                      linear_interp_custom_guidance_inverted_start, encode_to_latents, decode_to_images, LDM_preprocess, tensor_to_PIL,
+                      tiled_inversion, tiled_ddib, tiled_inverted_regeneration, TiledTransferOutput)
+from .trajectories import DDIBGraph, CFGForwardStartGraph, SDDDIBGraph, GuidedTransferGraph, SDGuidedTransferGraph, TiledDDIBGraph  # noqa: F401
+from .tiling import TileGrid  # noqa: F401
+from . import tiling  # noqa: F401
 from .configs import UNET_CONFIGS, SCHEDULER_CONFIGS, SD15_UNET_CONFIG  # noqa: F401
 from . import configs  # noqa: F401
 from . import diagnostics  # noqa: F401

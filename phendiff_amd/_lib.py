@@ -269,6 +269,18 @@ class DdimStepThresholdArgs(C.Structure):
                 ("guidance_cfg", C.c_int), ("prev_sample", vp), ("pred_x0", vp), ("quantile", vp), ("sample_max_value", C.c_float)]
 
 
+_TILE_GRID_FIELDS = [("B", C.c_int), ("C", C.c_int), ("Hc", C.c_int), ("Wc", C.c_int), ("th", C.c_int), ("tw", C.c_int), ("nty", C.c_int),
+                     ("ntx", C.c_int), ("sy", C.c_int), ("sx", C.c_int)]
+
+
+class TileGatherArgs(C.Structure):
+    _fields_ = _TILE_GRID_FIELDS + [("first", C.c_int), ("count", C.c_int), ("canvas", vp), ("tiles", vp)]
+
+
+class TileBlendArgs(C.Structure):
+    _fields_ = _TILE_GRID_FIELDS + [("tiles", vp), ("wy", vp), ("wx", vp), ("out", vp)]
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("heads", C.c_int), ("N", C.c_int), ("q", vp), ("k", vp), ("v", vp),
                 ("o", vp), ("dout", vp), ("lse", vp), ("delta", vp), ("dqkv", vp), ("slab", vp), ("slab_bytes", C.c_size_t)]
@@ -458,6 +470,8 @@ SYMBOLS = {
     "pd_abs_quantile_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
     "pd_ddim_raw_x0": (C.c_int, [C.POINTER(DdimStepThresholdArgs), vp, vp]),
     "pd_ddim_step_threshold": (C.c_int, [C.POINTER(DdimStepThresholdArgs), vp]),
+    "pd_tile_gather": (C.c_int, [C.POINTER(TileGatherArgs), vp]),
+    "pd_tile_blend": (C.c_int, [C.POINTER(TileBlendArgs), vp]),
     "pd_diffusion_loss": (C.c_int, [C.POINTER(LossArgs), vp]),
     "pd_grad_norm": (C.c_int, [vp, C.c_int64, vp, C.c_float, vp, vp, vp]),
     "pd_adamw_ema": (C.c_int, [C.POINTER(AdamWEmaArgs), vp]),

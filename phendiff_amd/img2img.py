@@ -7,19 +7,23 @@ Two execution modes, same arithmetic:
   * eager  -- this module: ``inversion`` / ``ddib`` walk the reference's Python loops over the drop-in objects;
   * graph  -- ``trajectories.py``: :class:`~phendiff_amd.trajectories.DDIBGraph` captures the whole 2*S-step trajectory (time/class
     embedding table, 2*S UNet evaluations, 2*S fused scheduler updates, post-processing) into ONE hipGraph and replays it per batch.
+``tiled_inversion`` / ``tiled_ddib`` / ``tiled_inverted_regeneration`` run the same trajectories on a canvas larger than the size the model
+was trained at (``tiling.py``: overlapping tiles through the UNet, blended into one model output per step); captured:
+:class:`~phendiff_amd.trajectories.TiledDDIBGraph`.
 The gradient-guided transfer (``:651-760``) has the same two modes: ``custom_guided_generation`` here, ``GuidedTransferGraph`` /
 ``SDGuidedTransferGraph`` there; what both need to build a step's ``pd_lp_guidance`` arguments (:class:`_LpGuidance`) lives here.
 """
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
 
 from . import _lib as L
 from .pipeline import ConditionalDDIMPipeline, require_pil_channels
-from .schedulers import THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT, DDIMInverseScheduler, refuse_thresholding
+from .schedulers import THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT, DDIMInverseScheduler, quantile_rank, refuse_thresholding
 
 
 @torch.no_grad()
@@ -88,6 +92,177 @@ def ddib(pipe, clean_images, orig_class_labels, target_class_labels, num_inferen
 def inverted_regeneration(pipe, clean_images, orig_class_labels, num_inference_steps: int, **kw):
     """``"inverted_regeneration"`` (utils_Img2Img.py:374-384): DDIB with the original class as target."""
     return ddib(pipe, clean_images, orig_class_labels, orig_class_labels, num_inference_steps, **kw)
+
+
+# ---- tiled trajectories: a field of view larger than the training size -------------------------------------------------------------------
+class TiledTransferOutput(SimpleNamespace):
+    """What a tiled transfer returns: ``.images`` (NHWC float in [0, 1]), ``.images_u8`` (its ``uint8`` quantisation), ``.inverted`` (the
+    canvas at the end of the inversion) and ``.sample`` (the canvas at the end of the transfer, in the model's range: what
+    ``ImagePreprocessor.restore`` takes) -- the last two NCHW on the device."""
+
+
+def _check_tiled_request(pipe, canvas_shape, who: str):
+    """What a tiled trajectory refuses before it packs a weight, builds a plan or launches anything."""
+    from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
+    if isinstance(pipe, CustomStableDiffusionImg2ImgPipeline):
+        raise NotImplementedError(f"{who}: tiled trajectories run in image space (ConditionalDDIMPipeline); the latent tier is not tiled")
+    if not isinstance(pipe, ConditionalDDIMPipeline):
+        raise NotImplementedError(f"{who}: {type(pipe).__name__} (a ConditionalDDIMPipeline is needed; the gradient-guided transfer is not tiled)")
+    if len(canvas_shape) != 4:
+        raise ValueError(f"{who}: expected (B, C, H, W) images, got {tuple(canvas_shape)}")
+    c, u = pipe.scheduler.config, pipe.unet.config
+    if u.in_channels != u.out_channels or canvas_shape[1] != u.in_channels:
+        raise ValueError(f"{who}: {canvas_shape[1]}-channel images for a model with in_channels = {u.in_channels}, out_channels = "
+                         f"{u.out_channels} (the blended model output updates the canvas: all three must agree)")
+    if getattr(c, "thresholding", False):      # the quantile of a step is taken over the whole image, not per tile
+        n = int(canvas_shape[1]) * int(canvas_shape[2]) * int(canvas_shape[3])
+        try:
+            quantile_rank(n, float(c.dynamic_thresholding_ratio))
+        except ValueError as e:
+            raise ValueError(f"{who}: thresholding=True takes the quantile of a step over the whole {tuple(canvas_shape[1:])} canvas: {e}") from None
+
+
+def tile_conditioning(cond: torch.Tensor, tiles_per_image: int) -> torch.Tensor:
+    """A batch's class conditioning (labels, label values or embedding rows) per tile: a tile carries its image's class."""
+    return cond.repeat_interleave(tiles_per_image, dim=0)
+
+
+class _TiledForward:
+    """One evaluation of the UNet over a canvas, for the eager loop and the captured one: ``pd_tile_gather`` of all ``T = B * nty * ntx``
+    tiles into ``tiles_in``, the launch plan over chunks of ``tile_batch`` tiles (default ``min(T, unet.max_batch(th, tw))``; a short last
+    chunk runs on a second plan of its own size, so no slot is ever padded), ``pd_tile_blend`` of ``tiles_out`` into the model output.
+    ``bind(canvas, model_out)`` fixes the two canvas-sized tensors; ``evaluate(temb_ptr, st)`` launches, ``temb_ptr``: the [T][proj_dim]
+    projection table of the step (tile order: image, then ky, then kx)."""
+
+    def __init__(self, unet, grid, batch_size: int, tile_batch, device, private_plan: bool = False):
+        self.lib, self.grid, self.B = L.lib(), grid, batch_size
+        self.T = T = batch_size * grid.tiles_per_image
+        most = unet.max_batch(grid.th, grid.tw)
+        tb = min(T, most) if tile_batch is None else int(tile_batch)
+        if not 1 <= tb <= most:
+            raise ValueError(f"tile_batch {tile_batch}: one launch plan holds 1 to {most} tiles of {grid.th}x{grid.tw}")
+        self.tile_batch = tb = min(tb, T)
+        self.chunks = [(first, min(tb, T - first)) for first in range(0, T, tb)]
+        make = unet.new_plan if private_plan else unet.plan_for
+        self.plans = {n: make(n, grid.th, grid.tw, device) for n in sorted({n for _, n in self.chunks}, reverse=True)}
+        self.plan = self.plans[tb]
+        ch = unet.config.in_channels
+        self.tiles_in = torch.empty((T, ch, grid.th, grid.tw), dtype=torch.float32, device=device)
+        self.tiles_out = torch.empty_like(self.tiles_in)
+        self.tile_bytes, self.row_bytes = 4 * ch * grid.th * grid.tw, 4 * self.plan.w.proj_dim
+        self.gather_args = self.blend_args = None
+
+    def bind(self, canvas: torch.Tensor, model_out: torch.Tensor):
+        self.gather_args = self.grid.gather_args(canvas, self.tiles_in)
+        self.blend_args = self.grid.blend_args(self.tiles_out, model_out)
+        self._bound = (canvas, model_out)
+        return self
+
+    def evaluate(self, temb_ptr: int, st: int):
+        L.check(self.lib.pd_tile_gather(C.byref(self.gather_args), st), "pd_tile_gather")
+        src, dst = self.tiles_in.data_ptr(), self.tiles_out.data_ptr()
+        for first, count in self.chunks:
+            self.plans[count].run(src + first * self.tile_bytes, temb_ptr + first * self.row_bytes, dst + first * self.tile_bytes, st)
+        L.check(self.lib.pd_tile_blend(C.byref(self.blend_args), st), "pd_tile_blend")
+
+
+class _TiledEager:
+    """The eager tiled loop: the canvas ``x`` (updated in place), the blended ``model_out`` and :class:`_TiledForward` between them."""
+
+    def __init__(self, pipe, images: torch.Tensor, tile, overlap, tile_batch, who: str):
+        from .tiling import TileGrid
+        _check_tiled_request(pipe, images.shape, who)
+        self.pipe, unet = pipe, pipe.unet
+        B, _, H, W = images.shape
+        self.grid = TileGrid(H, W, tile, default_overlap(tile) if overlap is None else overlap)
+        if not images.is_cuda:
+            raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the inputs to 'cuda'")
+        self.x = images.detach().to(torch.float32).contiguous().clone()
+        self.model_out = torch.empty_like(self.x)
+        self.dev = self.x.device
+        self.fwd = _TiledForward(unet, self.grid, B, tile_batch, self.dev).bind(self.x, self.model_out)
+        T = self.fwd.T
+        self.ts = torch.empty((T,), dtype=torch.float32, device=self.dev)
+        self.temb = torch.empty((T, self.fwd.plan.w.proj_dim), dtype=torch.float32, device=self.dev)
+        self.label_dtype = torch.int64 if unet.config.class_embed_type is None else torch.float32
+
+    def steps(self, sched, timesteps, class_labels: torch.Tensor):
+        """Per timestep: the tiled UNet evaluation under ``class_labels`` (one entry per image), then the scheduler's own update of the
+        canvas -- ``pd_ddim_step``, or the launches of ``threshold_step`` where the scheduler thresholds (quantile over the whole image)."""
+        fwd, x, out = self.fwd, self.x, self.model_out
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        labels = tile_conditioning(class_labels.to(device=self.dev, dtype=self.label_dtype), self.grid.tiles_per_image).contiguous()
+        for t in timesteps:
+            self.ts.fill_(float(t))
+            fwd.plan.temb_rows(self.ts, labels, None, st, rows=fwd.T, out=self.temb)
+            fwd.evaluate(self.temb.data_ptr(), st)
+            if getattr(sched.config, "thresholding", False):
+                sched.threshold_step(t, x, out, x, st).enqueue(st)
+            else:
+                L.check(fwd.lib.pd_ddim_step(C.byref(sched.ddim_step_args(t, x, out, x)), st), "pd_ddim_step")
+
+    def invert(self, class_labels, num_inference_steps: int, variant: str):
+        inv = DDIMInverseScheduler.from_config(self.pipe.scheduler.config, variant=variant)
+        inv.set_timesteps(num_inference_steps)
+        self.steps(inv, inv.timesteps, class_labels)
+
+    def generate(self, class_labels, num_inference_steps: int):
+        fwd = self.pipe.scheduler
+        fwd.set_timesteps(num_inference_steps)
+        self.steps(fwd, fwd.timesteps, class_labels)      # (frac_diffusion_skipped = 0: every timestep, pipeline :250-258)
+
+    def postproc(self):
+        """``(x / 2 + .5).clamp(0, 1)`` NCHW -> NHWC, float and uint8, in one ``pd_postproc``."""
+        B, Cc, H, W = self.x.shape
+        f32 = torch.empty((B, H, W, Cc), dtype=torch.float32, device=self.dev)
+        u8 = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=self.dev)
+        a = L.PostprocArgs(B=B, C=Cc, H=H, W=W, x=self.x.data_ptr(), out_f32=f32.data_ptr(), out_u8=u8.data_ptr())
+        L.check(self.fwd.lib.pd_postproc(C.byref(a), torch.cuda.current_stream(self.dev).cuda_stream), "pd_postproc")
+        return f32, u8
+
+
+def default_overlap(tile):
+    """An eighth of the tile on each axis (256 -> 32), what the tiled functions take when no overlap is given."""
+    return tuple(int(t) // 8 for t in tile) if isinstance(tile, (tuple, list)) else int(tile) // 8
+
+
+@torch.no_grad()
+def tiled_inversion(pipe, input_images: torch.Tensor, class_labels: torch.Tensor, num_inference_steps: int, tile, overlap=None,
+                    tile_batch: Optional[int] = None, variant: str = "0.18.2") -> torch.Tensor:
+    """:func:`inversion` of a canvas larger than the training size (``ConditionalDDIMPipeline`` only): at every step the UNet evaluates
+    the overlapping ``tile`` x ``tile`` tiles of the canvas (:class:`~phendiff_amd.tiling.TileGrid`; ``overlap`` defaults to an eighth of
+    the tile), their outputs are blended into one canvas-sized model output and the inverse scheduler steps on the canvas.  ``tile_batch``:
+    tiles per launch-plan call (default: all of them, up to ``unet.max_batch``); the result does not depend on it.  On a canvas of one
+    tile this is :func:`inversion`, bit for bit."""
+    run = _TiledEager(pipe, input_images, tile, overlap, tile_batch, "tiled_inversion")
+    run.invert(class_labels, num_inference_steps, variant)
+    return run.x
+
+
+@torch.no_grad()
+def tiled_ddib(pipe, clean_images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor,
+               num_inference_steps: int, tile, overlap=None, tile_batch: Optional[int] = None, variant: str = "0.18.2",
+               output_type: str = "numpy") -> TiledTransferOutput:
+    """:func:`ddib` of a canvas larger than the training size, tiled as in :func:`tiled_inversion`: inversion under the original class,
+    denoising under the target class.  With ``thresholding=True`` the forward scheduler takes its quantile over the whole image (a canvas
+    above ``quantile_rank``'s 16 000 000 elements is refused before anything is launched).  ``output_type``: "numpy" (host arrays, as
+    :func:`ddib` returns them) or "pt" (device tensors); ``.inverted`` stays on the device either way."""
+    if output_type not in ("numpy", "pt"):
+        raise ValueError(f'output_type must be "numpy" or "pt", got {output_type!r}')
+    run = _TiledEager(pipe, clean_images, tile, overlap, tile_batch, "tiled_ddib")
+    run.invert(orig_class_labels, num_inference_steps, variant)
+    inverted = run.x.clone()
+    run.generate(target_class_labels, num_inference_steps)
+    images, images_u8 = run.postproc()
+    if output_type == "numpy":
+        images, images_u8 = images.cpu().numpy(), images_u8.cpu().numpy()
+    return TiledTransferOutput(images=images, images_u8=images_u8, inverted=inverted, sample=run.x)
+
+
+@torch.no_grad()
+def tiled_inverted_regeneration(pipe, clean_images, orig_class_labels, num_inference_steps: int, tile, **kw) -> TiledTransferOutput:
+    """:func:`inverted_regeneration` of a canvas: :func:`tiled_ddib` with the original class as target."""
+    return tiled_ddib(pipe, clean_images, orig_class_labels, orig_class_labels, num_inference_steps, tile, **kw)
 
 
 @torch.no_grad()

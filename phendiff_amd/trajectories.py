@@ -6,7 +6,9 @@ no Python launch cost (~120 launches x 2*S per batch otherwise).  Same arithmeti
     in latent space (``CustomStableDiffusionImg2ImgPipeline``) once: their buffers and argument structs, and the launches of each phase;
   * :class:`_ClassRows` (class conditioning of the pixel UNet) and :class:`_GuidedSteps` (the gradient-guided half) are phases both kinds use;
   * the runners -- :class:`DDIBGraph`, :class:`CFGForwardStartGraph`, :class:`GuidedTransferGraph`, :class:`SDDDIBGraph`,
-    :class:`SDGuidedTransferGraph` -- say in ``_enqueue`` which phases they string together.
+    :class:`SDGuidedTransferGraph` -- say in ``_enqueue`` which phases they string together;
+  * :class:`TiledDDIBGraph` is :class:`DDIBGraph`'s string of phases on a canvas larger than the training size: its UNet phase
+    (``_unet``) is ``img2img._TiledForward`` -- gather the tiles, the plan over them, blend -- and its class table has a row per tile.
 
 Inside a capture every torch call is a device-to-device operation between pre-allocated buffers on the runner's stream; nothing allocates.
 """
@@ -229,10 +231,7 @@ class _PixelTrajectory(_TrajectoryRunner):
         unet = pipe.unet
         super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
         B, H, W, dev = self.B, self.H, self.W, self.device
-        if B > unet.max_batch(H, W):
-            raise ValueError(f"batch_size {B} exceeds what one launch plan holds at {H}x{W} ({unet.max_batch(H, W)} images)")
-        self.plan = unet.new_plan(B, H, W, dev) if private_plan else unet.plan_for(B, H, W, dev)
-        self.gplan = unet.input_grad_plan(B, H, W, dev) if input_grad else None
+        self._make_plans(private_plan, input_grad)
         # (both plans before any buffer: which freed block a later allocation reuses follows this order, and scripts/trajectory_signature.py
         # compares the aliasing of pointers across revisions)
         self.x = torch.empty((B, unet.config.in_channels, H, W), dtype=torch.float32, device=dev)
@@ -243,6 +242,20 @@ class _PixelTrajectory(_TrajectoryRunner):
         self.post_args = L.PostprocArgs(B=B, C=self.x.shape[1], H=H, W=W, x=self.x.data_ptr(), out_f32=self.images.data_ptr(),
                                         out_u8=self.images_u8.data_ptr())
 
+    def _make_plans(self, private_plan, input_grad):
+        """``plan`` (and ``gplan``): one launch plan of the whole batch at the size of the working buffer."""
+        unet, B, H, W, dev = self.pipe.unet, self.B, self.H, self.W, self.device
+        if B > unet.max_batch(H, W):
+            raise ValueError(f"batch_size {B} exceeds what one launch plan holds at {H}x{W} ({unet.max_batch(H, W)} images)")
+        self.plan = unet.new_plan(B, H, W, dev) if private_plan else unet.plan_for(B, H, W, dev)
+        self.gplan = unet.input_grad_plan(B, H, W, dev) if input_grad else None
+
+    rows_per_step = property(lambda self: self.B, doc="conditioning rows of one step: one per UNet sample (the images of the batch)")
+
+    def _unet(self, st, temb_ptr, out_ptr):
+        """One UNet evaluation of ``x`` under the row block at ``temb_ptr`` into the canvas-sized tensor at ``out_ptr``."""
+        self.plan.run(self.x.data_ptr(), temb_ptr, out_ptr, st)
+
     def _image_outputs(self):
         """``.images`` (NHWC float in [0, 1]) and ``.images_u8`` of the whole batch."""
         shape = (self.B, self.H, self.W, self.pipe.unet.config.in_channels)
@@ -252,8 +265,8 @@ class _PixelTrajectory(_TrajectoryRunner):
     def _class_table(self, timesteps):
         """The static conditioning of a run of steps: per (step, image) row its timestep and class (``_fill`` writes the classes), and
         the projection table ``temb`` one captured ``pd_temb`` makes of them."""
-        rows = len(timesteps) * self.B
-        self.ts_rows = torch.tensor(timesteps, dtype=torch.float32).repeat_interleave(self.B).to(self.device)
+        rows = len(timesteps) * self.rows_per_step
+        self.ts_rows = torch.tensor(timesteps, dtype=torch.float32).repeat_interleave(self.rows_per_step).to(self.device)
         self.class_rows = _ClassRows(self.plan, rows, self.device)
         self.temb = torch.empty((rows, self.plan.w.proj_dim), dtype=torch.float32, device=self.device)
 
@@ -279,11 +292,11 @@ class _PixelTrajectory(_TrajectoryRunner):
         """Per entry of ``step_args``: the UNet from ``x`` into ``model_out`` under row block ``first + i`` of ``temb``, then its
         ``pd_ddim_step`` (or the launches of its thresholded form, the ones the eager ``step`` enqueues).  ``uncond = (table, out)``: a
         second evaluation under the same row block of another table before the update."""
-        plan, step_bytes = self.plan, self.B * self.plan.w.proj_dim * 4
+        step_bytes = self.rows_per_step * self.plan.w.proj_dim * 4
         for i, a in enumerate(step_args, first):
-            plan.run(self.x.data_ptr(), self.temb.data_ptr() + i * step_bytes, self.model_out.data_ptr(), st)
+            self._unet(st, self.temb.data_ptr() + i * step_bytes, self.model_out.data_ptr())
             if uncond is not None:
-                plan.run(self.x.data_ptr(), uncond[0].data_ptr() + i * step_bytes, uncond[1].data_ptr(), st)
+                self._unet(st, uncond[0].data_ptr() + i * step_bytes, uncond[1].data_ptr())
             if isinstance(a, ThresholdStep):
                 a.enqueue(st)
             else:
@@ -381,6 +394,68 @@ class _SlicedDDIBGraph(DDIBGraph):
         for r in self._runners.values():
             r.join()
         return self
+
+
+class TiledDDIBGraph(_PixelTrajectory):
+    """One hipGraph for the tiled invert -> class-swap -> denoise trajectory of a batch of canvases (``img2img.tiled_ddib``, bit for bit):
+    the working buffer is the (B, C, height, width) canvas; every step gathers its overlapping ``tile`` x ``tile`` tiles
+    (:class:`~phendiff_amd.tiling.TileGrid`), runs the UNet's launch plan over them in chunks of ``tile_batch``, blends the outputs into
+    the canvas-sized model output and steps the scheduler on the canvas -- thresholded over the whole image where the scheduler
+    thresholds.  The class table holds one row block per (step, tile): a tile carries its image's class.
+
+    ``run(images, orig_labels, target_labels)`` leaves ``.images`` (NHWC float in [0, 1]), ``.images_u8``, ``.inverted`` and ``.sample``
+    (the canvas at the end of the transfer, in the model's range)."""
+
+    sample = property(lambda self: self.x, doc="the canvas at the end of the transfer, NCHW in the model's range")
+
+    def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, height: int, width: int, tile,
+                 overlap=None, tile_batch: int = None, variant: str = "0.18.2", device=None, use_graph: bool = True,
+                 private_plan: bool = False):
+        from .tiling import TileGrid
+        channels = getattr(getattr(getattr(pipe, "unet", None), "config", None), "in_channels", 0)
+        E._check_tiled_request(pipe, (batch_size, channels, height, width), "TiledDDIBGraph")
+        self.grid = TileGrid(height, width, tile, E.default_overlap(tile) if overlap is None else overlap)
+        if pipe.unet.device.type != "cuda":
+            raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the pipeline to 'cuda'")
+        self._tile_batch = tile_batch
+        super().__init__(pipe, batch_size, num_inference_steps, height, width, device, use_graph, private_plan, inverts=True)
+        self.tiled.bind(self.x, self.model_out)
+        self.inv, fwd, self.inv_ts, self.gen_ts = _schedules(
+            pipe, self.S, variant, lambda fwd: fwd.timesteps[fwd.timesteps <= fwd.config.num_train_timesteps * (1 - 0)])
+        self._class_table(self.inv_ts + self.gen_ts)
+        self.inv_args = [self.inv.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.inv_ts]
+        self.gen_args = [self._forward_step_args(fwd, t) for t in self.gen_ts]
+        self._inverted_snapshot()
+        self._capture()
+
+    def _make_plans(self, private_plan, input_grad):
+        """The launch plans of the TILES (``plan``: the one of a full chunk, whose weights the class table goes through)."""
+        self.tiled = E._TiledForward(self.pipe.unet, self.grid, self.B, self._tile_batch, self.device, private_plan)
+        self.plan, self.gplan = self.tiled.plan, None
+
+    rows_per_step = property(lambda self: self.tiled.T, doc="conditioning rows of one step: one per tile")
+
+    def _unet(self, st, temb_ptr, out_ptr):
+        assert out_ptr == self.model_out.data_ptr(), "the blend writes the model output the runner was bound to"
+        self.tiled.evaluate(temb_ptr, st)
+
+    def _enqueue(self, st):
+        self.class_rows.temb(self.ts_rows, st, self.temb)
+        self._ddim_steps(st, self.inv_args)
+        self._snapshot(st)
+        self._ddim_steps(st, self.gen_args, first=len(self.inv_args))
+        self._postproc(st)
+
+    def _fill(self, clean_images, orig_class_labels, target_class_labels):
+        T, n_inv, n_gen, per = self.tiled.T, len(self.inv_ts), len(self.gen_ts), self.grid.tiles_per_image
+        self.x.copy_(clean_images, non_blocking=True)
+        self.class_rows.fill(slice(0, n_inv * T), n_inv, T, E.tile_conditioning(orig_class_labels.to(self.device), per))
+        self.class_rows.fill(slice(n_inv * T, (n_inv + n_gen) * T), n_gen, T, E.tile_conditioning(target_class_labels.to(self.device), per))
+
+    def run(self, clean_images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor, join: bool = True):
+        """``join=False`` leaves the caller's stream un-joined (``self.join()`` before reading the outputs)."""
+        _check_shape(clean_images, self.x)
+        return self._replay(join, clean_images, orig_class_labels, target_class_labels)
 
 
 class CFGForwardStartGraph(_PixelTrajectory):
