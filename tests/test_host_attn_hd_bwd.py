@@ -5,7 +5,7 @@ import ctypes as C
 import pytest
 import torch
 
-from test_host_sd15 import header_fields
+from abi_header import header_fields
 
 BWD_FIELDS = ["dtype", "B", "heads", "D", "Nq", "Nkv", "scale", "q", "q_stride", "k", "v", "kv_stride", "o", "dout", "o_stride",
               "lse", "delta", "dq", "dq_stride", "dk", "dv", "dkv_stride"]

@@ -15,9 +15,8 @@ import pytest
 import torch
 
 import gaussianity_ref as R
+from abi_header import ROOT, define, header_fields, source
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
 SIZES = (8, 20, 105, 3072, 4099, 196608)
 
 
@@ -65,20 +64,6 @@ def test_product_has_no_scipy_import():
 
 
 # ---------------------------------------------------------------------------------------------------------------- C ABI
-def header_fields(cname):
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*" + cname + ";", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    return fields
-
-
 def test_struct_and_constants_match_header():
     import phendiff_amd._lib as L
     want = ["dtype", "bins", "B", "n", "y_sample_stride", "x", "y", "edges", "stats", "hist", "workspace", "workspace_bytes"]
@@ -86,8 +71,7 @@ def test_struct_and_constants_match_header():
     T = L.SampleStatsArgs
     assert [getattr(T, f).offset for f in want] == [0, 4, 8, 16, 24, 32, 40, 48, 56, 64, 72, 80]
     assert C.sizeof(T) == 88
-    src = open(HEADER).read()
-    define = lambda name: int(re.search(r"#define\s+" + name + r"\s+(\d+)", src).group(1))      # noqa: E731
+    src = source()
     assert define("PD_SAMPLE_STATS_FIELDS") == len(L.SAMPLE_STATS_FIELDS) == 10
     assert define("PD_SAMPLE_STATS_CHUNK") == L.SAMPLE_STATS_CHUNK
     assert define("PD_SAMPLE_STATS_MAX_BINS") == L.SAMPLE_STATS_MAX_BINS

@@ -5,7 +5,7 @@ import ctypes as C
 
 import pytest
 
-from test_host_sd15 import header_fields
+from abi_header import header_fields
 
 FIELDS = ["numel", "per_sample", "pred_type", "clip", "clip_range", "use_clipped_model_output", "sqrt_a", "sqrt_b", "sqrt_ap", "dir_coef",
           "guidance_scale", "grad_scale", "sample", "g_direct", "g_unet", "model_out", "prev_sample", "pushed", "overflow"]

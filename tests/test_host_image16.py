@@ -3,17 +3,13 @@ PIL's mode I;16 resize), the three new entry points' structs, symbols and refusa
 and the rank rule of band_percentiles."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_header import define, header_fields
 from image16_ref import KINDS, contents, emulate_resize16, pil_bands16
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
 
 # (H, W) -> (OH, OW): down, up, one axis unchanged (either one), both changed by a hair, nothing changed, the 32 x limit (65 taps)
 SHAPES = [((37, 53), (16, 16)), ((16, 16), (37, 53)), ((64, 48), (64, 16)), ((33, 70), (8, 70)), ((130, 97), (32, 24)), ((9, 9), (9, 9)),
@@ -52,20 +48,6 @@ def test_emulated_arithmetic_equals_pil_i16_resize(src, dst, kind):
     assert int((got != want).sum()) == 0
 
 
-def header_fields(cname):
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*" + cname + ";", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    return fields
-
-
 def test_new_symbols_are_exported_prototyped_and_laid_out_as_the_header_says():
     import phendiff_amd._lib as L
     lib = L.lib()
@@ -82,8 +64,7 @@ def test_new_symbols_are_exported_prototyped_and_laid_out_as_the_header_says():
     want[want.index("y_u8")] = "y_u16"
     assert [f[0] for f in L.ImagePreprocessBands16Args._fields_] == want
     # added entry points, no struct changed: the ABI version stays
-    src = open(HEADER).read()
-    assert int(re.search(r"#define PD_ABI_VERSION (\d+)", src).group(1)) == L.ABI_VERSION == lib.pd_abi_version() == 8
+    assert define("PD_ABI_VERSION") == L.ABI_VERSION == lib.pd_abi_version() == 8
 
 
 def _args(**kw):

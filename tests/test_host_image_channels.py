@@ -1,31 +1,20 @@
 """Image stacks of 4 to 32 channels -- what needs no GPU: pd_image_preprocess_bands' struct, symbol and refusals, the argument checks of
 ImagePreprocessor(channels=C), the channel range of the pixel UNet and the PIL refusal of the pipeline."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
+from abi_header import define, header_fields
 
 
 def test_bands_struct_matches_header_and_is_bound():
     import phendiff_amd._lib as L
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*pd_image_preprocess_bands_args;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        for part in decl.strip().split(","):
-            if part.strip():
-                fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    assert fields == [f[0] for f in L.ImagePreprocessBandsArgs._fields_]
+    assert header_fields("pd_image_preprocess_bands_args") == [f[0] for f in L.ImagePreprocessBandsArgs._fields_]
     assert "pd_image_preprocess_bands" in L.SYMBOLS and hasattr(L.lib(), "pd_image_preprocess_bands")
     # an added entry point, no struct changed: the ABI version stays
-    assert int(re.search(r"#define PD_ABI_VERSION (\d+)", src).group(1)) == L.ABI_VERSION == L.lib().pd_abi_version() == 8
+    assert define("PD_ABI_VERSION") == L.ABI_VERSION == L.lib().pd_abi_version() == 8
     # the RGB entry's struct is what it was
     assert [f[0] for f in L.ImagePreprocessArgs._fields_][19:25] == ["mean0", "mean1", "mean2", "std0", "std1", "std2"]
 

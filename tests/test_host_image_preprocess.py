@@ -1,15 +1,12 @@
 """Image preprocessing (phendiff_amd/data.py, pd_image_preprocess) -- what needs no GPU: the resampling tables against PIL itself, the output
 size rule, the order in which flip codes consume the RNG, and the C entry point's argument validation."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
+from abi_header import define, header_fields
 
 # (H, W) -> (OH, OW): up-scaling, down-scaling, 1-pixel sources, one axis unchanged, nothing to do, and the training shape
 SHAPES = [((37, 53), (16, 16)), ((16, 16), (37, 53)), ((64, 64), (32, 32)), ((97, 61), (128, 128)), ((200, 300), (128, 128)),
@@ -93,22 +90,14 @@ def test_draw_flips_consumes_the_rng_like_the_composed_transform():
 def test_struct_matches_header_and_is_bound():
     import phendiff_amd as P
     import phendiff_amd._lib as L
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*pd_image_preprocess_args;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        for part in decl.strip().split(","):
-            if part.strip():
-                fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    assert fields == [f[0] for f in L.ImagePreprocessArgs._fields_]
+    assert header_fields("pd_image_preprocess_args") == [f[0] for f in L.ImagePreprocessArgs._fields_]
     assert "pd_image_preprocess" in L.SYMBOLS and hasattr(L.lib(), "pd_image_preprocess")
-    assert int(re.search(r"#define PD_ABI_VERSION (\d+)", src).group(1)) == L.ABI_VERSION == L.lib().pd_abi_version()
+    assert define("PD_ABI_VERSION") == L.ABI_VERSION == L.lib().pd_abi_version()
     assert P.data.ImagePreprocessor is P.ImagePreprocessor
 
 
 def test_the_three_structs_keep_their_abi_8_layout():
-    """The three image structs are built from one shared list of leading fields: their sizes and offsets are pinned to what the C
+    """The three image structs share their 19 leading fields: their sizes and offsets are pinned to what the C
     structs of ABI 8 have (ints, two long longs, pointers and floats under the x86-64 rules)."""
     import phendiff_amd._lib as L
     rgb, bands, bands16 = L.ImagePreprocessArgs, L.ImagePreprocessBandsArgs, L.ImagePreprocessBands16Args

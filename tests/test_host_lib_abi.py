@@ -1,19 +1,14 @@
 """The C-ABI shared library loads on a CPU-only box and exports every symbol include/phendiff_hip.h declares
-(no compute calls here: there is no GPU).  Also pins the ctypes struct layouts against the header's field lists."""
+(no compute calls here: there is no GPU).  Also holds the binding that phendiff_amd/_lib.py derives from the header against what a C
+compiler makes of the same header: every struct, every field, offsets, sizes and type classes."""
 import ctypes as C
 import os
-import re
+import shutil
+import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
-
-
-def declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pd_[a-z0-9_]+)\s*\(", src)))
+from abi_header import HEADER, declared_functions, define, header_fields, source, struct_names
 
 
 def test_library_exports_every_declared_symbol():
@@ -28,33 +23,132 @@ def test_library_exports_every_declared_symbol():
     assert sorted(L.SYMBOLS) == names
     # one version number in three places: the header's macro, the binding's constant, the library's answer (bumped whenever an
     # args struct grows or an entry point is added: r2 added trailing pointer fields, r3 = 3)
-    import re
-    macro = int(re.search(r"#define PD_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
-    assert lib.pd_abi_version() == L.ABI_VERSION == macro
+    assert lib.pd_abi_version() == L.ABI_VERSION == define("PD_ABI_VERSION")
     assert lib.pd_last_error() is not None
 
 
-def test_struct_field_order_matches_header():
+def class_of(cname):
+    """The binding's class of a C struct, by the naming rule: pd_foo_bar_args -> FooBarArgs."""
     import phendiff_amd._lib as L
-    src = open(HEADER).read()
-    pairs = {"pd_temb_args": L.TembArgs, "pd_conv_in_args": L.ConvInArgs, "pd_gn_stats_args": L.GnStatsArgs,
-             "pd_conv_args": L.ConvArgs, "pd_gn_finalize_args": L.GnFinalizeArgs, "pd_attn_args": L.AttnArgs,
-             "pd_ddim_step_args": L.DdimStepArgs, "pd_add_noise_args": L.AddNoiseArgs, "pd_postproc_args": L.PostprocArgs,
-             "pd_attn_d64_args": L.AttnD64Args, "pd_attn_wide_args": L.AttnWideArgs, "pd_attn_wide_bwd_args": L.AttnWideBwdArgs, "pd_latent_sample_args": L.LatentSampleArgs,
-             "pd_attn_d64_bwd_args": L.AttnD64BwdArgs, "pd_layernorm_bwd_args": L.LayerNormBwdArgs,
-             "pd_geglu_bwd_args": L.GegluBwdArgs, "pd_linear_args": L.LinearArgs, "pd_gn_apply_args": L.GnApplyArgs, "pd_token_wgrad_args": L.TokenWgradArgs, "pd_layernorm_args": L.LayerNormArgs, "pd_geglu_args": L.GegluArgs,
-             "pd_pack_weight_args": L.PackWeightArgs, "pd_pack_weight_batch_args": L.PackWeightBatchArgs, "pd_zero_args": L.ZeroArgs}
-    for cname, cls in pairs.items():
-        body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*" + cname + ";", src, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            for part in decl.split(","):
-                fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-        assert fields == [f[0] for f in cls._fields_], cname
+    return getattr(L, "".join(w.capitalize() for w in cname[3:].split("_")))
+
+
+def host_c_compiler():
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    for cc in (shutil.which("cc"), os.path.join(rocm, "llvm", "bin", "clang"), os.path.join(rocm, "lib", "llvm", "bin", "clang")):
+        if cc and os.path.exists(cc):
+            return cc
+    pytest.fail("no host C compiler (cc, or ROCm's clang): the library's build needs one too")
+
+
+PROBE = """#include <stdio.h>
+#include "phendiff_hip.h"
+#define KIND(x) _Generic((x), int: "int", float: "float", double: "double", long: "long", long long: "longlong", \\
+                         unsigned long: "ulong", default: "other")
+#define FIELD(T, f) printf("F %s %zu %zu %s\\n", #f, offsetof(T, f), sizeof(((T*)0)->f), KIND(((T*)0)->f))
+int main(void) {
+@BODY@  return 0;
+}
+"""
+
+
+def compiled_layout(tmp_path):
+    """{struct: (sizeof, [(field, offset, size, kind)])} as the host C compiler lays the header's structs out."""
+    lines = "".join(f'  printf("S {s} %zu\\n", sizeof({s}));\n' + "".join(f"  FIELD({s}, {f});\n" for f in header_fields(s))
+                    for s in struct_names())
+    (tmp_path / "layout.c").write_text(PROBE.replace("@BODY@", lines))
+    exe = str(tmp_path / "layout")
+    subprocess.run([host_c_compiler(), "-std=c11", "-I", os.path.dirname(HEADER), "-o", exe, str(tmp_path / "layout.c")], check=True)
+    layout = {}
+    for tag, name, *rest in (line.split() for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()):
+        if tag == "S":
+            fields = []
+            layout[name] = (int(rest[0]), fields)
+        else:
+            fields.append((name, int(rest[0]), int(rest[1]), rest[2]))
+    return layout
+
+
+def same_type(ctype, kind, size):
+    """Is a ctypes field type what C calls `kind` (a _Generic class) of `size` bytes?"""
+    if kind in ("float", "double"):
+        return ctype is {"float": C.c_float, "double": C.c_double}[kind]
+    if kind == "other":     # a pointer or char[N]
+        return ctype is C.c_void_p and size == C.sizeof(C.c_void_p) or issubclass(ctype, C.Array) and ctype._type_ is C.c_char and ctype._length_ == size
+    codes = "BHILQ" if kind == "ulong" else "bhilq"      # integers: signedness and width
+    return issubclass(ctype, C._SimpleCData) and ctype._type_ in codes and C.sizeof(ctype) == size
+
+
+def test_struct_field_order_matches_header(tmp_path):
+    """Every struct of the header, as the compiler lays it out, against the derived ctypes class: field names and order, every offset
+    and size, float / double exactly where C has them, integers by signedness and width, c_void_p for pointers, sizeof."""
+    import phendiff_amd._lib as L
+    layout = compiled_layout(tmp_path)
+    assert list(layout) == struct_names() and len(layout) >= 62
+    nfields = 0
+    for cname, (size, fields) in layout.items():
+        cls = class_of(cname)
+        assert L.STRUCTS[cname] is cls and issubclass(cls, C.Structure)
+        assert [f[0] for f in fields] == [f[0] for f in cls._fields_] == header_fields(cname), cname
+        for (name, offset, fsize, kind), (_, ctype) in zip(fields, cls._fields_):
+            where = f"{cname}.{name}"
+            assert (getattr(cls, name).offset, getattr(cls, name).size) == (offset, fsize), where
+            assert same_type(ctype, kind, fsize), (where, kind, ctype)
+            nfields += 1
+        assert C.sizeof(cls) == size, cname
+    assert nfields >= 840
+    # the three classes whose long-standing names the rule does not give
+    assert (L.AdamWEmaArgs, L.LayerNormArgs, L.LayerNormBwdArgs) == (class_of("pd_adamw_ema_args"), class_of("pd_layernorm_args"),
+                                                                    class_of("pd_layernorm_bwd_args"))
+    assert not same_type(C.c_int, "float", 4) and not same_type(C.c_int, "long", 8) and not same_type(C.c_int64, "ulong", 8)
+
+
+def test_prototypes_match_header():
+    import re
+    import phendiff_amd._lib as L
+    src = re.sub(r"/\*.*?\*/", "", source(), flags=re.S)
+    nstruct = 0
+    for fn, params in re.findall(r"\b(pd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        restype, argtypes = L.SYMBOLS[fn]
+        params = [] if params.strip() == "void" else params.split(",")
+        assert len(argtypes) == len(params), fn
+        for p, t in zip(params, argtypes):
+            m = re.fullmatch(r"\s*(?:const\s+)?(pd_\w+)\s*\*\s*\w+\s*", p)
+            if m:
+                assert t is C.POINTER(class_of(m.group(1))), (fn, p)
+                nstruct += 1
+    assert nstruct >= 69      # struct-pointer parameters of the 89 prototypes of ABI 8
+    # scalars the host receives through byref(); device pointers passed as integers stay c_void_p
+    assert L.SYMBOLS["pd_event_elapsed_ms"] == (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)])
+    assert L.SYMBOLS["pd_comm_query"] == (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)])
+    assert L.SYMBOLS["pd_grad_norm"][1] == [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert L.SYMBOLS["pd_allreduce_bucket"][1] == [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+    assert L.SYMBOLS["pd_lp_guidance_scaled"][1][1:] == L.SYMBOLS["pd_ddim_raw_x0"][1][1:] == [C.c_void_p, C.c_void_p]
+    assert L.SYMBOLS["pd_last_error"] == (C.c_char_p, []) and L.SYMBOLS["pd_graph_end"][1] == [C.c_void_p, C.POINTER(C.c_void_p)]
+    assert L.SYMBOLS["pd_conv_wgrad_workspace"] == (C.c_size_t, [C.POINTER(L.WgradArgs)])
+
+
+def test_the_reader_refuses_what_it_does_not_know(tmp_path):
+    """Nothing is guessed: an unmapped type names its struct and field, a stale out-parameter is an error, a missing header names its path."""
+    import phendiff_amd._lib as L
+    from phendiff_amd import _abi
+    ok = "typedef struct { int n; const float *a, *b; char tag[16]; } pd_toy_args;\nint pd_toy(const pd_toy_args* a, void* stream);\n"
+    structs, symbols, _ = _abi.read(ok, {})
+    assert structs["pd_toy_args"]._fields_ == [("n", C.c_int), ("a", C.c_void_p), ("b", C.c_void_p), ("tag", C.c_char * 16)]
+    assert symbols == {"pd_toy": (C.c_int, [C.POINTER(structs["pd_toy_args"]), C.c_void_p])}
+    with pytest.raises(TypeError, match=r"pd_toy_args\.flag.*'short'"):
+        _abi.read(ok.replace("int n;", "int n; short flag;"), {})
+    with pytest.raises(TypeError, match="pd_toy.*'unsigned'"):
+        _abi.read(ok.replace("void* stream", "unsigned flags"), {})
+    with pytest.raises(TypeError, match="pd_toy.*'float'"):
+        _abi.read(ok.replace("int pd_toy", "float pd_toy"), {})
+    with pytest.raises(TypeError, match="pd_gone"):
+        _abi.read(ok, {("pd_gone", "out"): C.POINTER(C.c_int)})
+    with pytest.raises(TypeError, match="explicit integer value"):
+        _abi.read(ok + "enum { PD_A = 0, PD_B };\n", {})
+    missing = str(tmp_path / "phendiff_hip.h")
+    with pytest.raises(L.PhenDiffHipError, match=missing):
+        L.read_header(missing)
 
 
 def test_argument_validation_without_gpu():

@@ -4,29 +4,12 @@ no CPU fallback; the new switch defaults to off)."""
 import ctypes as C
 import inspect
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
-
-
-def header_fields(cname):
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*" + cname + ";", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    return fields
+from abi_header import define, header_fields
 
 
 def test_structs_and_constants_match_header():
@@ -40,8 +23,6 @@ def test_structs_and_constants_match_header():
     assert header_fields("pd_feature_moments_args") == want == [f[0] for f in L.FeatureMomentsArgs._fields_]
     assert [getattr(L.FeatureMomentsArgs, f).offset for f in want] == list(range(0, 72, 8))
     assert C.sizeof(L.FeatureMomentsArgs) == 72
-    src = open(HEADER).read()
-    define = lambda name: int(re.search(r"#define\s+" + name + r"\s+(\d+)", src).group(1))      # noqa: E731
     assert define("PD_METRIC_STATS_TILE") == L.METRIC_STATS_TILE
     assert define("PD_FEATURE_MOMENTS_CHUNK") == L.FEATURE_MOMENTS_CHUNK
 

@@ -1,14 +1,11 @@
 """Stable Diffusion 1.x denoisers without a GPU: the module tree (parameter count, diffusers' key names and shapes with the 1x1-conv
 ``proj_in`` / ``proj_out``), config round trips, the refusals, and the C ABI of ``pd_attn_hd`` (struct layout, export, validation)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
+from abi_header import header_fields
 
 SD15_PARAMS = 859_520_964       # the public SD 1.x UNet count; re-derived from the oracle below
 
@@ -106,20 +103,6 @@ def test_training_is_refused_before_anything_runs():
 
 
 # ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-def header_fields(cname):
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*" + cname + ";", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    return fields
-
-
 def test_attn_hd_struct_and_export():
     import phendiff_amd._lib as L
     want = ["dtype", "B", "heads", "D", "Nq", "Nkv", "scale", "q", "q_stride", "k", "v", "kv_stride", "out", "out_stride", "lse"]

@@ -9,7 +9,7 @@ import torch
 
 import flat_refs as R
 import threshold_refs as T
-from test_host_sd15 import header_fields
+from abi_header import header_fields
 
 
 def test_quantile_rank_sort_lerp_equals_torch_quantile():

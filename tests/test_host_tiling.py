@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import tiled_refs as T
-from test_host_sd15 import header_fields
+from abi_header import header_fields
 
 AXES = tuple(k for k, _ in T.KNOWN_ORIGINS) + ((1024, 256, 32), (1080, 256, 32), (2048, 256, 64), (100, 7, 6), (50, 32, 31))
 

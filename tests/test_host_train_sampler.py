@@ -2,17 +2,14 @@
 known-answer vectors and plain statistics, the C ABI of ``pd_train_sample`` (struct layout, export, every refusal before a launch),
 the sampler's ``state_dict`` and the untouched default path of ``sample_training_inputs``."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import philox_ref as R
+from abi_header import header_fields
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
 SEED = 1          # the statistics below hold for this seed (restatement alone, on the CPU)
 
 # Random123's kat_vectors for philox4x32-10: (counter, key, output)
@@ -71,16 +68,7 @@ def test_restatement_slices_agree():
 # ---------------------------------------------------------------------------------------------------------------- C ABI
 def test_struct_field_order_matches_header():
     import phendiff_amd._lib as L
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*pd_train_sample_args;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
+    fields = header_fields("pd_train_sample_args")
     assert fields == [f[0] for f in L.TrainSampleArgs._fields_]
     assert fields == ["seed", "step", "rank", "purpose", "B", "per_sample", "elem_base", "N", "clean", "sqrt_acp", "sqrt_1m_acp",
                       "timesteps_in", "timesteps_out", "noise", "noisy"]

@@ -1,14 +1,10 @@
 """`components_to_train autoencoder` (train.py:189-199, 268-285) on the engine -- what needs no GPU: the C ABI of
 pd_latent_chain_bwd, the layout of the trainer's flat buffers with a training / frozen autoencoder, accelerate's checkpoint
 numbering, and the argument guards of `step_images`."""
-import os
-import re
-
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "phendiff_hip.h")
+from abi_header import define, header_fields
 
 TINY_VAE = dict(block_out_channels=(32, 64), layers_per_block=1)      # the tiny configuration of tests/test_gpu_vae.py
 
@@ -23,19 +19,9 @@ def models():
 
 def test_latent_chain_bwd_struct_matches_header_and_is_bound():
     import phendiff_amd._lib as L
-    src = open(HEADER).read()
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*pd_latent_chain_bwd_args;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    assert fields == [f[0] for f in L.LatentChainBwdArgs._fields_]
+    assert header_fields("pd_latent_chain_bwd_args") == [f[0] for f in L.LatentChainBwdArgs._fields_]
     assert "pd_latent_chain_bwd" in L.SYMBOLS and hasattr(L.lib(), "pd_latent_chain_bwd")
-    assert int(re.search(r"#define PD_ABI_VERSION (\d+)", src).group(1)) == L.ABI_VERSION == 8
+    assert define("PD_ABI_VERSION") == L.ABI_VERSION == 8
 
 
 def test_latent_chain_bwd_validates_before_launching():
