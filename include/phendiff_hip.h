@@ -40,7 +40,7 @@ extern "C" {
  * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace), pd_lp_guidance_scaled, pd_guided_step
  * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args), pd_image_preprocess_bands16, pd_band_histogram16,
  * pd_postproc_bands16 (+ their args structs), pd_abs_quantile (+ pd_abs_quantile_workspace), pd_ddim_raw_x0, pd_ddim_step_threshold (+ their
- * args structs), pd_tile_gather, pd_tile_blend (+ their args structs). */
+ * args structs), pd_tile_gather, pd_tile_blend (+ their args structs), pd_ssim (+ pd_ssim_args, pd_ssim_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -1108,6 +1108,56 @@ typedef struct {
 } pd_sample_stats_args;
 size_t pd_sample_stats_workspace(int64_t B, int64_t n, int bins);
 int pd_sample_stats(const pd_sample_stats_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_ssim (added under ABI 8): structural similarity (Wang et al. 2004) and the ingredients of multi-scale SSIM (Wang et al. 2003) between
+ * two batches that stay on the device, reduced to B x C x levels x 2 fp64 numbers: per (sample, channel, scale) the mean of the SSIM map and
+ * the mean of its contrast-structure factor.  csrc/ssim.hip; host side phendiff_amd.diagnostics (ssim_maps_means, sample_ssim: the channel
+ * means, the clamp, the powers and the product of MS-SSIM are taken there in float64).
+ *   x: contiguous [B][C][H][W] of `dtype` (PD_F32 / PD_BF16 / PD_F16); sample b starts at element b * C * H * W, whatever its alignment.
+ *      Every element is widened to fp64 (exactly) before any arithmetic, and everything after it is fp64.
+ *   y: same dtype; y_sample_stride = C * H * W for one y per sample, 0 for one y [C][H][W] shared by all samples.
+ *   w0 .. w(win - 1): the window's taps, BY VALUE (nothing to keep alive for a captured graph); win odd, 3 .. PD_SSIM_MAX_WIN.  The host
+ *      passes g[i] = exp(-(i - (win - 1) / 2)^2 / (2 sigma^2)) / sum (diagnostics.gaussian_window); taps past win are ignored.  The 2-D
+ *      window is the outer product of the taps, applied as a row filter and then a column filter.  Filtering is VALID: no padding, the maps
+ *      have (H - win + 1) x (W - win + 1) positions (Wang et al.'s original; pytorch_msssim).
+ *   Per position, with mx, my, exx, eyy, exy the five filtered maps of x, y, x^2, y^2, xy:
+ *        vx = exx - mx^2, vy = eyy - my^2, vxy = exy - mx my
+ *        cs = (2 vxy + c2) / (vx + vy + c2),   ssim = cs (2 mx my + c1) / (mx^2 + my^2 + c1)
+ *      c1 = (0.01 R)^2, c2 = (0.03 R)^2 for a data range R are the caller's to compute; both finite and positive.
+ *   levels 1 .. PD_SSIM_MAX_LEVELS: scale s >= 1 is scale s - 1 of both images reduced by a 2x2 mean of stride 2, an odd trailing row or
+ *      column dropped, computed as ((a00 + a01) + (a10 + a11)) * 0.25 in fp64 and KEPT in fp64.  min(H, W) >> (levels - 1) >= win.
+ *   out [B][C][levels][2] fp64, every element written by every call: [..][s][0] the mean of ssim, [..][s][1] the mean of cs over the valid
+ *      positions of scale s.  A NaN / infinity in a plane of x or y makes that plane's numbers NaN (the IEEE result) and no other's.
+ *   workspace: pd_ssim_workspace(B, C, H, W, levels) bytes (16 bytes per tile of 16 x 32 positions, counted for the smallest window, plus
+ *      the fp64 pyramid of both images, y's counted per sample; 0 for sizes the call refuses), 8-byte aligned, contents irrelevant before and
+ *      after; workspace_bytes states what the caller allocated.
+ * Launches: per scale s >= 1 one reduce launch for x and one for y, per scale one tiled pass (a workgroup of 256 threads owns 16 x 32 valid
+ * positions of one plane: it stages those plus the win - 1 halo of x and y in LDS as fp64, filters rows into five LDS maps, then columns,
+ * and reduces ssim / cs to one pair; LDS 8 (2 (15 + win)(31 + win) + 160 (15 + win)) bytes: 50,752 at win 11, 110,592 at win 33), one fold
+ * launch at the end; 2 * levels .. 3 * levels - 1 launches, no host synchronisation, capturable.
+ * Every sum runs in a fixed order (lane, wave, workgroup, tile index), no floating-point atomics; only element loads are used and the
+ * position -> lane map depends on the position within the plane only: a sample's numbers are bitwise reproducible and do not depend on B, on
+ * its row in the batch or on the pointers' alignment.  Nothing outside x's B * C * H * W and y's elements is read: a position outside a
+ * plane is never loaded, and what would need it is left out by selection, never multiplied by zero.
+ * Refused before any launch: null args / x / y / out / workspace, a dtype outside the three, non-finite or non-positive c1 / c2, a
+ * non-finite tap, a workspace_bytes below the query's (PD_ERR_ARG); B, C, H, W <= 0, an even win or one outside 3 .. 33, levels outside
+ * 1 .. 5, min(H, W) >> (levels - 1) < win, y_sample_stride outside {0, C * H * W}, more than 2^40 elements or 2^31 - 1 workgroups
+ * (PD_ERR_SHAPE). */
+#define PD_SSIM_MAX_WIN 33
+#define PD_SSIM_MAX_LEVELS 5
+typedef struct {
+  int dtype, C, H, W, win, levels;
+  int64_t B, y_sample_stride;
+  double w0, w1, w2, w3, w4, w5, w6, w7, w8, w9, w10, w11, w12, w13, w14, w15, w16, w17, w18, w19, w20, w21, w22,
+         w23, w24, w25, w26, w27, w28, w29, w30, w31, w32;
+  double c1, c2;
+  const void* x; const void* y;
+  double* out;
+  void* workspace; size_t workspace_bytes;
+} pd_ssim_args;
+size_t pd_ssim_workspace(int64_t B, int C, int H, int W, int levels);
+int pd_ssim(const pd_ssim_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_kid_mmd, pd_feature_moments (added under ABI 8): the statistics of KID and FID over features that stay on the device -- torch-fidelity's

@@ -20,6 +20,7 @@ from .configs import UNET_CONFIGS, SCHEDULER_CONFIGS, SD15_UNET_CONFIG  # noqa: 
 from . import configs  # noqa: F401
 from . import diagnostics  # noqa: F401
 from .diagnostics import check_gaussianity, sample_distances, normaltest_from_moments, GaussianityReport  # noqa: F401
+from .diagnostics import sample_ssim, ssim_maps_means, gaussian_window  # noqa: F401
 from .comm import NativeComm  # noqa: F401
 from . import training  # noqa: F401
 from .training import DeviceTrainingSampler  # noqa: F401

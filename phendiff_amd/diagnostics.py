@@ -7,7 +7,10 @@ the output (fp16 is BASELINE configs[4]'s dtype: `--mixed_precision fp16`, img2i
 Over an inverted or regenerated batch that stays on the device (``pd_sample_stats``, csrc/sample_stats.hip): ``check_gaussianity`` -- the
 reference's ``check_Gaussianity`` (utils_Img2Img.py:79-93: per-sample mean, std, the 100-bin histogram on (-3, 3) and the p-value of
 D'Agostino-Pearson's K^2 test) -- and ``sample_distances`` (``Lp_loss``, :245-270, for p = 1, 2, inf, plus MSE and PSNR).  Only
-B x (10 + bins) numbers cross to the host; ``normaltest_from_moments`` turns the moments into the test there."""
+B x (10 + bins) numbers cross to the host; ``normaltest_from_moments`` turns the moments into the test there.
+
+Between a source batch and its transfer (``pd_ssim``, csrc/ssim.hip): ``sample_ssim`` -- SSIM and multi-scale SSIM per sample in fp64, what
+image-to-image work reports for "everything but the phenotype stayed"; ``ssim_maps_means`` is the device-side call under it."""
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -217,3 +220,115 @@ def sample_distances(x, y, data_range: float = 2.0, stream=None) -> dict:
     with np.errstate(divide="ignore"):
         psnr = 10.0 * np.log10(float(data_range) ** 2 / mse)
     return {"l1": st[:, i1].copy(), "l2": np.sqrt(st[:, i2]), "linf": st[:, im].copy(), "mse": mse, "psnr": psnr}
+
+
+# ------------------------------------------------------------------------------------------------ pd_ssim
+SSIM_MAX_WIN = L.CONSTANTS["PD_SSIM_MAX_WIN"]
+SSIM_MAX_LEVELS = L.CONSTANTS["PD_SSIM_MAX_LEVELS"]
+SSIM_K1, SSIM_K2 = 0.01, 0.03
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli & Bovik 2003
+
+
+def gaussian_window(win_size: int = 11, sigma: float = 1.5) -> np.ndarray:
+    """The ``win_size`` taps g[i] = exp(-(i - (win_size - 1) / 2)^2 / (2 sigma^2)) divided by their sum, numpy float64: the separable window
+    of SSIM (11, 1.5: Wang et al. 2004).  ``win_size`` odd, 3 .. 33; ``sigma`` finite and positive."""
+    win_size, sigma = int(win_size), float(sigma)
+    if win_size % 2 != 1 or not 3 <= win_size <= SSIM_MAX_WIN:
+        raise ValueError(f"win_size = {win_size}: odd, 3 .. {SSIM_MAX_WIN}")
+    if not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError(f"sigma = {sigma}: finite and positive")
+    d = np.arange(win_size, dtype=np.float64) - (win_size - 1) / 2.0
+    g = np.exp(-(d * d) / (2.0 * sigma * sigma))
+    return g / g.sum()
+
+
+def _ssim_operands(x, y, levels, win_size):
+    """The checks of ``ssim_maps_means``, what the tensors ARE before where they live (so each is reported on any box): returns y's sample
+    stride (C * H * W, or 0 for one shared y)."""
+    for t, what in ((x, "x"), (y, "y")):
+        if not torch.is_tensor(t):
+            raise L.PhenDiffHipError(f"{what} must be a tensor on an MI355X device (no CPU fallback)")
+        if t.dtype not in _DTYPES:
+            raise TypeError(f"{what}: dtype {t.dtype} (float32, bfloat16 or float16)")
+    if x.dim() != 4 or not x.is_contiguous() or not y.is_contiguous():
+        raise ValueError(f"x must be a contiguous (B, C, H, W) tensor and y a contiguous one; x.shape={tuple(x.shape)}")
+    if y.dtype != x.dtype:
+        raise ValueError(f"y ({y.dtype}) must share x's dtype ({x.dtype})")
+    B, Cc, H, W = x.shape
+    if tuple(y.shape) == tuple(x.shape):
+        stride = Cc * H * W
+    elif tuple(y.shape) == tuple(x.shape[1:]):
+        stride = 0
+    else:
+        raise ValueError(f"y.shape={tuple(y.shape)} should be equal to either x.shape or x.shape[1:] (x.shape={tuple(x.shape)})")
+    if not 1 <= levels <= SSIM_MAX_LEVELS:
+        raise ValueError(f"levels = {levels}: 1 .. {SSIM_MAX_LEVELS}")
+    if min(B, Cc, H, W) < 1:
+        raise ValueError(f"x.shape={tuple(x.shape)}: every dimension must be positive")
+    if min(H, W) >> (levels - 1) < win_size:
+        raise ValueError(f"images of {H} x {W} are too small for win_size = {win_size} at levels = {levels}: "
+                         f"min(H, W) must be at least {win_size << (levels - 1)}")
+    if not x.is_cuda or not y.is_cuda:
+        raise L.PhenDiffHipError("x and y must live on an MI355X device (no CPU fallback)")
+    if y.device != x.device:
+        raise ValueError(f"y (on {y.device}) must share x's device ({x.device})")
+    return stride
+
+
+def ssim_maps_means(x, y, data_range: float = 2.0, levels: int = 1, win_size: int = 11, sigma: float = 1.5, stream=None):
+    """One ``pd_ssim`` call on ``x`` (B, C, H, W) and ``y`` (``x.shape`` or ``x.shape[1:]``): returns float64 [B, C, levels, 2] ON THE
+    DEVICE -- per sample, channel and scale the mean of the SSIM map ([..., 0]) and of its contrast-structure factor ([..., 1]) over the
+    valid positions of a ``win_size``-tap Gaussian window (no padding); scale s is the 2x2 mean of scale s - 1.  All arithmetic is fp64.
+    ``stream``: a ``torch.cuda.Stream`` (default: the current one); nothing synchronises, so the call can be captured."""
+    levels, win_size, data_range = int(levels), int(win_size), float(data_range)
+    taps = gaussian_window(win_size, sigma)
+    if not (math.isfinite(data_range) and data_range > 0.0):
+        raise ValueError(f"data_range = {data_range}: finite and positive")
+    stride = _ssim_operands(x, y, levels, win_size)
+    dev = x.device
+    B, Cc, H, W = x.shape
+    with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        lib = L.lib()
+        ws_bytes = lib.pd_ssim_workspace(B, Cc, H, W, levels)
+        ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=dev)
+        out = torch.empty((B, Cc, levels, 2), dtype=torch.float64, device=dev)
+        a = L.SsimArgs(dtype=_DTYPES[x.dtype], C=Cc, H=H, W=W, win=win_size, levels=levels, B=B, y_sample_stride=stride,
+                       c1=(SSIM_K1 * data_range) ** 2, c2=(SSIM_K2 * data_range) ** 2, x=x.data_ptr(), y=y.data_ptr(), out=out.data_ptr(),
+                       workspace=ws.data_ptr(), workspace_bytes=ws_bytes, **{f"w{i}": float(g) for i, g in enumerate(taps)})
+        L.check(lib.pd_ssim(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "pd_ssim")
+    return out
+
+
+def ms_ssim_weights(levels: int, weights=None) -> np.ndarray:
+    """The ``levels`` exponents of MS-SSIM, float64: the first ``levels`` of ``MS_SSIM_WEIGHTS`` renormalised to sum 1, or ``weights`` as given
+    (``levels`` positive finite numbers)."""
+    if weights is None:
+        w = np.asarray(MS_SSIM_WEIGHTS[:levels], dtype=np.float64)
+        return w / w.sum() if levels < len(MS_SSIM_WEIGHTS) else w
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != levels or not np.all(np.isfinite(w)) or not np.all(w > 0.0):
+        raise ValueError(f"weights: {levels} positive numbers, one per level; got {weights!r}")
+    return w
+
+
+@torch.no_grad()
+def sample_ssim(x, y, data_range: float = 2.0, levels: int = 1, win_size: int = 11, sigma: float = 1.5, weights=None, stream=None) -> dict:
+    """Structural similarity between ``x`` (B, C, H, W) and ``y`` (``x.shape`` or ``x.shape[1:]``) on the device, in fp64 (``pd_ssim``):
+    ``"ssim"`` [B] the channel mean of ``"ssim_per_channel"`` [B, C] (the mean SSIM map at full resolution: Wang et al. 2004, Gaussian
+    window of ``win_size`` taps and ``sigma``, valid positions only, C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2; data_range 2.0:
+    images in [-1, 1]), ``"cs_per_channel"`` [B, C, levels] the mean contrast-structure factor per scale.  With ``levels`` > 1 also
+    ``"ms_ssim"`` [B] and ``"ms_ssim_per_channel"`` [B, C]: prod_{s < levels - 1} max(cs_s, 0)^w_s * max(ssim_{levels - 1}, 0)^w_{levels - 1}
+    over the 2x2-mean pyramid, ``weights`` defaulting to the first ``levels`` of (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) renormalised to
+    sum 1.  min(H, W) must be at least win_size * 2^(levels - 1).  numpy float64.  Synchronises ``stream``."""
+    levels = int(levels)
+    w = ms_ssim_weights(levels, weights) if 1 <= levels <= SSIM_MAX_LEVELS else None
+    means_dev = ssim_maps_means(x, y, data_range=data_range, levels=levels, win_size=win_size, sigma=sigma, stream=stream)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(x.device)):
+        m = means_dev.cpu().numpy()
+    out = {"ssim": m[:, :, 0, 0].mean(axis=1), "ssim_per_channel": m[:, :, 0, 0].copy(), "cs_per_channel": m[:, :, :, 1].copy()}
+    if levels > 1:
+        factors = np.concatenate([m[:, :, :levels - 1, 1], m[:, :, levels - 1:, 0]], axis=2)      # cs of every scale but the last, ssim of the last
+        # (np.maximum passes a NaN on: a sample with a NaN stays NaN)
+        out["ms_ssim_per_channel"] = np.prod(np.maximum(factors, 0.0) ** w, axis=2)
+        out["ms_ssim"] = out["ms_ssim_per_channel"].mean(axis=1)
+    return out
