@@ -40,7 +40,8 @@ extern "C" {
  * (+ pd_sample_stats_workspace), pd_kid_mmd (+ pd_kid_mmd_workspace), pd_feature_moments (+ pd_feature_moments_workspace), pd_lp_guidance_scaled, pd_guided_step
  * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args), pd_image_preprocess_bands16, pd_band_histogram16,
  * pd_postproc_bands16 (+ their args structs), pd_abs_quantile (+ pd_abs_quantile_workspace), pd_ddim_raw_x0, pd_ddim_step_threshold (+ their
- * args structs), pd_tile_gather, pd_tile_blend (+ their args structs), pd_ssim (+ pd_ssim_args, pd_ssim_workspace). */
+ * args structs), pd_tile_gather, pd_tile_blend (+ their args structs), pd_ssim (+ pd_ssim_args, pd_ssim_workspace),
+ * pd_knn_radii (+ pd_knn_radii_args, pd_knn_radii_workspace), pd_manifold_query (+ pd_manifold_query_args, pd_manifold_query_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -1214,6 +1215,64 @@ typedef struct {
 } pd_feature_moments_args;
 size_t pd_feature_moments_workspace(int64_t N, int D);
 int pd_feature_moments(const pd_feature_moments_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_knn_radii, pd_manifold_query (added under ABI 8): the k-nearest-neighbour manifold estimates under improved precision / recall
+ * (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) over features that stay on the device, fp64 on
+ * v_mfma_f64_16x16x4_f64 from fp32 features (every element widened exactly before any arithmetic).  csrc/manifold_stats.hip; host side
+ * phendiff_amd.metrics (knn_radii_device, manifold_query_device, precision_recall_device, density_coverage_device).
+ *
+ * Everything is in SQUARED distances; no square root is taken anywhere:
+ *     d2(a, b) = max(0, |a|^2 + |b|^2 - 2 a.b)
+ *   The dot product and both norms come out of the same contraction order (a norm is the Gram entry of a row with itself), so two
+ *   bitwise-equal rows give d2 == 0.0 exactly.  A NaN d2 counts as +inf: it is never selected as a neighbour and never counted, whatever
+ *   the radius.  A pair's d2 depends on its two rows alone -- not on their position, on `splits`, on the other rows.
+ *
+ * pd_knn_radii: rad2[i] = the (k + 1)-th smallest value of row i of the d2 matrix of f [N][f_stride] with itself, the diagonal SELECTED to
+ *   exactly 0 (the row's own entry takes one place, as in kthvalue(k + 1) over a cdist that includes self).  1 <= k <= PD_MANIFOLD_MAX_K,
+ *   k + 1 <= N.  A row with fewer than k + 1 finite distances (a NaN row) gets +inf.
+ * pd_manifold_query: for query row j of q [Nq][q_stride] against the references r [Nr][r_stride]:
+ *     count[j] = #{ i : d2(q_j, r_i) <= rad2[i] }   (rad2 [Nr], one radius per REFERENCE row; count NULL: not computed, rad2 not read)
+ *     dmin2[j] = min_i d2(q_j, r_i)                 (NULL: not written; +inf for a NaN query row)
+ *   A NaN in one query row touches only that row's outputs; a NaN reference row is never near anything.
+ *
+ *   Features: fp32, 16-byte aligned, strides in elements (>= D, multiples of 4); D a multiple of 64 in 64 .. 4096; N, Nq, Nr < 2^31.
+ *   splits: a workgroup owns a block of 64 rows and walks one of `splits` ranges of the 64-column tiles, so that a few thousand rows still
+ *   fill the device; 0 = the library's default, some S in 1 .. min(column tiles, PD_MANIFOLD_MAX_SPLITS) that is a function of the shapes
+ *   only, never of the device (the workspace queries answer for it: what they return for splits = 0 is what they return for that S).
+ *   The N x N matrix is never stored: each split leaves its k + 1 candidates (resp. a count and a minimum) per row in the workspace and a
+ *   second launch merges them.  No atomics; the reductions are order statistics, integer sums and minima: the outputs are bitwise
+ *   reproducible and independent of `splits` and of the order of the reference rows.  Rows at or past N of a ragged tile are not read and
+ *   their distances are selected to +inf, never multiplied by zero; nothing outside [N][D] of a strided row is read.
+ *   workspace (8-byte aligned, contents irrelevant; S = the splits in effect; 0 for sizes the call refuses):
+ *     pd_knn_radii_workspace(N, k, splits)        = 8 (N + N S (k + 1)) bytes           (the norms, the candidates)
+ *     pd_manifold_query_workspace(Nq, Nr, splits) = 8 (Nq + Nr + Nq S) + 4 Nq S bytes, rounded up to 8 (norms, minima, counts)
+ *   Refused before any launch: null args / pointers, count without rad2, count and dmin2 both NULL, misaligned pointers, a workspace_bytes
+ *   below the query's (PD_ERR_ARG); D, the strides, k outside 1 .. 16, k + 1 > N, a size below 1 or at or above 2^31, splits outside
+ *   0 .. PD_MANIFOLD_MAX_SPLITS, more than 2^31 - 1 workgroups (PD_ERR_SHAPE). */
+#define PD_MANIFOLD_MAX_K 16
+#define PD_MANIFOLD_MAX_SPLITS 64
+typedef struct {
+  int D, k, splits;
+  int64_t N, f_stride;
+  const float* f;
+  double* rad2;
+  void* workspace; size_t workspace_bytes;
+} pd_knn_radii_args;
+size_t pd_knn_radii_workspace(int64_t N, int k, int splits);
+int pd_knn_radii(const pd_knn_radii_args* a, void* stream);
+
+typedef struct {
+  int D, splits;
+  int64_t Nq, Nr, q_stride, r_stride;
+  const float* q; const float* r;
+  const double* rad2;
+  int32_t* count;
+  double* dmin2;
+  void* workspace; size_t workspace_bytes;
+} pd_manifold_query_args;
+size_t pd_manifold_query_workspace(int64_t Nq, int64_t Nr, int splits);
+int pd_manifold_query(const pd_manifold_query_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_comm_*: the data-parallel gradient exchange -- DistributedDataParallel's bucketed all-reduce under accelerator.backward(loss)

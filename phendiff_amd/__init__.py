@@ -32,6 +32,6 @@ from .vae import AutoencoderKL, VaeImageProcessor, DiagonalGaussianDistribution,
 from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline, hack_class_embedding  # noqa: F401
 from .sd_unet_train import SDUNetTrainer, SDUNetTrainPlan, sd_training_param_order, sd_training_layout  # noqa: F401
 from .vae_train import VaeEncodeTrainPlan, vae_training_param_order  # noqa: F401
-from . import metrics  # noqa: F401,E402  (FID / IS / KID: InceptionV3Features, calculate_metrics, class_metrics_hook)
+from . import metrics  # noqa: F401,E402  (FID / IS / KID, precision / recall, density / coverage: InceptionV3Features, calculate_metrics, class_metrics_hook, precision_recall_device, density_coverage_device)
 from . import data  # noqa: F401,E402  (uint8 images -> the engine's input: ImagePreprocessor, resample_tables, draw_flips)
 from .data import ImagePreprocessor, band_percentiles, resample_tables_f64, restore_bands16  # noqa: F401,E402

@@ -13,7 +13,10 @@ host, like the library's (numpy / scipy) -- or, with ``device_statistics=True``,
 ``pd_kid_mmd``, ``pd_feature_moments``) with the matrix square root and the Inception score still on the host.  Deviation, stated: the reference writes PNG files and torch-fidelity reads them back; this module
 takes the uint8 arrays themselves (``round(255 x)`` of the pipeline's float output -- the bytes the PNGs would hold), so there is no file
 round trip.  The module tree carries torch-fidelity's state_dict names: its published ``pt_inception-2015-12-05`` weights load with
-``load_state_dict``.  They are not obtainable here (no network), so tests and examples run the structure on seeded random weights."""
+``load_state_dict``.  They are not obtainable here (no network), so tests and examples run the structure on seeded random weights.
+
+Beyond what the reference logs: improved precision / recall and density / coverage over the same 2048-d features (``prc=`` / ``dc=``, off by
+default; ``csrc/manifold_stats.hip`` on the device path) -- see the section below the KID / FID device statistics."""
 from __future__ import annotations
 
 import ctypes as C
@@ -420,6 +423,174 @@ def fid_statistics_device(features: torch.Tensor) -> tuple:
     return mu, sigma
 
 
+# ---- precision / recall / density / coverage: k-nearest-neighbour manifold estimates over the 2048-d features ----------------------------
+# Improved precision and recall (Kynkaanniemi et al. 2019; torch-fidelity's `prc`) and density / coverage (Naeem et al. 2020; the `prdc`
+# package), by their published definitions, everything in SQUARED distances:
+#     d2(a, b)       = max(0, |a|^2 + |b|^2 - 2 a.b), a NaN counted as +inf (never a neighbour, never counted)
+#     rad2_k(F)[i]   = the (k + 1)-th smallest of row i of d2(F, F), the diagonal exactly 0 (the row's own entry takes one place)
+#     precision      = mean_j [ exists i: d2(y_j, x_i) <= rad2_k(X)[i] ]          recall = mean_i [ exists j: d2(x_i, y_j) <= rad2_k(Y)[j] ]
+#     density        = sum_j #{ i: d2(y_j, x_i) <= rad2_k(X)[i] } / (k Ng)        coverage = mean_i [ min_j d2(x_i, y_j) <= rad2_k(X)[i] ]
+# with X the real and Y the generated features.  Deviation, stated: torch-fidelity's default extractor for `prc` is VGG-16; here both pairs
+# run over the 2048-d Inception pool features the other metrics use (as users of `prdc` commonly do).  No parity with torch-fidelity's code
+# is claimed (it is not available to test against): the definitions above are the contract.
+KEY_PRECISION, KEY_RECALL, KEY_F_SCORE, KEY_DENSITY, KEY_COVERAGE = "precision", "recall", "f_score", "density", "coverage"
+_MANIFOLD_BLOCK_ROWS = 2048
+
+
+def _f64_rows(f, what: str) -> np.ndarray:
+    f = np.asarray(f, dtype=np.float64)
+    if f.ndim != 2 or f.shape[0] < 1:
+        raise ValueError(f"{what}: expecting features of shape (N, D), got {f.shape}")
+    return f
+
+
+def _d2_rows(a, na, b, nb):
+    """[len(a)][len(b)] squared distances in the Gram form; NaN -> +inf."""
+    d = (na[:, None] + nb[None, :]) - 2.0 * (a @ b.T)
+    with np.errstate(invalid="ignore"):
+        return np.where(d > 0, d, np.where(d <= 0, 0.0, np.inf))
+
+
+def knn_radii(features, k: int, block_rows: int = _MANIFOLD_BLOCK_ROWS) -> np.ndarray:
+    """``rad2_k(features)``: fp64 [N], the squared distance of every row to its k-th nearest other row (``kthvalue(k + 1)`` of a row of the
+    distance matrix that includes the row itself, at exactly 0).  ``block_rows`` rows at a time: no N x N array."""
+    f = _f64_rows(features, "knn_radii")
+    n = len(f)
+    if not 1 <= k <= L.CONSTANTS["PD_MANIFOLD_MAX_K"] or k + 1 > n:
+        raise ValueError(f"knn_radii: k = {k} (1 .. {L.CONSTANTS['PD_MANIFOLD_MAX_K']}, and k + 1 <= N = {n})")
+    nf = np.einsum("ij,ij->i", f, f)
+    out = np.empty(n)
+    for i in range(0, n, block_rows):
+        d = _d2_rows(f[i:i + block_rows], nf[i:i + block_rows], f, nf)
+        r = np.arange(len(d))
+        d[r, i + r] = 0.0
+        out[i:i + block_rows] = np.partition(d, k, axis=1)[:, k]
+    return out
+
+
+def manifold_query(queries, refs, rad2=None, block_rows: int = _MANIFOLD_BLOCK_ROWS):
+    """``(count | None, dmin2)`` per query row: ``count[j] = #{i: d2(q_j, r_i) <= rad2[i]}`` (int64; None without ``rad2``) and
+    ``dmin2[j] = min_i d2(q_j, r_i)``."""
+    q, r = _f64_rows(queries, "manifold_query"), _f64_rows(refs, "manifold_query")
+    if q.shape[1] != r.shape[1]:
+        raise ValueError("manifold_query: the two feature sets must share a width")
+    nq, nr = np.einsum("ij,ij->i", q, q), np.einsum("ij,ij->i", r, r)
+    rad2 = None if rad2 is None else np.asarray(rad2, dtype=np.float64)
+    count = None if rad2 is None else np.empty(len(q), dtype=np.int64)
+    dmin2 = np.empty(len(q))
+    for i in range(0, len(q), block_rows):
+        d = _d2_rows(q[i:i + block_rows], nq[i:i + block_rows], r, nr)
+        dmin2[i:i + block_rows] = d.min(axis=1)
+        if count is not None:
+            count[i:i + block_rows] = (np.isfinite(d) & (d <= rad2[None, :])).sum(axis=1)
+    return count, dmin2
+
+
+def _f_score(p: float, r: float) -> float:
+    return 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+
+
+def precision_recall(features_1, features_2, neighborhood: int = 3, block_rows: int = _MANIFOLD_BLOCK_ROWS) -> dict:
+    """Improved precision / recall of the generated ``features_1`` against the real ``features_2``, fp64 on the host."""
+    gen, real = _f64_rows(features_1, "precision_recall"), _f64_rows(features_2, "precision_recall")
+    in_real, _ = manifold_query(gen, real, knn_radii(real, neighborhood, block_rows), block_rows)
+    in_gen, _ = manifold_query(real, gen, knn_radii(gen, neighborhood, block_rows), block_rows)
+    p, r = float((in_real > 0).mean()), float((in_gen > 0).mean())
+    return {KEY_PRECISION: p, KEY_RECALL: r, KEY_F_SCORE: _f_score(p, r)}
+
+
+def density_coverage(features_1, features_2, nearest_k: int = 5, block_rows: int = _MANIFOLD_BLOCK_ROWS) -> dict:
+    """Density / coverage of the generated ``features_1`` against the real ``features_2``, fp64 on the host."""
+    gen, real = _f64_rows(features_1, "density_coverage"), _f64_rows(features_2, "density_coverage")
+    rad2 = knn_radii(real, nearest_k, block_rows)
+    count, _ = manifold_query(gen, real, rad2, block_rows)
+    _, dmin2 = manifold_query(real, gen, None, block_rows)
+    return {KEY_DENSITY: float(count.sum() / (nearest_k * len(gen))), KEY_COVERAGE: float((np.isfinite(dmin2) & (dmin2 <= rad2)).mean())}
+
+
+def knn_radii_device(features: torch.Tensor, k: int, splits: int = 0) -> torch.Tensor:
+    """:func:`knn_radii` over fp32 features that stay on the device (``pd_knn_radii``): fp64 [N] ON THE DEVICE.  ``splits``: column ranges
+    per block of 64 rows (0: the library's default; the result does not depend on it)."""
+    f = _device_features(features, "knn_radii_device")
+    dev, (N, D) = f.device, f.shape
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        rad2 = torch.empty((N,), dtype=torch.float64, device=dev)
+        ws_bytes = lib.pd_knn_radii_workspace(N, int(k), int(splits))
+        ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
+        a = L.KnnRadiiArgs(D=D, k=int(k), splits=int(splits), N=N, f_stride=f.stride(0), f=f.data_ptr(), rad2=rad2.data_ptr(),
+                           workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+        L.check(lib.pd_knn_radii(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "pd_knn_radii")
+    return rad2
+
+
+def manifold_query_device(queries: torch.Tensor, refs: torch.Tensor, rad2: Optional[torch.Tensor] = None, splits: int = 0):
+    """:func:`manifold_query` over fp32 features that stay on the device (``pd_manifold_query``): ``(count | None, dmin2)`` ON THE DEVICE,
+    int32 [Nq] (None without ``rad2``, an fp64 device tensor [Nr]) and fp64 [Nq]."""
+    q, r = _device_features(queries, "manifold_query_device"), _device_features(refs, "manifold_query_device")
+    if q.device != r.device or q.shape[1] != r.shape[1]:
+        raise ValueError("manifold_query_device: the two feature sets must share a device and a width")
+    if rad2 is not None:
+        if not torch.is_tensor(rad2) or rad2.device != r.device or rad2.dtype != torch.float64 or rad2.shape != (r.shape[0],):
+            raise ValueError(f"manifold_query_device: rad2 must be an fp64 tensor of shape ({r.shape[0]},) on the features' device")
+        rad2 = rad2.contiguous()
+    dev, (Nq, D), Nr = q.device, q.shape, r.shape[0]
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        count = None if rad2 is None else torch.empty((Nq,), dtype=torch.int32, device=dev)
+        dmin2 = torch.empty((Nq,), dtype=torch.float64, device=dev)
+        ws_bytes = lib.pd_manifold_query_workspace(Nq, Nr, int(splits))
+        ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
+        a = L.ManifoldQueryArgs(D=D, splits=int(splits), Nq=Nq, Nr=Nr, q_stride=q.stride(0), r_stride=r.stride(0), q=q.data_ptr(), r=r.data_ptr(),
+                                rad2=L.ptr(rad2), count=L.ptr(count), dmin2=dmin2.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+        L.check(lib.pd_manifold_query(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "pd_manifold_query")
+    return count, dmin2
+
+
+def _precision_recall_on_device(gen, real, k):
+    in_real, _ = manifold_query_device(gen, real, knn_radii_device(real, k))
+    in_gen, _ = manifold_query_device(real, gen, knn_radii_device(gen, k))
+    return [(in_real > 0).sum(), (in_gen > 0).sum()]
+
+
+def _density_coverage_on_device(gen, real, k):
+    rad2 = knn_radii_device(real, k)
+    count, _ = manifold_query_device(gen, real, rad2)
+    _, dmin2 = manifold_query_device(real, gen)
+    return [count.sum(dtype=torch.int64), (torch.isfinite(dmin2) & (dmin2 <= rad2)).sum()]
+
+
+def manifold_metrics_device(features_1: torch.Tensor, features_2: torch.Tensor, neighborhood: Optional[int] = None,
+                            nearest_k: Optional[int] = None) -> dict:
+    """Either pair or both over fp32 features that stay on the device: precision / recall / f_score with ``neighborhood``, density / coverage
+    with ``nearest_k`` (None: that pair is left out).  Radii, counts and minima come from ``pd_knn_radii`` / ``pd_manifold_query``; the rows
+    inside a manifold are counted on the device and two integers per pair reach the host in ONE transfer, where they are divided (exact
+    integer sums and one correctly rounded division each, like the host twins' means: the same bits)."""
+    gen, real = _device_features(features_1, "manifold_metrics_device"), _device_features(features_2, "manifold_metrics_device")
+    parts = (_precision_recall_on_device(gen, real, neighborhood) if neighborhood is not None else []) + \
+            (_density_coverage_on_device(gen, real, nearest_k) if nearest_k is not None else [])
+    if not parts:
+        return {}
+    n = [int(v) for v in torch.stack(parts).cpu()]
+    ng, nr, out = gen.shape[0], real.shape[0], {}
+    if neighborhood is not None:
+        p, r = n[0] / ng, n[1] / nr
+        out.update({KEY_PRECISION: p, KEY_RECALL: r, KEY_F_SCORE: _f_score(p, r)})
+    if nearest_k is not None:
+        out.update({KEY_DENSITY: n[-2] / (nearest_k * ng), KEY_COVERAGE: n[-1] / nr})
+    return out
+
+
+def precision_recall_device(features_1: torch.Tensor, features_2: torch.Tensor, neighborhood: int = 3) -> dict:
+    """:func:`precision_recall` over fp32 features that stay on the device (:func:`manifold_metrics_device`)."""
+    return manifold_metrics_device(features_1, features_2, neighborhood=neighborhood)
+
+
+def density_coverage_device(features_1: torch.Tensor, features_2: torch.Tensor, nearest_k: int = 5) -> dict:
+    """:func:`density_coverage` over fp32 features that stay on the device (:func:`manifold_metrics_device`)."""
+    return manifold_metrics_device(features_1, features_2, nearest_k=nearest_k)
+
+
 def to_uint8(images) -> np.ndarray:
     """What the reference's PNG files hold: ``(images * 255).round().astype("uint8")`` of the pipeline's float NHWC output in [0, 1]
     (utils_training.py:829,915); uint8 arrays pass through."""
@@ -450,12 +621,13 @@ def extract_features_device(net: InceptionV3Features, images, batch_size: int = 
     return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
 
 
-def _calculate_metrics_device(net, input1, input2, isc, fid, kid, kid_subset_size, batch_size, input2_features) -> dict:
+def _calculate_metrics_device(net, input1, input2, isc, fid, kid, kid_subset_size, batch_size, input2_features, prc=False,
+                              prc_neighborhood=3, dc=False, dc_nearest_k=5) -> dict:
     f1 = extract_features_device(net, input1, batch_size)
     out = {}
     if isc:
         out.update(inception_score(f1["logits_unbiased"].double().cpu().numpy()))
-    if fid or kid:
+    if fid or kid or prc or dc:
         f2 = input2_features if input2_features is not None else extract_features_device(net, input2, batch_size)
         g1, g2 = f1["2048"], f2["2048"]
         if not torch.is_tensor(g2):      # features cached on the host: fp32 features widened to fp64, so the way back is exact
@@ -466,39 +638,52 @@ def _calculate_metrics_device(net, input1, input2, isc, fid, kid, kid_subset_siz
                                                *(t.cpu().numpy() for t in fid_statistics_device(g2)))
         if kid:
             out.update(kernel_inception_distance_device(g1, g2, kid_subset_size=kid_subset_size))
+        if prc or dc:      # (one transfer of the counts for both pairs)
+            out.update(manifold_metrics_device(g1, g2, prc_neighborhood if prc else None, dc_nearest_k if dc else None))
     return out
 
 
 def calculate_metrics(net: InceptionV3Features, input1, input2=None, *, isc: bool = True, fid: bool = True, kid: bool = False,
                       kid_subset_size: int = 1000, batch_size: int = 64, input2_features: Optional[dict] = None,
-                      device_statistics: bool = False) -> dict:
+                      device_statistics: bool = False, prc: bool = False, prc_neighborhood: int = 3, dc: bool = False,
+                      dc_nearest_k: int = 5) -> dict:
     """``torch_fidelity.calculate_metrics(input1=generated, input2=real, isc=, fid=, kid=, kid_subset_size=)`` on image arrays: IS of
     ``input1``; FID / KID between ``input1`` and ``input2``.  ``input2_features``: features of the real images extracted once (what the
     reference gets from ``cache_root`` / ``input2_cache_name``).  ``device_statistics``: the 2048-d features stay on the device and the
     statistics of FID (mean, covariance) and KID (per-subset MMD^2) come from ``pd_feature_moments`` / ``pd_kid_mmd``; the logits go to
-    the host for the Inception score, the covariances for the matrix square root; ``input2_features`` may then hold device tensors."""
+    the host for the Inception score, the covariances for the matrix square root; ``input2_features`` may then hold device tensors.
+    ``prc`` (``prc_neighborhood``): improved precision / recall / f_score; ``dc`` (``dc_nearest_k``): density / coverage -- both over the
+    2048-d features (:func:`precision_recall`, :func:`density_coverage`; ``pd_knn_radii`` / ``pd_manifold_query`` with
+    ``device_statistics``).  Both default to off, and nothing of them runs then."""
     if device_statistics:
-        return _calculate_metrics_device(net, input1, input2, isc, fid, kid, kid_subset_size, batch_size, input2_features)
+        return _calculate_metrics_device(net, input1, input2, isc, fid, kid, kid_subset_size, batch_size, input2_features, prc,
+                                         prc_neighborhood, dc, dc_nearest_k)
     f1 = extract_features(net, input1, batch_size)
     out = {}
     if isc:
         out.update(inception_score(f1["logits_unbiased"]))
-    if fid or kid:
+    if fid or kid or prc or dc:
         f2 = input2_features if input2_features is not None else extract_features(net, input2, batch_size)
         if fid:
             out[KEY_FID] = fid_from_statistics(*fid_statistics(f1["2048"]), *fid_statistics(f2["2048"]))
         if kid:
             out.update(kernel_inception_distance(f1["2048"], f2["2048"], kid_subset_size=kid_subset_size))
+        if prc:
+            out.update(precision_recall(f1["2048"], f2["2048"], prc_neighborhood))
+        if dc:
+            out.update(density_coverage(f1["2048"], f2["2048"], dc_nearest_k))
     return out
 
 
 def class_metrics_hook(net: InceptionV3Features, real_images_by_class: Dict[int, Sequence], results: dict, *, isc: bool = True,
                        fid: bool = True, kid: bool = False, kid_subset_size: int = 1000, batch_size: int = 64,
-                       device_statistics: bool = False):
+                       device_statistics: bool = False, prc: bool = False, prc_neighborhood: int = 3, dc: bool = False,
+                       dc_nearest_k: int = 5):
     """``on_class_done`` callback for :func:`phendiff_amd.eval_generation.generate_samples`: what ``_compute_log_metrics`` does after a
     class's images were generated (utils_training.py:948-1001) -- metrics of that class's generated images against its real images
     (their features cached per class, like ``input2_cache_name``), stored as ``results[f"{metric}/{class_name}"]``.
-    ``device_statistics``: as in :func:`calculate_metrics` (the cached features are device tensors then)."""
+    ``device_statistics``: as in :func:`calculate_metrics` (the cached features are device tensors then); ``prc`` / ``dc`` and their
+    neighbourhood sizes likewise."""
     cache: Dict[int, dict] = {}
     extract = extract_features_device if device_statistics else extract_features
 
@@ -507,7 +692,8 @@ def class_metrics_hook(net: InceptionV3Features, real_images_by_class: Dict[int,
         if class_label not in cache:
             cache[class_label] = extract(net, real_images_by_class[class_label], batch_size)
         m = calculate_metrics(net, gen, isc=isc, fid=fid, kid=kid, kid_subset_size=kid_subset_size, batch_size=batch_size,
-                              input2_features=cache[class_label], device_statistics=device_statistics)
+                              input2_features=cache[class_label], device_statistics=device_statistics, prc=prc,
+                              prc_neighborhood=prc_neighborhood, dc=dc, dc_nearest_k=dc_nearest_k)
         for k, v in m.items():
             results[f"{k}/{class_name}"] = v
     return done
