@@ -41,7 +41,8 @@ extern "C" {
  * (+ pd_guided_step_args), pd_image_preprocess_bands (+ pd_image_preprocess_bands_args), pd_image_preprocess_bands16, pd_band_histogram16,
  * pd_postproc_bands16 (+ their args structs), pd_abs_quantile (+ pd_abs_quantile_workspace), pd_ddim_raw_x0, pd_ddim_step_threshold (+ their
  * args structs), pd_tile_gather, pd_tile_blend (+ their args structs), pd_ssim (+ pd_ssim_args, pd_ssim_workspace),
- * pd_knn_radii (+ pd_knn_radii_args, pd_knn_radii_workspace), pd_manifold_query (+ pd_manifold_query_args, pd_manifold_query_workspace). */
+ * pd_knn_radii (+ pd_knn_radii_args, pd_knn_radii_workspace), pd_manifold_query (+ pd_manifold_query_args, pd_manifold_query_workspace),
+ * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance. */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -1061,6 +1062,54 @@ typedef struct {
   float* noise; float* noisy;
 } pd_train_sample_args;
 int pd_train_sample(const pd_train_sample_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_stream_noise / pd_stream_advance (added under ABI 8): out = a * x + b * z over fp32 [B][per_sample], z drawn from pd_train_sample's
+ * stream above -- the same key and counter layout, the same Box-Muller, the same rounding (csrc/pd_philox.h is compiled into both) -- at a
+ * position that lives in DEVICE memory, so that a captured launch draws new numbers on every replay.  csrc/stream_noise.hip; host side
+ * phendiff_amd.DeviceNoise; the from-noise generation of trajectories.GenerationGraph.
+ *
+ *   state: 16 bytes on the device, {uint64 seed, uint64 index}; read by every launch, written only by pd_stream_advance.
+ *   One stream per IMAGE: row b of a launch draws with step = index + index_offset + b, so image k of a run is a function of (seed, k)
+ *     alone, whatever the batch size, the rank layout or the number of batches drawn before it.  Element e of the row is flat element
+ *     elem_base + e of that stream: word (elem_base + e) & 3 of counter q = (elem_base + e) >> 2 under
+ *     counter = (q low, q high, step low 32 bits, ((step bits 32..47) << 16) | (rank << 4) | purpose), key = (seed low, seed high).
+ *     Row b equals pd_train_sample's `noise` for (seed, step, rank, purpose, B = 1, per_sample, elem_base), bit for bit.
+ *   Purposes, beside pd_train_sample's 0 (training noise), 1 (timesteps: never a noise purpose) and 2 (randn):
+ *     PD_PURPOSE_INITIAL_SAMPLE  3  x_T of a generation, elem_base = 0;
+ *     PD_PURPOSE_FORWARD_NOISE   4  the noise of add_forward_noise_to_image / DDIMScheduler.add_noise, elem_base = 0;
+ *     PD_PURPOSE_VARIANCE_NOISE  5  the variance noise of stochastic DDIM (eta > 0): trajectory step i (its position in the scheduler's
+ *                                   timesteps) takes elements i * per_sample .. (i + 1) * per_sample - 1 of the image's stream.
+ *   Coefficients: the scalars a, b by value, or -- sa and sb both given -- per-row device tables sa[B], sb[B] (DDIMScheduler.add_noise's
+ *     form).  x == NULL: out = b * z.  out may be x.  Each product and the sum are rounded separately (no contraction), as pd_add_noise
+ *     rounds them: with the tables the result is pd_add_noise's on the same z, bit for bit.
+ *   per_sample is a multiple of 4 (every model's C * H * W here), so no counter straddles two images; elem_base is arbitrary: a head or
+ *     tail counter cut by the row's ends is written element by element, everything else by 16-byte loads and stores where x and out are
+ *     aligned there.  One thread per counter; no atomics; nothing read outside x, the tables and the state, nothing written outside out.
+ *   The step field holds 48 bits.  index_offset + B beyond 2^48 is refused; the launch cannot refuse a device-side index that has grown
+ *     past it: the field then WRAPS (step mod 2^48), i.e. the streams of the first images come again.  DeviceNoise checks its host
+ *     shadow of the index before every launch.
+ * pd_stream_advance: index += n by one thread; capturable -- the last node of a captured generation, so the next replay draws the next
+ *   images.
+ * Refused before any launch: null args / state / out, a misaligned pointer, rank outside [0, 4096), purpose outside 0 .. 15 or 1, only one
+ * of sa / sb, index_offset + B > 2^48 (PD_ERR_ARG); B < 1, per_sample < 1 or no multiple of 4, a grid of 2^31 blocks or more
+ * (PD_ERR_SHAPE). */
+#define PD_PURPOSE_INITIAL_SAMPLE 3
+#define PD_PURPOSE_FORWARD_NOISE 4
+#define PD_PURPOSE_VARIANCE_NOISE 5
+typedef struct {
+  const uint64_t* state;    /* device: {seed, index} */
+  uint64_t index_offset;
+  int rank, purpose;
+  int64_t B, per_sample;
+  uint64_t elem_base;
+  float a, b;               /* used when sa == NULL */
+  const float* sa; const float* sb;   /* [B] (device) or both NULL */
+  const float* x;           /* [B][per_sample] or NULL */
+  float* out;               /* [B][per_sample]; may be x */
+} pd_stream_noise_args;
+int pd_stream_noise(const pd_stream_noise_args* a, void* stream);
+int pd_stream_advance(void* state, uint64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * pd_sample_stats (added under ABI 8): per-sample diagnostics of a batch that stays on the device -- what check_Gaussianity

@@ -13,7 +13,9 @@ from .img2img import (inversion, ddib, inverted_regeneration, classifier_free_gu
                       shard_batches, swap_binary_labels, custom_guided_generation,
                       linear_interp_custom_guidance_inverted_start, encode_to_latents, decode_to_images, LDM_preprocess, tensor_to_PIL,
                       tiled_inversion, tiled_ddib, tiled_inverted_regeneration, TiledTransferOutput)
+from .noise import DeviceNoise  # noqa: F401
 from .trajectories import DDIBGraph, CFGForwardStartGraph, SDDDIBGraph, GuidedTransferGraph, SDGuidedTransferGraph, TiledDDIBGraph  # noqa: F401
+from .trajectories import GenerationGraph  # noqa: F401
 from .tiling import TileGrid  # noqa: F401
 from . import tiling  # noqa: F401
 from .configs import UNET_CONFIGS, SCHEDULER_CONFIGS, SD15_UNET_CONFIG  # noqa: F401

@@ -35,6 +35,24 @@ def eval_batch_sizes(nb_generated_images: int, eval_batch_size: int, num_process
     return split(glob, num_processes, process_index)
 
 
+def eval_batch_offsets(nb_generated_images: int, eval_batch_size: int, num_processes: int = 1, process_index: int = 0) -> List[int]:
+    """Per batch of :func:`eval_batch_sizes` for THIS process: the number ``j`` of its first image among the class's
+    ``nb_generated_images`` (the global batches come before it in order, all of them full but the last)."""
+    tot = ceil(nb_generated_images / eval_batch_size)
+    mine = split(range(tot), num_processes, process_index)
+    return [eval_batch_size * g for g in mine]
+
+
+def generation_indices(nb_classes: int, nb_generated_images: int, eval_batch_size: int, num_processes: int = 1,
+                       process_index: int = 0) -> List[Tuple[int, int, int]]:
+    """``(class, batch size, global index of the batch's first image)`` for every batch THIS process generates: image ``j`` of class
+    ``c`` has global index ``c * nb_generated_images + j`` on whatever process draws it, so over all processes the indices cover
+    ``0 .. nb_classes * nb_generated_images - 1`` once each.  Pure host arithmetic."""
+    sizes = eval_batch_sizes(nb_generated_images, eval_batch_size, num_processes, process_index)
+    offsets = eval_batch_offsets(nb_generated_images, eval_batch_size, num_processes, process_index)
+    return [(c, bs, c * nb_generated_images + j) for c in range(nb_classes) for bs, j in zip(sizes, offsets)]
+
+
 def get_initial_best_metric() -> float:
     return float("inf")
 
@@ -87,10 +105,23 @@ class GeneratedBatch:
     filenames: List[str]
     images: np.ndarray                      # (b, H, W, C) float in [0, 1] — the pipeline's "numpy" output
     latents: Optional[torch.Tensor] = None  # SD only ("np+latent")
+    # generate_samples(device_noise=...): the uint8 images as they were quantised ON the device, (b, H, W, C); ``images`` may then be
+    # passed as None and is filled on first use by one copy, as float32 ``uint8 / 255`` (what the PNG files would hold, read back)
+    images_u8_device: Optional[torch.Tensor] = None
+
+    def __getattribute__(self, name):
+        value = object.__getattribute__(self, name)
+        if name == "images" and value is None:
+            u8 = object.__getattribute__(self, "images_u8_device")
+            if u8 is not None:
+                value = u8.cpu().numpy().astype(np.float32) / np.float32(255)
+                object.__setattr__(self, "images", value)
+        return value
 
     @property
     def uint8(self) -> np.ndarray:
-        return images_to_uint8(self.images)
+        u8 = self.images_u8_device
+        return u8.cpu().numpy() if u8 is not None else images_to_uint8(self.images)
 
 
 def _filenames(local_process_index: int, eval_batch_size: int, batch_idx: int, n: int) -> List[str]:
@@ -111,6 +142,21 @@ def generate_images_for_this_class_DDIM(pipeline, class_label: int, batch_sizes:
         images = pipeline(labels, emb, guidance_factor, generator=generator, num_inference_steps=num_inference_steps,
                           output_type="numpy").images
         yield GeneratedBatch(class_label, class_name, batch_idx, _filenames(local_process_index, ebs, batch_idx, bs), images)
+
+
+def generate_images_for_this_class_device(runners: dict, device_noise, class_label: int, batch_sizes: Sequence[int],
+                                          first_indices: Sequence[int], *, eval_batch_size: Optional[int] = None,
+                                          local_process_index: int = 0, class_name: str = "") -> Iterator[GeneratedBatch]:
+    """:func:`generate_images_for_this_class_DDIM` on captured trajectories: ``runners`` maps a batch size to its
+    :class:`~phendiff_amd.trajectories.GenerationGraph` (all drawing from ``device_noise``); batch ``i`` starts at global image index
+    ``first_indices[i]``.  The uint8 images stay on the device (``images_u8_device``: the runner's output, cloned)."""
+    ebs = eval_batch_size if eval_batch_size is not None else (max(batch_sizes) if batch_sizes else 0)
+    for batch_idx, (bs, first) in enumerate(zip(batch_sizes, first_indices)):
+        runner = runners[bs]
+        device_noise.seek(first)
+        u8 = runner.run(torch.full((bs,), class_label, device=runner.device).long()).clone()
+        yield GeneratedBatch(class_label, class_name, batch_idx, _filenames(local_process_index, ebs, batch_idx, bs), None,
+                             images_u8_device=u8)
 
 
 def generate_images_for_this_class_SD(pipeline, class_label: int, batch_sizes: Sequence[int], *, guidance_factor,
@@ -146,13 +192,27 @@ def generate_samples(pipeline, *, nb_classes: int, nb_generated_images: int, eva
                      use_ema: bool = True, class_names: Optional[Sequence[str]] = None, num_processes: int = 1,
                      process_index: int = 0, local_process_index: Optional[int] = None, generator=None,
                      latent_hw: Tuple[int, int] = (16, 16),
-                     on_class_done: Optional[Callable[[int, str, List[GeneratedBatch]], None]] = None) -> EvalGeneration:
+                     on_class_done: Optional[Callable[[int, str, List[GeneratedBatch]], None]] = None,
+                     device_noise=None, use_graph: bool = True) -> EvalGeneration:
     """Steps 2–5 of ``_generate_samples_and_compute_metrics`` (``utils_training.py:664-769``).  ``trainer`` (optional): swap
     its EMA weights in for the duration.  ``generator`` defaults to the reference's: a generator on the pipeline's device
     seeded with ``EVAL_SEED``, shared by all classes and batches (so class c's noise depends on the batches drawn before
-    it).  ``on_class_done(label, name, batches)`` is where the reference computes that class's FID/IS/KID."""
+    it).  ``on_class_done(label, name, batches)`` is where the reference computes that class's FID/IS/KID.
+
+    ``device_noise`` (a :class:`~phendiff_amd.DeviceNoise`; ``model_type="DDIM"``): the noise is drawn on the device and every batch
+    runs as one :class:`~phendiff_amd.trajectories.GenerationGraph` per distinct batch size (``use_graph=False``: the same launches,
+    eagerly); the batches carry ``images_u8_device``.  Image ``j`` of class ``c`` draws at global index ``c * nb_generated_images + j``
+    on whatever process generates it (:func:`generation_indices`) -- give every process a ``DeviceNoise`` of the same seed and rank --
+    and ``generator`` is not used."""
     if model_type not in ("DDIM", "StableDiffusion"):
         raise ValueError(f"Unknown model type {model_type}")
+    if device_noise is not None:
+        if model_type != "DDIM":
+            raise NotImplementedError("generate_samples(device_noise=...) runs model_type='DDIM' only: the latent tier has no captured "
+                                      "generation (SDGenerationGraph) yet")
+        if proba_uncond == 1:
+            raise NotImplementedError("generate_samples(device_noise=...) with proba_uncond=1: GenerationGraph takes class_emb rows for "
+                                      "class_embed_type='identity' models only")
     dev = pipeline.device if model_type == "DDIM" else pipeline._execution_device
     if generator is None:
         generator = torch.Generator(device=dev).manual_seed(EVAL_SEED)
@@ -161,6 +221,8 @@ def generate_samples(pipeline, *, nb_classes: int, nb_generated_images: int, eva
     if proba_uncond == 1:
         nb_classes = 1                                     # one pass for an unconditional model (:706-708)
     out = EvalGeneration()
+    plan = generation_indices(nb_classes, nb_generated_images, eval_batch_size, num_processes, process_index)
+    runners = {}
 
     @contextmanager
     def _noop():
@@ -169,7 +231,13 @@ def generate_samples(pipeline, *, nb_classes: int, nb_generated_images: int, eva
     with (ema_weights(trainer, use_ema) if trainer is not None else _noop()):
         for c in range(nb_classes):
             name = "unconditional" if proba_uncond == 1 else (class_names[c] if class_names is not None else str(c))
-            if model_type == "DDIM":
+            if device_noise is not None:
+                from .trajectories import GenerationGraph
+                for bs in set(sizes) - set(runners):      # (built inside ema_weights: a runner captures the weights' pointers as they are)
+                    runners[bs] = GenerationGraph(pipeline, bs, num_inference_steps, device_noise, w=guidance_factor, use_graph=use_graph)
+                it = generate_images_for_this_class_device(runners, device_noise, c, sizes, [k for cc, _, k in plan if cc == c],
+                                                           eval_batch_size=eval_batch_size, local_process_index=lpi, class_name=name)
+            elif model_type == "DDIM":
                 it = generate_images_for_this_class_DDIM(pipeline, c, sizes, guidance_factor=guidance_factor,
                                                          num_inference_steps=num_inference_steps, generator=generator,
                                                          proba_uncond=proba_uncond, eval_batch_size=eval_batch_size,

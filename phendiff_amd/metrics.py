@@ -688,7 +688,11 @@ def class_metrics_hook(net: InceptionV3Features, real_images_by_class: Dict[int,
     extract = extract_features_device if device_statistics else extract_features
 
     def done(class_label: int, class_name: str, batches):
-        gen = np.concatenate([to_uint8(b.images) for b in batches])
+        on_device = [getattr(b, "images_u8_device", None) for b in batches]
+        if device_statistics and batches and all(t is not None for t in on_device):
+            gen = torch.cat(on_device)      # generated on the device (generate_samples(device_noise=...)): the pixels never leave it
+        else:
+            gen = np.concatenate([to_uint8(b.images) for b in batches])
         if class_label not in cache:
             cache[class_label] = extract(net, real_images_by_class[class_label], batch_size)
         m = calculate_metrics(net, gen, isc=isc, fid=fid, kid=kid, kid_subset_size=kid_subset_size, batch_size=batch_size,

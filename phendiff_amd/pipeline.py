@@ -4,6 +4,9 @@
 Differences that do not change results: the conditional and unconditional UNet passes of classifier-free
 guidance feed one fused ``pd_ddim_step`` (guidance combine + scheduler update in one launch); the final
 ``(x/2+.5).clamp(0,1)`` + NCHW->NHWC is one ``pd_postproc`` launch before the single D2H copy.
+
+``generator=DeviceNoise`` (opt-in; not the reference's noise): the initial sample, the forward noise and the variance noise of the
+batch are drawn on the device, row ``b`` from the stream of image ``generator.index + b``, and the object moves on by the batch size.
 """
 from __future__ import annotations
 
@@ -16,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .noise import DeviceNoise
 from .schedulers import DDIMScheduler, randn_tensor
 
 DEFAULT_NUM_INFERENCE_STEPS = 50
@@ -121,7 +125,7 @@ class ConditionalDDIMPipeline:
     @torch.no_grad()
     def __call__(self, class_labels: Optional[torch.Tensor], class_emb: Optional[torch.Tensor] = None,
                  w: Union[int, float, torch.Tensor, None] = None,
-                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator], DeviceNoise]] = None, eta: float = 0.0,
                  num_inference_steps: int = DEFAULT_NUM_INFERENCE_STEPS, use_clipped_model_output: Optional[bool] = None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, start_image: Optional[torch.Tensor] = None,
                  add_forward_noise_to_image: bool = True, frac_diffusion_skipped: Optional[float] = None,
@@ -139,6 +143,8 @@ class ConditionalDDIMPipeline:
         image_shape = (batch_size, cin, ss, ss) if isinstance(ss, int) else (batch_size, cin, *ss)
         if start_image is not None:  # :237-245
             image = start_image.to(device=device, dtype=torch.float32)
+        elif isinstance(generator, DeviceNoise):      # row b: the initial sample of image generator.index + b
+            image = generator.randn(image_shape, DeviceNoise.PURPOSE_INITIAL_SAMPLE)
         else:
             image = self._randn(image_shape, generator, device)
         self.scheduler.set_timesteps(num_inference_steps)  # :248
@@ -147,7 +153,9 @@ class ConditionalDDIMPipeline:
             timesteps = self.scheduler.timesteps[self.scheduler.timesteps <= init_timestep]
         else:
             timesteps = self.scheduler.timesteps
-        if add_forward_noise_to_image:  # :263-269
+        if add_forward_noise_to_image and isinstance(generator, DeviceNoise):
+            image = generator.add_noise(self.scheduler, image, timesteps[0].repeat(batch_size))
+        elif add_forward_noise_to_image:  # :263-269
             noise = self._randn(image.shape, generator, device)
             image = self.scheduler.add_noise(image, noise, timesteps[0].repeat(batch_size))
         do_cfg = (isinstance(w, torch.Tensor)  # :272-284
@@ -169,6 +177,8 @@ class ConditionalDDIMPipeline:
             image, _ = self.scheduler._device_step(
                 cond, t, image, eta, bool(use_clipped_model_output), generator,
                 None, uncond_output=uncond, w=w, guidance_cfg=(guidance_eqn == "CFG"), want_x0=False)
+        if isinstance(generator, DeviceNoise):
+            generator.advance(batch_size)      # the next call draws the next images
         # :349-350 -- (image/2+.5).clamp(0,1), NCHW -> NHWC, one D2H copy
         B, Cc, H, W = image.shape
         out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=image.device)

@@ -15,6 +15,10 @@ captured trajectory: :meth:`DDIMScheduler.threshold_step` builds the launches of
 :func:`quantile_rank`.  With the default ``sample_max_value=1.0`` s is always 1 and thresholding equals clipping to [-1, 1].
 ``DDIMInverseScheduler`` does not threshold (diffusers' has ``clip_sample`` only).  ``trained_betas`` (a sequence of floats) replaces the
 named beta schedule in both.
+
+``DDIMScheduler.step(..., eta > 0, generator=DeviceNoise)`` draws the variance noise on the device: one ``pd_stream_noise`` launch in
+place on ``prev_sample`` (after the thresholding, like the host-drawn term), from the stream of the step's position in ``timesteps``
+(:class:`~phendiff_amd.noise.DeviceNoise`).  A ``torch.Generator`` or an explicit ``variance_noise`` keeps the torch arithmetic.
 """
 from __future__ import annotations
 
@@ -26,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-
+from .noise import DeviceNoise
 
 
 def randn_tensor(shape, generator, device, dtype=torch.float32):
@@ -233,10 +237,22 @@ class _SchedulerBase:
             a = self.ddim_step_args(timestep, x, mo, prev, uo, wt, guidance_cfg, use_clipped_model_output, x0, eta)
             L.check(L.lib().pd_ddim_step(C.byref(a), st), "pd_ddim_step")
         if eta > 0:
+            if variance_noise is None and isinstance(generator, DeviceNoise):
+                # one pd_stream_noise launch in place on prev_sample (after the thresholding, like the host-drawn term below)
+                generator.add_variance_noise(prev, self.step_coefficients(timestep, eta)[4], self.step_index(timestep), st)
+                return prev, x0
             if variance_noise is None:
                 variance_noise = randn_tensor(mo.shape, generator, mo.device, mo.dtype)
             prev = prev + self.step_coefficients(timestep, eta)[4] * variance_noise.to(device=mo.device, dtype=mo.dtype)
         return prev, x0
+
+    def step_index(self, timestep) -> int:
+        """The position of ``timestep`` in ``self.timesteps``: the trajectory step a ``DeviceNoise`` draws the variance noise of."""
+        t = self._t_int(timestep)
+        at = (self.timesteps == t).nonzero()
+        if at.numel() == 0:
+            raise ValueError(f"timestep {t} is not one of this scheduler's {self.timesteps.numel()} timesteps")
+        return int(at[0])
 
     def _per_sample_coefs(self, timesteps, device):
         """sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t) per sample.  The tables are computed once on the host in fp32 (the
