@@ -42,7 +42,7 @@ extern "C" {
  * pd_postproc_bands16 (+ their args structs), pd_abs_quantile (+ pd_abs_quantile_workspace), pd_ddim_raw_x0, pd_ddim_step_threshold (+ their
  * args structs), pd_tile_gather, pd_tile_blend (+ their args structs), pd_ssim (+ pd_ssim_args, pd_ssim_workspace),
  * pd_knn_radii (+ pd_knn_radii_args, pd_knn_radii_workspace), pd_manifold_query (+ pd_manifold_query_args, pd_manifold_query_workspace),
- * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance. */
+ * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance, pd_multistep_step (+ pd_multistep_step_args). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -830,6 +830,52 @@ typedef struct {
 } pd_ddim_step_threshold_args;
 int pd_ddim_raw_x0(const pd_ddim_step_threshold_args* a, float* x0, void* stream);
 int pd_ddim_step_threshold(const pd_ddim_step_threshold_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_multistep_step (added under ABI 8; csrc/multistep_kernels.hip, host side phendiff_amd.schedulers.DPMSolverMultistepScheduler /
+ * DPMSolverMultistepInverseScheduler): one update of a second-order linear multistep solver of the diffusion ODE (DPM-Solver++ 2M,
+ * arXiv 2211.01095, and its noise-prediction twin), one fused elementwise launch on dense fp32 NCHW tensors.  Per element:
+ *     o    = model_out, or the guidance combine of pd_ddim_step (same equations, same order of operations)
+ *     m0   = form 0 (data prediction):  x0 of pd_ddim_step's three prediction types from (sample, o, sqrt_a, sqrt_b), then the static
+ *                                       clamp (clip, clip_range) or, with quantile != NULL, the dynamic one of pd_ddim_step_threshold:
+ *                                       s = min(max(quantile[b], 1), sample_max_value), x0 = min(max(x0, -s), s) / s
+ *            form 1 (noise prediction): eps of pd_ddim_step's three prediction types; no clamp
+ *     prev_sample = a * sample + b * m0                        (c == 0)
+ *                   (a * sample + b * m0) + c * (m0 - m1)      (c != 0; m1 = hist_in)
+ *     hist_out = m0;   pred_x0 = m0 where given (form 0 only)
+ * every operation rounded to fp32 on its own (no contraction).  a, b, c come from the host (fp64, rounded once): the solver's exponential-
+ * integrator coefficients of the step from the level (sqrt_a, sqrt_b) to the next one; c = 0 makes the step first-order (DDIM).
+ * With c == 0 hist_in is not read at all: it may be NULL, or hold NaN.  prev_sample may alias sample; hist_out must not be hist_in.
+ * x0 goes through the inline function pd_ddim_raw_x0 goes through (csrc/pd_guided.h: ddim_x0_eps) under the same contraction setting, so
+ * pd_ddim_raw_x0 -> pd_abs_quantile -> pd_multistep_step thresholds bit for bit the x0 whose quantile was taken.
+ * A tensor of more than 1024 x 1024 elements is walked in a grid-stride loop; no host read, no allocation, capturable.
+ * Refused before any launch: null args / sample / model_out / prev_sample / hist_out, hist_in == NULL with c != 0, hist_out == hist_in,
+ * guidance without weights, a prediction type outside the three, a form outside {0, 1}, form 1 with clip != 0, a quantile or pred_x0,
+ * tensors that are not 16-byte aligned, w or a quantile that is not 4-byte aligned, a quantile with sample_max_value that is not positive
+ * (PD_ERR_ARG); numel < 1, per_sample < 1 or not a divisor of numel (PD_ERR_SHAPE). */
+typedef struct {
+  int64_t numel;            /* B*C*H*W */
+  int64_t per_sample;       /* C*H*W: element i belongs to row i / per_sample of w (per sample) and of quantile */
+  int pred_type;            /* pd_pred_type */
+  int form;                 /* 0: m0 = x0 (data prediction, "dpmsolver++"), 1: m0 = eps (noise prediction, "dpmsolver") */
+  int clip;                 /* form 0: clamp x0 to [-clip_range, clip_range] (not looked at when quantile is given) */
+  float clip_range;
+  float sqrt_a, sqrt_b;     /* sqrt(alpha_bar), sqrt(1 - alpha_bar) of the level `sample` is at */
+  float a, b, c;            /* prev_sample = a * sample + b * m0 + c * (m0 - m1) */
+  const float* sample;
+  const float* model_out;
+  const float* uncond_out;  /* NULL: no guidance */
+  const float* w;           /* guidance weights: [B] or 1 value */
+  int w_per_sample;
+  int guidance_cfg;         /* 0: imagen eqn, 1: CFG eqn */
+  const float* hist_in;     /* m1, the previous step's m0; not read when c == 0 (may be NULL then) */
+  float* prev_sample;       /* out (may alias sample) */
+  float* hist_out;          /* out: m0 (required; not hist_in) */
+  float* pred_x0;           /* out or NULL: m0 (form 0 only) */
+  const float* quantile;    /* NULL, or [numel / per_sample]: pd_abs_quantile's out (form 0 only) */
+  float sample_max_value;
+} pd_multistep_step_args;
+int pd_multistep_step(const pd_multistep_step_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Tiled trajectories (added under ABI 8; csrc/tile_kernels.hip, host side phendiff_amd.tiling): the working sample is a canvas

@@ -88,12 +88,22 @@ def load_scheduler(cls, folder: str, **overrides):
     return cls.from_config(cfg, **overrides)
 
 
+def saved_scheduler_class(folder: str):
+    """The class a pixel pipeline's saved scheduler loads as: the multistep sampler where ``_class_name`` names it, DDIM for everything
+    else (the pipeline converts whatever it is given to DDIM, as the reference's does)."""
+    from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
+    with open(os.path.join(folder, "scheduler_config.json")) as f:
+        name = json.load(f).get("_class_name")
+    return DPMSolverMultistepScheduler if name == DPMSolverMultistepScheduler.__name__ else DDIMScheduler
+
+
 def save_pipeline(pipe, folder: str, safe_serialization: bool = True) -> None:
     os.makedirs(folder, exist_ok=True)
     index = {"_class_name": "ConditionalDDIMPipeline", "_diffusers_version": "0.18.2",
              # the reference records its custom classes by module path (SURVEY.md 8f-3)
              "unet": ["src.cond_unet_2d.cond_unet_2d", "CustomCondUNet2DModel"],
-             "scheduler": ["diffusers", "DDIMScheduler"]}
+             "scheduler": ["diffusers", type(pipe.scheduler).__name__ if type(pipe.scheduler).__name__.startswith("DPMSolver")
+                           else "DDIMScheduler"]}
     with open(os.path.join(folder, "model_index.json"), "w") as f:
         json.dump(index, f, indent=2)
     save_unet(pipe.unet, os.path.join(folder, "unet"), safe_serialization)

@@ -23,15 +23,19 @@ import torch
 
 from . import _lib as L
 from .pipeline import ConditionalDDIMPipeline, require_pil_channels
-from .schedulers import THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT, DDIMInverseScheduler, quantile_rank, refuse_thresholding
+from .schedulers import (MULTISTEP_NOT_GUIDED, MULTISTEP_NOT_LATENT, MULTISTEP_NOT_TILED, THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT,
+                         DDIMInverseScheduler, inverse_scheduler, quantile_rank, refuse_multistep, refuse_thresholding)
 
 
 @torch.no_grad()
 def inversion(pipe, input_images: torch.Tensor, class_labels: torch.Tensor, num_inference_steps: int,
               proc_idx: Optional[int] = None, variant: str = "0.18.2") -> torch.Tensor:
     """``_inversion`` (utils_Img2Img.py:763-800)."""
+    from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
+    if isinstance(pipe, CustomStableDiffusionImg2ImgPipeline):
+        refuse_multistep(pipe.scheduler, "inversion with a latent-diffusion pipeline", MULTISTEP_NOT_LATENT)
     gauss = input_images.clone().detach()
-    inv = DDIMInverseScheduler.from_config(pipe.scheduler.config, variant=variant)
+    inv = inverse_scheduler(pipe.scheduler, variant)      # (the eager counterpart of trajectories._schedules)
     inv.set_timesteps(num_inference_steps)
     for t in inv.timesteps:
         model_output = pipe.unet(gauss, t, class_labels).sample
@@ -72,6 +76,7 @@ def ddib(pipe, clean_images, orig_class_labels, target_class_labels, num_inferen
     from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
     if isinstance(pipe, CustomStableDiffusionImg2ImgPipeline):
         refuse_thresholding(pipe.scheduler, "ddib with a latent-diffusion pipeline", THRESHOLDING_NOT_LATENT)      # (before the VAE encodes)
+        refuse_multistep(pipe.scheduler, "ddib with a latent-diffusion pipeline", MULTISTEP_NOT_LATENT)
         clean_images, [orig_class_cond] = LDM_preprocess(pipe, clean_images, [orig_class_labels], generator)
     elif isinstance(pipe, ConditionalDDIMPipeline):
         require_pil_channels(clean_images.shape[1], output_type)      # (before the inversion: half of the trajectory)
@@ -110,6 +115,7 @@ def _check_tiled_request(pipe, canvas_shape, who: str):
         raise NotImplementedError(f"{who}: {type(pipe).__name__} (a ConditionalDDIMPipeline is needed; the gradient-guided transfer is not tiled)")
     if len(canvas_shape) != 4:
         raise ValueError(f"{who}: expected (B, C, H, W) images, got {tuple(canvas_shape)}")
+    refuse_multistep(pipe.scheduler, who, MULTISTEP_NOT_TILED)
     c, u = pipe.scheduler.config, pipe.unet.config
     if u.in_channels != u.out_channels or canvas_shape[1] != u.in_channels:
         raise ValueError(f"{who}: {canvas_shape[1]}-channel images for a model with in_channels = {u.in_channels}, out_channels = "
@@ -274,6 +280,7 @@ def classifier_free_guidance_forward_start(pipe, clean_images, target_class_labe
     classifier-free guidance."""
     from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
     if isinstance(pipe, CustomStableDiffusionImg2ImgPipeline):       # :638-645: strength = frac_diffusion_skipped
+        refuse_multistep(pipe.scheduler, "classifier_free_guidance_forward_start with a latent-diffusion pipeline", MULTISTEP_NOT_LATENT)
         return pipe(image=clean_images, class_labels=target_class_labels, strength=frac_diffusion_skipped,
                     num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, generator=generator,
                     output_type={"numpy": "np"}.get(output_type, output_type))
@@ -337,6 +344,7 @@ def custom_guided_generation(pipe, input_images: torch.Tensor, target_class_labe
     if not ldm and not isinstance(pipe, ConditionalDDIMPipeline):
         raise NotImplementedError(type(pipe))
     refuse_thresholding(pipe.scheduler, "custom_guided_generation", THRESHOLDING_NOT_GUIDED)
+    refuse_multistep(pipe.scheduler, "custom_guided_generation", MULTISTEP_NOT_GUIDED)
     if not input_images.is_cuda:
         raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the inputs to 'cuda'")
     _check_lp_exponent(p)
@@ -407,6 +415,7 @@ def linear_interp_custom_guidance_inverted_start(pipe, clean_images, orig_class_
     ldm = isinstance(pipe, CustomStableDiffusionImg2ImgPipeline)
     target_cond = target_class_labels
     refuse_thresholding(pipe.scheduler, "the gradient-guided transfer", THRESHOLDING_NOT_GUIDED)      # (before the inversion half)
+    refuse_multistep(pipe.scheduler, "the gradient-guided transfer", MULTISTEP_NOT_GUIDED)
     if not ldm:
         require_pil_channels(clean_images.shape[1], output_type)
     if ldm:      # :663-671: images -> latents, both label tensors -> 77-token class embeddings

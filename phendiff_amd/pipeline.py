@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 from .noise import DeviceNoise
-from .schedulers import DDIMScheduler, randn_tensor
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, randn_tensor
 
 DEFAULT_NUM_INFERENCE_STEPS = 50
 
@@ -48,8 +48,10 @@ def require_pil_channels(channels: int, output_type: Optional[str]) -> None:
 
 class ConditionalDDIMPipeline:
     def __init__(self, unet, scheduler):
-        # pipeline_conditionial_ddim.py:44-47: always converted to a DDIM scheduler
-        scheduler = DDIMScheduler.from_config(scheduler.config)
+        # pipeline_conditionial_ddim.py:44-47: always converted to a DDIM scheduler -- but for the multistep sampler, which is kept
+        # (`pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)` after construction does the same)
+        if not isinstance(scheduler, DPMSolverMultistepScheduler):
+            scheduler = DDIMScheduler.from_config(scheduler.config)
         self._modules = {}
         self.register_modules(unet=unet, scheduler=scheduler)
         self._progress_bar_config = {}
@@ -78,7 +80,9 @@ class ConditionalDDIMPipeline:
         import os
         from .unet import CustomCondUNet2DModel
         unet = kwargs.pop("unet", None) or CustomCondUNet2DModel.from_pretrained(os.path.join(path, "unet"), compute_dtype=compute_dtype)
-        scheduler = kwargs.pop("scheduler", None) or DDIMScheduler.from_pretrained(os.path.join(path, "scheduler"))
+        from .checkpoint import saved_scheduler_class
+        folder = os.path.join(path, "scheduler")
+        scheduler = kwargs.pop("scheduler", None) or saved_scheduler_class(folder).from_pretrained(folder)
         return cls(unet=unet, scheduler=scheduler)
 
     def save_pretrained(self, path, safe_serialization=True):
@@ -136,6 +140,8 @@ class ConditionalDDIMPipeline:
             num_inference_steps = DEFAULT_NUM_INFERENCE_STEPS
         if guidance_eqn not in ("imagen", "CFG"):
             raise ValueError(f"Unknown guidance equation '{guidance_eqn}'; should be 'imagen' or 'CFG'")
+        if eta and isinstance(self.scheduler, DPMSolverMultistepScheduler):      # (before the first UNet evaluation)
+            raise ValueError(f"DPMSolverMultistepScheduler is a deterministic ODE solver: eta = {eta} has no SDE variant here")
         batch_size = class_labels.shape[0] if class_labels is not None else class_emb.shape[0]
         device = self.device
         ss = self.unet.config.sample_size

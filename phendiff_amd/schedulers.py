@@ -123,6 +123,37 @@ def refuse_thresholding(scheduler, who: str, why: str) -> None:
         raise ValueError(f"{who} does not run a scheduler with thresholding=True: {why}")
 
 
+MULTISTEP_NOT_TILED = "the tiled trajectories step DDIM on the canvas; the solver's history is not kept per canvas yet"
+MULTISTEP_NOT_GUIDED = ("the gradient-guided transfer pushes the sample between two steps, which invalidates the previous step's prediction "
+                        "a multistep update reuses")
+MULTISTEP_NOT_LATENT = "the multistep solvers are wired into the pixel tier (ConditionalDDIMPipeline) only"
+
+
+def refuse_multistep(scheduler, who: str, why: str) -> None:
+    """What does not run a DPM-Solver multistep scheduler says so, and why, before it packs or launches anything."""
+    if isinstance(scheduler, (DPMSolverMultistepScheduler, DPMSolverMultistepInverseScheduler)):
+        raise NotImplementedError(f"{who} does not run a {type(scheduler).__name__}: {why}")
+
+
+def sampler_grid(config, num_inference_steps: int) -> np.ndarray:
+    """The descending int64 timestep grid ``t_0 > ... > t_{S-1}`` of a sampler: diffusers' three spacings and ``steps_offset``
+    (``DDIMScheduler.set_timesteps``; the multistep schedulers walk the same grid)."""
+    n = config.num_train_timesteps
+    if num_inference_steps > n:
+        raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than {n}")
+    mode = config.timestep_spacing
+    if mode == "linspace":
+        grid = np.linspace(0, n - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
+    elif mode == "leading":
+        grid = (np.arange(num_inference_steps) * (n // num_inference_steps)).round()[::-1].copy().astype(np.int64)
+        grid += config.steps_offset
+    elif mode == "trailing":
+        grid = np.round(np.arange(n, 0, -(n / num_inference_steps))).astype(np.int64) - 1
+    else:
+        raise ValueError(f"{mode} is not supported. Choose one of 'leading', 'trailing' or 'linspace'.")
+    return grid
+
+
 def _beta_list(trained_betas):
     """``trained_betas`` as the config keeps it: None, or a plain list of floats (what a JSON config round-trips)."""
     if trained_betas is None:
@@ -246,6 +277,22 @@ class _SchedulerBase:
             prev = prev + self.step_coefficients(timestep, eta)[4] * variance_noise.to(device=mo.device, dtype=mo.dtype)
         return prev, x0
 
+    def _threshold_scratch(self, sample, stream: int):
+        """The scratch set (x0, quantiles, workspace) of a (B, n, device, stream), made on first use and kept by order of last use."""
+        B, n = sample.shape[0], sample[0].numel()
+        key = (B, n, sample.device, int(stream))
+        bufs = self._threshold_buffers.pop(key, None)
+        if bufs is None:
+            ws = L.lib().pd_abs_quantile_workspace(B, n)
+            if ws == 0:
+                raise ValueError(f"dynamic thresholding: no per-sample quantile over a ({B}, {n}) batch")
+            bufs = (torch.empty((B, n), dtype=torch.float32, device=sample.device), torch.empty((B,), dtype=torch.float32, device=sample.device),
+                    torch.empty((ws,), dtype=torch.uint8, device=sample.device))
+        self._threshold_buffers[key] = bufs                     # (re-inserted: the dict's order is the order of last use)
+        while len(self._threshold_buffers) > THRESHOLD_SCRATCH_SETS:
+            del self._threshold_buffers[next(iter(self._threshold_buffers))]
+        return bufs
+
     def step_index(self, timestep) -> int:
         """The position of ``timestep`` in ``self.timesteps``: the trajectory step a ``DeviceNoise`` draws the variance noise of."""
         t = self._t_int(timestep)
@@ -309,20 +356,8 @@ class DDIMScheduler(_SchedulerBase):
         self.timesteps = torch.from_numpy(np.arange(num_train_timesteps)[::-1].copy().astype(np.int64))
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        n = self.config.num_train_timesteps
-        if num_inference_steps > n:
-            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than {n}")
+        grid = sampler_grid(self.config, num_inference_steps)
         self.num_inference_steps = num_inference_steps
-        mode = self.config.timestep_spacing
-        if mode == "linspace":
-            grid = np.linspace(0, n - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
-        elif mode == "leading":
-            grid = (np.arange(num_inference_steps) * (n // num_inference_steps)).round()[::-1].copy().astype(np.int64)
-            grid += self.config.steps_offset
-        elif mode == "trailing":
-            grid = np.round(np.arange(n, 0, -(n / num_inference_steps))).astype(np.int64) - 1
-        else:
-            raise ValueError(f"{mode} is not supported. Choose one of 'leading', 'trailing' or 'linspace'.")
         self.timesteps = torch.from_numpy(grid)  # kept on the host: indexing tables must not sync the device
         return self
 
@@ -348,18 +383,7 @@ class DDIMScheduler(_SchedulerBase):
         holds its set itself, so whoever keeps the step (a runner's captured graph) keeps the memory it launches into."""
         c = self.config
         B, n = sample.shape[0], sample[0].numel()
-        key = (B, n, sample.device, int(stream))
-        bufs = self._threshold_buffers.pop(key, None)
-        if bufs is None:
-            ws = L.lib().pd_abs_quantile_workspace(B, n)
-            if ws == 0:
-                raise ValueError(f"dynamic thresholding: no per-sample quantile over a ({B}, {n}) batch")
-            bufs = (torch.empty((B, n), dtype=torch.float32, device=sample.device), torch.empty((B,), dtype=torch.float32, device=sample.device),
-                    torch.empty((ws,), dtype=torch.uint8, device=sample.device))
-        self._threshold_buffers[key] = bufs                     # (re-inserted: the dict's order is the order of last use)
-        while len(self._threshold_buffers) > THRESHOLD_SCRATCH_SETS:
-            del self._threshold_buffers[next(iter(self._threshold_buffers))]
-        x0_raw, quant, workspace = bufs
+        x0_raw, quant, workspace = self._threshold_scratch(sample, stream)
         sa, sb, sap, dirc, _ = self.step_coefficients(timestep, eta)
         ptr = lambda b: b.data_ptr() if torch.is_tensor(b) else b
         step = L.DdimStepThresholdArgs(
@@ -440,3 +464,291 @@ class DDIMInverseScheduler(_SchedulerBase):
         if not return_dict:
             return (prev, x0)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+
+# ---- second-order multistep solvers (DPM-Solver++ 2M, arXiv 2211.01095) ------------------------------------------------------------------
+# One update is  x' = a x + b m0 + c (m0 - m1)  (``pd_multistep_step``): m0 the model's prediction at the level the sample is at, in the
+# solver's variable (x0: the data form, the sampler's; eps: the noise form, the inversion's), m1 the previous step's.  For a step from
+# level abar_s to level abar_t, with  alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = ln alpha - ln sigma, h = lambda_t - lambda_s:
+#     data form    a = sigma_t / sigma_s    b = -alpha_t expm1(-h)       abar_t = 1: (0, 1)      abar_s = 0: (sigma_t, alpha_t)
+#     noise form   a = alpha_t / alpha_s    b = -sigma_t expm1(h)        abar_t = 0: (0, 1)
+#     c = b h / (2 h_prev)  for a second-order step whose h and h_prev (the previous step's h) are finite and non-zero; 0 otherwise
+# (the limits are taken explicitly, not through inf arithmetic).  Everything in float64 on the host from ``alphas_cumprod``; the struct
+# rounds each coefficient to fp32 once.  c = 0 is the first-order update: DDIM, written in the solver's variable.
+DATA_FORM, NOISE_FORM = 0, 1
+
+
+def _half_log_snr(abar: float) -> float:
+    """lambda = ln alpha - ln sigma; +inf at abar = 1, -inf at abar = 0."""
+    if abar >= 1.0:
+        return math.inf
+    if abar <= 0.0:
+        return -math.inf
+    return 0.5 * (math.log(abar) - math.log1p(-abar))
+
+
+def solver_coefficients(levels, form: int, solver_order: int = 2, lower_order_final: bool = False):
+    """Per step ``i`` of the path ``levels`` (n + 1 values of alpha_bar, float64) the float64 tuple ``(sqrt_a, sqrt_b, a, b, c, h)``:
+    ``sqrt_a, sqrt_b`` of the level the sample is at (what turns the model's output into m0), the update's three coefficients, and h.
+    ``lower_order_final``: the last of fewer than 15 steps is first-order."""
+    if form not in (DATA_FORM, NOISE_FORM):
+        raise ValueError(f"form must be {DATA_FORM} (data prediction) or {NOISE_FORM} (noise prediction), got {form}")
+    if solver_order not in (1, 2):
+        raise ValueError(f"solver_order must be 1 or 2, got {solver_order}")
+    levels = [float(v) for v in levels]
+    n = len(levels) - 1
+    out, h_prev = [], None
+    for i in range(n):
+        s, t = levels[i], levels[i + 1]
+        al_s, sg_s, al_t, sg_t = math.sqrt(s), math.sqrt(1.0 - s), math.sqrt(t), math.sqrt(1.0 - t)
+        h = 0.0 if s == t else _half_log_snr(t) - _half_log_snr(s)
+        if form == DATA_FORM:
+            if t >= 1.0:
+                a, b = 0.0, 1.0
+            elif s <= 0.0:
+                a, b = sg_t, al_t
+            elif s >= 1.0:
+                raise ValueError("the data form is singular going up from a noise-free level (sigma = 0): invert with the noise form")
+            else:
+                a, b = sg_t / sg_s, -al_t * math.expm1(-h)
+        else:
+            if t <= 0.0:
+                a, b = 0.0, 1.0
+            elif s <= 0.0:
+                raise ValueError("the noise form is singular going down from pure noise (alpha = 0): sample with the data form")
+            else:
+                a, b = al_t / al_s, -sg_t * math.expm1(h)
+        second = (solver_order == 2 and i > 0 and math.isfinite(h) and h != 0.0 and math.isfinite(h_prev) and h_prev != 0.0
+                  and not (lower_order_final and i == n - 1 and n < 15))
+        out.append((al_s, sg_s, a, b, 0.5 * b * h / h_prev if second else 0.0, h))
+        h_prev = h
+    return out
+
+
+class MultistepThresholdStep(ThresholdStep):
+    """The launches of one dynamically thresholded multistep update: ``pd_ddim_raw_x0``, ``pd_abs_quantile`` (:class:`ThresholdStep`'s
+    structs and scratch set, whose ``step`` carries the operands the raw x0 is made of) and ``pd_multistep_step`` with the quantile."""
+
+    def __init__(self, update: "L.MultistepStepArgs", step, quantile, x0_raw, quant, workspace, stream: int):
+        super().__init__(step, quantile, x0_raw, quant, workspace, stream)
+        self.update = update
+        assert update.quantile == quant.data_ptr() and (update.sample, update.model_out, update.uncond_out, update.w) == (
+            step.sample, step.model_out, step.uncond_out, step.w), "both structs name the same operands"
+
+    def enqueue(self, st: int):
+        if int(st) != self.stream:
+            raise ValueError(f"MultistepThresholdStep built for stream {self.stream:#x} enqueued on stream {int(st):#x}")
+        lib = L.lib()
+        L.check(lib.pd_ddim_raw_x0(C.byref(self.step), self.x0_raw.data_ptr(), st), "pd_ddim_raw_x0")      # before an in-place update
+        L.check(lib.pd_abs_quantile(C.byref(self.quantile), st), "pd_abs_quantile")
+        L.check(lib.pd_multistep_step(C.byref(self.update), st), "pd_multistep_step")
+
+
+class _MultistepBase(_SchedulerBase):
+    """What the sampler and the inversion share: the coefficient table of the path, the one place the struct is built, the eager step
+    with its two ping-pong history tensors.  A subclass sets ``form`` and, in ``set_timesteps``, ``timesteps`` and ``levels``."""
+    order = 2
+    form = DATA_FORM
+
+    def _set_path(self, num_inference_steps: int, timesteps: np.ndarray, levels):
+        self.num_inference_steps = num_inference_steps
+        self.timesteps = torch.from_numpy(np.ascontiguousarray(timesteps, dtype=np.int64))      # (on the host, as the DDIM pair's)
+        self.levels = np.asarray(levels, dtype=np.float64)
+        c = self.config
+        self._coefs = solver_coefficients(self.levels, self.form, c.solver_order, bool(getattr(c, "lower_order_final", False)))
+        self._hist, self._next_index = None, None
+
+    def _acp64(self, t: int) -> float:
+        return float(self.alphas_cumprod[int(t)].double())
+
+    def multistep_coefficients(self, i: int, first: bool = False):
+        """``(sqrt_a, sqrt_b, a, b, c)`` of step ``i`` of the path as python floats holding fp32 values.  ``first``: the trajectory starts
+        at this step (no history yet), so it is first-order whatever ``i``."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if not 0 <= i < len(self._coefs):
+            raise ValueError(f"step {i} of a path of {len(self._coefs)} steps")
+        sa, sb, a, b, c, _ = self._coefs[i]
+        return tuple(float(np.float32(v)) for v in (sa, sb, a, b, 0.0 if (first or i == 0) else c))
+
+    def step_coefficients(self, timestep, eta: float = 0.0):
+        raise ValueError(f"{type(self).__name__} has no DDIM coefficients: a step is multistep_step_args' pd_multistep_step")
+
+    def ddim_step_args(self, *args, **kw):
+        raise ValueError(f"{type(self).__name__}: a step is multistep_step_args' pd_multistep_step, not a pd_ddim_step")
+
+    def multistep_step_args(self, i: int, sample, model_out, prev_sample, hist_in, hist_out, uncond_out=None, w=None, guidance_cfg=False,
+                            pred_x0=None, first: bool = False, quantile=None, numel=None, per_sample=None, w_per_sample=None):
+        """The ``pd_multistep_step`` argument struct of step ``i`` of the path (``timesteps[i]`` is where the model was evaluated): form,
+        prediction type and clipping from the config, the coefficients from :meth:`multistep_coefficients`.  Buffers are dense fp32 tensors
+        or raw device pointers (ints), as for ``ddim_step_args``; ``hist_in`` holds the previous step's ``hist_out`` (not read by a
+        first-order step, may be None then).  ``quantile``: the (B,) output of ``pd_abs_quantile`` over this step's raw x0 (the dynamic
+        threshold replaces the clamp)."""
+        sa, sb, a, b, c = self.multistep_coefficients(i, first)
+        ptr = lambda t: t.data_ptr() if torch.is_tensor(t) else t
+        if numel is None:
+            numel, per_sample = sample.numel(), sample[0].numel()
+        if w_per_sample is None:
+            w_per_sample = torch.is_tensor(w) and w.numel() > 1
+        cfg = self.config
+        clip = self.form == DATA_FORM and bool(getattr(cfg, "clip_sample", False))
+        return L.MultistepStepArgs(numel=numel, per_sample=per_sample, pred_type=_PRED[cfg.prediction_type], form=self.form, clip=int(clip),
+                                   clip_range=float(getattr(cfg, "clip_sample_range", 1.0)), sqrt_a=sa, sqrt_b=sb, a=a, b=b, c=c,
+                                   sample=ptr(sample), model_out=ptr(model_out), uncond_out=ptr(uncond_out), w=ptr(w),
+                                   w_per_sample=int(w_per_sample), guidance_cfg=int(guidance_cfg), hist_in=ptr(hist_in) if c != 0.0 else None,
+                                   prev_sample=ptr(prev_sample), hist_out=ptr(hist_out), pred_x0=ptr(pred_x0), quantile=ptr(quantile),
+                                   sample_max_value=float(getattr(cfg, "sample_max_value", 1.0)))
+
+    def solver_step(self, i: int, sample, model_out, prev_sample, hist_in, hist_out, stream: int, uncond_out=None, w=None,
+                    guidance_cfg=False, pred_x0=None, first: bool = False):
+        """What one update enqueues: the ``pd_multistep_step`` struct, or -- ``thresholding=True`` -- a :class:`MultistepThresholdStep`
+        on ``stream`` (its scratch set is the scheduler's, one per (B, n, device, stream), as ``DDIMScheduler.threshold_step``'s).
+        ``sample`` is a dense fp32 (B, ...) tensor; the other buffers are such tensors or raw device pointers."""
+        cfg = self.config
+        if not (self.form == DATA_FORM and getattr(cfg, "thresholding", False)):
+            return self.multistep_step_args(i, sample, model_out, prev_sample, hist_in, hist_out, uncond_out, w, guidance_cfg, pred_x0, first)
+        B, n = sample.shape[0], sample[0].numel()
+        x0_raw, quant, workspace = self._threshold_scratch(sample, stream)
+        update = self.multistep_step_args(i, sample, model_out, prev_sample, hist_in, hist_out, uncond_out, w, guidance_cfg, pred_x0, first,
+                                          quantile=quant)
+        raw = L.DdimStepThresholdArgs(
+            numel=B * n, per_sample=n, pred_type=update.pred_type, use_clipped_model_output=0, sqrt_a=update.sqrt_a, sqrt_b=update.sqrt_b,
+            sqrt_ap=0.0, dir_coef=0.0, sample=update.sample, model_out=update.model_out, uncond_out=update.uncond_out, w=update.w,
+            w_per_sample=update.w_per_sample, guidance_cfg=update.guidance_cfg, prev_sample=update.prev_sample, pred_x0=None,
+            quantile=quant.data_ptr(), sample_max_value=update.sample_max_value)
+        lo, hi, wgt = quantile_rank(n, float(cfg.dynamic_thresholding_ratio))
+        q = L.AbsQuantileArgs(B=B, n=n, rank_lo=lo, rank_hi=hi, weight=wgt, x=x0_raw.data_ptr(), out=quant.data_ptr(),
+                              workspace=workspace.data_ptr())
+        return MultistepThresholdStep(update, raw, q, x0_raw, quant, workspace, int(stream))
+
+    def _device_step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None, variance_noise=None,
+                     uncond_output=None, w=None, guidance_cfg=False, out=None, want_x0=True, stream=None):
+        """The eager update at ``timestep`` (``DDIMScheduler._device_step``'s signature: the pipeline calls either).  The step's position
+        is ``timesteps``' index of ``timestep``; a step that does not follow the one before it (the first of a trajectory, a start
+        part-way down the grid, another batch shape) has no history and is first-order.  ``use_clipped_model_output`` has no meaning
+        here and is ignored; ``generator`` is not read (eta = 0: no variance noise)."""
+        if eta != 0 or variance_noise is not None:
+            raise ValueError(f"{type(self).__name__} is a deterministic ODE solver: eta = {eta} / variance noise has no SDE variant here")
+        if not (sample.is_cuda and model_output.is_cuda):
+            raise L.PhenDiffHipError("phendiff_amd schedulers step on MI355X tensors only (no CPU fallback)")
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        i = self.step_index(timestep)
+        x = sample.contiguous().float()
+        mo = model_output.contiguous().float()
+        prev = torch.empty_like(x) if out is None else out
+        x0 = torch.empty_like(x) if (want_x0 and self.form == DATA_FORM) else None
+        wt = uo = None
+        if uncond_output is not None:
+            uo = uncond_output.contiguous().float()
+            wt = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+        hist = self._hist
+        first = hist is None or self._next_index != i or hist[0].shape != x.shape or hist[0].device != x.device
+        if hist is None or hist[0].shape != x.shape or hist[0].device != x.device:
+            hist = self._hist = (torch.empty_like(x), torch.empty_like(x))
+        st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+        a = self.solver_step(i, x, mo, prev, hist[(i + 1) % 2], hist[i % 2], st, uo, wt, guidance_cfg, x0, first)
+        if isinstance(a, ThresholdStep):
+            a.enqueue(st)
+        else:
+            L.check(L.lib().pd_multistep_step(C.byref(a), st), "pd_multistep_step")
+        self._next_index = i + 1
+        return prev, x0
+
+    def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False, generator=None,
+             variance_noise=None, return_dict: bool = True):
+        if generator is not None:
+            raise ValueError(f"{type(self).__name__} is a deterministic ODE solver: it draws no variance noise, so it takes no generator")
+        prev, x0 = self._device_step(model_output, timestep, sample, eta, use_clipped_model_output, None, variance_noise)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+
+class DPMSolverMultistepScheduler(_MultistepBase):
+    """diffusers ``DPMSolverMultistepScheduler`` surface for DPM-Solver++ 2M ("dpmsolver++", "midpoint"), on ``DDIMScheduler``'s tables
+    and timestep grid: ``DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`` samples in the data form.  Step ``i``
+    evaluates the model at ``timesteps[i]`` and moves from ``levels[i]`` to ``levels[i + 1]``; the last level is alpha_bar = 1
+    (``final_sigmas_type="zero"``) or ``alphas_cumprod[0]`` ("sigma_min").  ``clip_sample`` (default False, diffusers' behaviour; a
+    scheduler made ``from_config`` of a DDIM config clips as that DDIM does) and ``thresholding`` limit x0 as ``DDIMScheduler`` does.
+    ``set_alpha_to_one`` is kept in the config for the round trip and not used."""
+    form = DATA_FORM
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 clip_sample=False, set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon", thresholding=False,
+                 dynamic_thresholding_ratio=0.995, clip_sample_range=1.0, sample_max_value=1.0, timestep_spacing="leading",
+                 rescale_betas_zero_snr=False, solver_order=2, algorithm_type="dpmsolver++", solver_type="midpoint",
+                 lower_order_final=True, final_sigmas_type="zero", **ignored):
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order}")
+        if algorithm_type != "dpmsolver++":
+            raise ValueError(f"algorithm_type {algorithm_type!r}: DPMSolverMultistepScheduler samples with 'dpmsolver++' only")
+        if solver_type != "midpoint":
+            raise ValueError(f"solver_type {solver_type!r}: 'midpoint' only")
+        if final_sigmas_type not in ("zero", "sigma_min"):
+            raise ValueError(f"final_sigmas_type must be 'zero' or 'sigma_min', got {final_sigmas_type!r}")
+        if thresholding:
+            quantile_rank(1, dynamic_thresholding_ratio)
+            if not float(sample_max_value) > 0:
+                raise ValueError(f"sample_max_value must be positive, got {sample_max_value}")
+        cfg = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                   trained_betas=_beta_list(trained_betas), clip_sample=clip_sample, set_alpha_to_one=set_alpha_to_one,
+                   steps_offset=steps_offset, prediction_type=prediction_type, thresholding=bool(thresholding),
+                   dynamic_thresholding_ratio=dynamic_thresholding_ratio, clip_sample_range=clip_sample_range,
+                   sample_max_value=sample_max_value, timestep_spacing=timestep_spacing, rescale_betas_zero_snr=rescale_betas_zero_snr,
+                   solver_order=solver_order, algorithm_type=algorithm_type, solver_type=solver_type,
+                   lower_order_final=bool(lower_order_final), final_sigmas_type=final_sigmas_type)
+        self._finish_init(cfg, rescale_betas_zero_snr)
+        self.timesteps = torch.from_numpy(np.arange(num_train_timesteps)[::-1].copy().astype(np.int64))
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        grid = sampler_grid(self.config, num_inference_steps)
+        if self.config.final_sigmas_type == "zero":
+            final = 1.0
+        elif int(grid[-1]) == 0:
+            raise ValueError("final_sigmas_type='sigma_min' with a grid that ends at timestep 0: the last step would not move")
+        else:
+            final = self._acp64(0)
+        self._set_path(num_inference_steps, grid, [self._acp64(t) for t in grid] + [final])
+        return self
+
+
+class DPMSolverMultistepInverseScheduler(_MultistepBase):
+    """The inversion that pairs with :class:`DPMSolverMultistepScheduler`: the same second-order multistep rule in the noise form
+    ("dpmsolver"), climbing the sampler's own grid.  The data form is singular going up from sigma ~ 0, the noise form is not.
+    Path: ``u = sorted({0} | sampler grid)``, ``timesteps = u[:-1]``; step ``j`` regards the sample as at ``alphas_cumprod[u_j]``,
+    evaluates the model there and moves to ``alphas_cumprod[u_{j + 1}]``, so the inversion ends exactly at the level the sampler starts
+    from (S steps; S - 1 on a grid that already holds 0).  No clamp, no thresholding (as ``DDIMInverseScheduler``), and no
+    ``lower_order_final`` (the sampler's key, ignored here: the last step of an inversion is at high noise, where second order is stable)."""
+    form = NOISE_FORM
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 steps_offset=0, prediction_type="epsilon", timestep_spacing="leading", rescale_betas_zero_snr=False, solver_order=2,
+                 **ignored):
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order}")
+        cfg = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                   trained_betas=_beta_list(trained_betas), steps_offset=steps_offset, prediction_type=prediction_type,
+                   timestep_spacing=timestep_spacing, rescale_betas_zero_snr=rescale_betas_zero_snr, solver_order=solver_order)
+        self._finish_init(cfg, rescale_betas_zero_snr)
+        self.timesteps = torch.from_numpy(np.arange(num_train_timesteps).copy().astype(np.int64))
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        u = sorted({0} | {int(t) for t in sampler_grid(self.config, num_inference_steps)})
+        self._set_path(num_inference_steps, np.array(u[:-1], dtype=np.int64), [self._acp64(t) for t in u])
+        return self
+
+    def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False, variance_noise=None,
+             return_dict: bool = True):
+        prev, _ = self._device_step(model_output, timestep, sample, eta, False, None, variance_noise, want_x0=False)
+        if not return_dict:
+            return (prev, None)
+        return SchedulerOutput(prev_sample=prev, pred_original_sample=None)
+
+
+def inverse_scheduler(forward, variant: str = "0.18.2"):
+    """The inversion that pairs with a forward scheduler, from its config: the multistep inverse for a multistep sampler,
+    ``DDIMInverseScheduler(variant=...)`` otherwise.  The one place the transfers choose."""
+    if isinstance(forward, DPMSolverMultistepScheduler):
+        return DPMSolverMultistepInverseScheduler.from_config(forward.config)
+    return DDIMInverseScheduler.from_config(forward.config, variant=variant)

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from .pipeline import numpy_to_pil
-from .schedulers import THRESHOLDING_NOT_LATENT, DDIMScheduler, randn_tensor, refuse_thresholding
+from .schedulers import MULTISTEP_NOT_LATENT, THRESHOLDING_NOT_LATENT, DDIMScheduler, randn_tensor, refuse_multistep, refuse_thresholding
 from .vae import VaeImageProcessor
 
 DEFAULT_NUM_INFERENCE_STEPS = 50
@@ -36,6 +36,7 @@ def hack_class_embedding(cl_embed: torch.Tensor) -> torch.Tensor:
 class CustomStableDiffusionImg2ImgPipeline:
     def __init__(self, vae, unet, scheduler, class_embedding):
         refuse_thresholding(scheduler, type(self).__name__, THRESHOLDING_NOT_LATENT)
+        refuse_multistep(scheduler, type(self).__name__, MULTISTEP_NOT_LATENT)
         cfg = dict(vars(scheduler.config)) if not isinstance(scheduler.config, dict) else dict(scheduler.config)
         patched = False
         if cfg.get("steps_offset", 1) != 1:                   # :74-91 (deprecation fix-up)
@@ -229,6 +230,7 @@ class CustomStableDiffusionImg2ImgPipeline:
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
                  cross_attention_kwargs: Optional[Dict[str, Any]] = None, device=None):
         refuse_thresholding(self.scheduler, type(self).__name__, THRESHOLDING_NOT_LATENT)      # (a scheduler swapped in after construction)
+        refuse_multistep(self.scheduler, type(self).__name__, MULTISTEP_NOT_LATENT)
         self.check_inputs(class_labels=class_labels, strength=strength, callback_steps=callback_steps,
                           class_labels_embeds=class_labels_embeds, latent_shape=latent_shape, image=image,
                           guidance_scale=guidance_scale)

@@ -12,6 +12,10 @@ no Python launch cost (~120 launches x 2*S per batch otherwise).  Same arithmeti
   * :class:`TiledDDIBGraph` is :class:`DDIBGraph`'s string of phases on a canvas larger than the training size: its UNet phase
     (``_unet``) is ``img2img._TiledForward`` -- gather the tiles, the plan over them, blend -- and its class table has a row per tile.
 
+A pipeline whose scheduler is a ``DPMSolverMultistepScheduler`` runs the pixel runners but the tiled and the gradient-guided one: the
+inversion is then ``DPMSolverMultistepInverseScheduler`` (``_schedules`` chooses by the forward scheduler's type), a step is
+``pd_multistep_step`` and the runner owns the solver's two history buffers (``_PixelTrajectory._solver_steps``).
+
 Inside a capture every torch call is a device-to-device operation between pre-allocated buffers on the runner's stream; nothing allocates.
 """
 from __future__ import annotations
@@ -25,8 +29,8 @@ from . import img2img as E
 from .img2img import GUIDANCE_MIN_GRAD_SCALE, _LpGuidance, _check_lp_exponent
 from .noise import DeviceNoise
 from .pipeline import ConditionalDDIMPipeline
-from .schedulers import (THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT, DDIMInverseScheduler, ThresholdStep, randn_tensor,
-                         refuse_thresholding)
+from .schedulers import (MULTISTEP_NOT_GUIDED, MULTISTEP_NOT_LATENT, THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT,
+                         DPMSolverMultistepScheduler, ThresholdStep, inverse_scheduler, randn_tensor, refuse_multistep, refuse_thresholding)
 
 
 def _identity_rows(cond: torch.Tensor, B: int, tdim: int, device) -> torch.Tensor:
@@ -87,7 +91,7 @@ def _check_shape(what: torch.Tensor, static: torch.Tensor):
 def _schedules(pipe, S: int, variant: str, gen_timesteps=lambda fwd: fwd.timesteps, **set_kw):
     """(inverse scheduler, the pipeline's forward scheduler, inversion timesteps, generation timesteps) at ``S`` steps: host tables, the
     timesteps as Python ints.  ``gen_timesteps(fwd)``: the forward timesteps the method keeps (default: all of them)."""
-    inv = DDIMInverseScheduler.from_config(pipe.scheduler.config, variant=variant)
+    inv = inverse_scheduler(pipe.scheduler, variant)      # (by the forward scheduler's type: DDIM's inverse, or the multistep one)
     inv.set_timesteps(S)
     fwd = pipe.scheduler
     fwd.set_timesteps(S, **set_kw)
@@ -156,6 +160,7 @@ def _check_guided_request(pipe, pipe_type, p):
     if not isinstance(pipe, pipe_type):
         raise NotImplementedError(f"{type(pipe).__name__}: this runner drives a {pipe_type.__name__}")
     refuse_thresholding(pipe.scheduler, "the gradient-guided transfer", THRESHOLDING_NOT_GUIDED)
+    refuse_multistep(pipe.scheduler, "the gradient-guided transfer", MULTISTEP_NOT_GUIDED)
     if pipe.unet.device.type != "cuda":
         raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the pipeline to 'cuda'")
 
@@ -292,9 +297,25 @@ class _PixelTrajectory(_TrajectoryRunner):
                                         use_clipped_model_output, eta=eta)
         return sched.ddim_step_args(t, self.x, self.model_out, self.x, uncond_out, w, guidance_cfg, use_clipped_model_output, eta=eta)
 
+    multistep = property(lambda self: isinstance(self.pipe.scheduler, DPMSolverMultistepScheduler),
+                         doc="the pipeline samples with the multistep solver (its runs of steps are _solver_steps')")
+
+    def _solver_steps(self, sched, timesteps, uncond_out=None, w=None, guidance_cfg=False):
+        """The in-place updates of ``x`` along ``timesteps`` (a run of consecutive entries of ``sched.timesteps``) under a multistep
+        scheduler, forward or inverse: per step its ``pd_multistep_step`` arguments (or the thresholded form's launches).  The two
+        history buffers are the runner's own (``hist``), allocated on first use -- after every buffer the DDIM form allocates -- and
+        ping-ponged by the position in the run; the first step of a run is first-order, so nothing is carried from run to run or
+        from replay to replay."""
+        if getattr(self, "hist", None) is None:
+            self.hist = (torch.empty_like(self.x), torch.empty_like(self.x))
+        return [sched.solver_step(sched.step_index(t), self.x, self.model_out, self.x, self.hist[(k + 1) % 2], self.hist[k % 2],
+                                  self.stream.cuda_stream, uncond_out, w, guidance_cfg, first=(k == 0))
+                for k, t in enumerate(timesteps)]
+
     def _ddim_steps(self, st, step_args, first: int = 0, uncond=None, variance=None):
         """Per entry of ``step_args``: the UNet from ``x`` into ``model_out`` under row block ``first + i`` of ``temb``, then its
-        ``pd_ddim_step`` (or the launches of its thresholded form, the ones the eager ``step`` enqueues).  ``uncond = (table, out)``: a
+        ``pd_ddim_step`` (or the launches of its thresholded form, the ones the eager ``step`` enqueues; or, for an entry of
+        :meth:`_solver_steps`, its ``pd_multistep_step``: the dispatch is on the argument's type).  ``uncond = (table, out)``: a
         second evaluation under the same row block of another table before the update.  ``variance``: per entry the ``pd_stream_noise``
         arguments of the step's variance term (stochastic DDIM), launched after the update."""
         step_bytes = self.rows_per_step * self.plan.w.proj_dim * 4
@@ -304,6 +325,8 @@ class _PixelTrajectory(_TrajectoryRunner):
                 self._unet(st, uncond[0].data_ptr() + i * step_bytes, uncond[1].data_ptr())
             if isinstance(a, ThresholdStep):
                 a.enqueue(st)
+            elif isinstance(a, L.MultistepStepArgs):
+                L.check(self.lib.pd_multistep_step(C.byref(a), st), "pd_multistep_step")
             else:
                 L.check(self.lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
             if variance is not None:
@@ -332,9 +355,13 @@ class DDIBGraph(_PixelTrajectory):
         self.inv, fwd, self.inv_ts, self.gen_ts = _schedules(
             pipe, self.S, variant, lambda fwd: fwd.timesteps[fwd.timesteps <= fwd.config.num_train_timesteps * (1 - 0)])
         self._class_table(self.inv_ts + self.gen_ts)
-        self.inv_args = [self.inv.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.inv_ts]
-        self.gen_args = [self._forward_step_args(fwd, t) for t in self.gen_ts]
-        self._inverted_snapshot()
+        if self.multistep:
+            self._inverted_snapshot()
+            self.inv_args, self.gen_args = self._solver_steps(self.inv, self.inv_ts), self._solver_steps(fwd, self.gen_ts)
+        else:
+            self.inv_args = [self.inv.ddim_step_args(t, self.x, self.model_out, self.x) for t in self.inv_ts]
+            self.gen_args = [self._forward_step_args(fwd, t) for t in self.gen_ts]
+            self._inverted_snapshot()
         self._capture()
 
     def _enqueue(self, st):
@@ -498,8 +525,11 @@ class CFGForwardStartGraph(_PixelTrajectory):
         self.noise_args = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0,
                                          x=self.clean.data_ptr(), noise=self.noise.data_ptr(), sa=sa.data_ptr(),
                                          sb=sb.data_ptr(), out=self.x.data_ptr())
-        self.step_args = [self._forward_step_args(sch, t, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
-                          for t in self.ts]
+        if self.multistep:
+            self.step_args = self._solver_steps(sch, self.ts, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
+        else:
+            self.step_args = [self._forward_step_args(sch, t, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
+                              for t in self.ts]
         self._capture()
 
     def _enqueue(self, st):
@@ -546,6 +576,8 @@ class GenerationGraph(_PixelTrajectory):
             raise TypeError(f"GenerationGraph draws from a DeviceNoise, not from a {type(noise).__name__}")
         if torch.is_tensor(w) and (w.ndim != 1 or w.shape[0] != batch_size):
             raise ValueError("w must be a 1D tensor of shape (batch_size,) if not None and not a single int/float.")
+        if eta and isinstance(pipe.scheduler, DPMSolverMultistepScheduler):
+            raise ValueError(f"GenerationGraph: DPMSolverMultistepScheduler is a deterministic ODE solver: eta = {eta} has no SDE variant here")
         if pipe.unet.device.type != "cuda":
             raise L.PhenDiffHipError("phendiff_amd runs on MI355X only (no CPU fallback): move the pipeline to 'cuda'")
         super().__init__(pipe, batch_size, num_inference_steps, height, width, None, use_graph)
@@ -567,8 +599,11 @@ class GenerationGraph(_PixelTrajectory):
             self.w_dev = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
         per = x[0].numel()
         self.init_args = noise.launch_args(x, B, per, DeviceNoise.PURPOSE_INITIAL_SAMPLE)
-        self.step_args = [self._forward_step_args(sch, t, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG",
-                                                  use_clipped_model_output, self.eta) for t in self.ts]
+        if self.multistep:
+            self.step_args = self._solver_steps(sch, self.ts, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
+        else:
+            self.step_args = [self._forward_step_args(sch, t, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG",
+                                                      use_clipped_model_output, self.eta) for t in self.ts]
         self.var_args = None
         if self.eta > 0:
             self.var_args = [noise.variance_args(i, x, sch.step_coefficients(t, self.eta)[4]) for i, t in enumerate(self.ts)]
@@ -686,6 +721,7 @@ class _LatentTrajectory(_TrajectoryRunner):
 
     def __init__(self, pipe, batch_size, num_inference_steps, height, width, device, use_graph, input_grad=False):
         refuse_thresholding(pipe.scheduler, type(self).__name__, THRESHOLDING_NOT_LATENT)
+        refuse_multistep(pipe.scheduler, type(self).__name__, MULTISTEP_NOT_LATENT)
         self.pipe = pipe
         unet, vae = pipe.unet, pipe.vae
         super().__init__(unet, batch_size, num_inference_steps, height, width, device, use_graph)
