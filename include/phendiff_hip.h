@@ -42,7 +42,8 @@ extern "C" {
  * pd_postproc_bands16 (+ their args structs), pd_abs_quantile (+ pd_abs_quantile_workspace), pd_ddim_raw_x0, pd_ddim_step_threshold (+ their
  * args structs), pd_tile_gather, pd_tile_blend (+ their args structs), pd_ssim (+ pd_ssim_args, pd_ssim_workspace),
  * pd_knn_radii (+ pd_knn_radii_args, pd_knn_radii_workspace), pd_manifold_query (+ pd_manifold_query_args, pd_manifold_query_workspace),
- * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance, pd_multistep_step (+ pd_multistep_step_args). */
+ * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance, pd_multistep_step (+ pd_multistep_step_args), pd_guidance_rescale
+ * (+ pd_guidance_rescale_args, pd_guidance_rescale_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -876,6 +877,49 @@ typedef struct {
   float sample_max_value;
 } pd_multistep_step_args;
 int pd_multistep_step(const pd_multistep_step_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pd_guidance_rescale (added under ABI 8; csrc/guidance_rescale.hip, host side phendiff_amd.schedulers.GuidanceRescale): the guided
+ * prediction of classifier-free guidance brought back towards the conditional prediction's per-sample standard deviation -- the third
+ * fix of arXiv 2305.08891 (section 3.4), diffusers' rescale_noise_cfg -- on dense fp32 [B][per_sample] tensors.  Per sample b:
+ *     cfg_i  = the guidance combine of pd_ddim_step: uncond + w (cond - uncond) (imagen) or cond + w (cond - uncond) (CFG), cond =
+ *              model_out; the same operations in the same order, each rounded to fp32 on its own (csrc/pd_guided.h: guidance_combine)
+ *     s_cond, s_cfg = the unbiased (n - 1) standard deviations of cond and of cfg over the sample, from sum x and sum x^2 accumulated in
+ *              fp64 (the square of an fp32 value is exact in fp64): var = max((sum x^2 - (sum x)^2 / n) / (n - 1), 0)
+ *     g_b    = rescale * (s_cond / s_cfg) + (1 - rescale)       in fp64, rounded to fp32 once
+ *     out_i  = cfg_i * g_b                                       one fp32 multiply
+ * which is rescale_noise_cfg factored: rescale * cfg * r + (1 - rescale) * cfg = cfg * (rescale * r + 1 - rescale).
+ * Two launches: per-chunk partial sums -- one workgroup of 256 threads per (sample, chunk of PD_GUIDANCE_RESCALE_CHUNK elements) -- then
+ * the apply pass on the same tiling, in which every workgroup folds its own sample's partials.  Every sum runs in one fixed order: lane (a
+ * thread's elements by ascending index), wave (xor butterfly 32 ... 1), workgroup (waves 0..3), chunk (256 runs of consecutive chunks in
+ * index order, then the runs in index order).  Which element a lane takes depends on the element's index within its sample only: a
+ * sample's result is a function of that sample alone -- not of B, of its row in the batch, of its alignment, of the grid or of the replay.
+ * No atomics, no host read, no allocation, capturable; each input is read twice and out written once.
+ *   Rows need not be 16-byte aligned (per_sample % 4 != 0): 16-byte accesses are used where four elements lie whole inside the row at an
+ *   aligned address, element accesses everywhere else; nothing outside a row enters its sums.
+ *   out may alias model_out (or uncond_out): the apply pass reads an element's inputs before it writes that element, and nothing else.
+ *   More than 65536 (sample, chunk) pairs are walked in a grid-stride loop.
+ *   A sample with s_cfg = 0 or with a NaN / infinity gives IEEE inf / NaN in its own row and touches no other row.
+ *   workspace: pd_guidance_rescale_workspace(B, per_sample) bytes (0 for sizes the call refuses), 8-byte aligned, contents irrelevant
+ *   before and after (every partial the apply pass reads was written by the first launch).
+ * Refused before any launch: null args / model_out / uncond_out / w / out / workspace, rescale that is not finite or outside [0, 1],
+ * tensors that are not 16-byte aligned, w that is not 4-byte aligned, a workspace that is not 8-byte aligned (PD_ERR_ARG); numel < 1,
+ * per_sample < 2 or not a divisor of numel, more than 2^31 - 1 (sample, chunk) pairs (PD_ERR_SHAPE). */
+#define PD_GUIDANCE_RESCALE_CHUNK 8192
+typedef struct {
+  int64_t numel;            /* B*C*H*W */
+  int64_t per_sample;       /* C*H*W: the elements of one sample (one standard deviation, one guidance weight) */
+  const float* model_out;   /* the conditional prediction */
+  const float* uncond_out;  /* the unconditional prediction */
+  const float* w;           /* guidance weights: [B] or 1 value */
+  int w_per_sample;
+  int guidance_cfg;         /* 0: imagen eqn, 1: CFG eqn */
+  float rescale;            /* phi in [0, 1]: 0 leaves the guided prediction as it is, 1 gives it the conditional one's std */
+  float* out;               /* the rescaled guided prediction (may alias model_out) */
+  void* workspace;          /* pd_guidance_rescale_workspace(numel / per_sample, per_sample) bytes */
+} pd_guidance_rescale_args;
+size_t pd_guidance_rescale_workspace(int64_t B, int64_t n);
+int pd_guidance_rescale(const pd_guidance_rescale_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Tiled trajectories (added under ABI 8; csrc/tile_kernels.hip, host side phendiff_amd.tiling): the working sample is a canvas

@@ -9,6 +9,7 @@ from ._lib import PhenDiffHipError, lib  # noqa: F401
 from .unet import CustomCondUNet2DModel, UNet2DOutput  # noqa: F401
 from .schedulers import DDIMScheduler, DDIMInverseScheduler, quantile_rank  # noqa: F401
 from .schedulers import DPMSolverMultistepScheduler, DPMSolverMultistepInverseScheduler  # noqa: F401
+from .schedulers import GuidanceRescale, guidance_rescale  # noqa: F401
 from .pipeline import ConditionalDDIMPipeline, ImagePipelineOutput  # noqa: F401
 from .img2img import (inversion, ddib, inverted_regeneration, classifier_free_guidance_forward_start,  # noqa: F401
                       shard_batches, swap_binary_labels, custom_guided_generation,

@@ -1,0 +1,212 @@
+// pd_guidance_rescale: classifier-free guidance with the guided prediction brought back towards the conditional prediction's per-sample
+// standard deviation (arXiv 2305.08891 section 3.4; diffusers' rescale_noise_cfg), on dense fp32 [B][n] tensors.  Contract:
+// include/phendiff_hip.h.  Host side: phendiff_amd.schedulers.GuidanceRescale.
+//     cfg = guidance_combine(cond, uncond, w)   (pd_guided.h: the step kernels' expression)
+//     g_b = phi * std(cond_b) / std(cfg_b) + (1 - phi)   (fp64, rounded to fp32 once)          out = cfg * g_b
+//
+// Two launches on one stream, no host synchronisation, the same tiling in both: a sample is cut into chunks of
+// PD_GUIDANCE_RESCALE_CHUNK elements and a workgroup of 256 threads takes one (sample, chunk) at a time.
+//   partial: sum cond, sum cond^2, sum cfg, sum cfg^2 of the chunk in fp64 -> workspace [B][chunks][4]
+//   apply:   every workgroup folds ITS sample's partials (all of them, in one order), makes g_b, and writes cfg * g_b for its chunk
+// The fold is repeated by each of a sample's workgroups instead of being a launch of its own: it reads 32 bytes per chunk (768 bytes for a
+// 3 x 256 x 256 image) from L2, against the 96 KiB the workgroup streams.  Traffic per element: cond and uncond read twice, out written once.
+//
+// Determinism (sample_stats.hip's rule): every reduction runs in one fixed order -- lane (a thread's elements by ascending index), wave
+// (xor butterfly 32, 16, ... 1), workgroup (waves 0..3), chunk (runs of consecutive chunks in index order, then the runs in index order).
+// Which element a lane takes depends only on the element's index WITHIN ITS SAMPLE, never on the address: the 16-byte access is used
+// where four elements lie whole inside the sample at an aligned address, element accesses everywhere else, and both hand the same values
+// to the same lane.  So a sample's g does not depend on B, on its row in the batch, on its alignment, on the grid or on the replay.
+#include "pd_guided.h"
+
+namespace pd {
+namespace {
+
+constexpr int CHUNK = PD_GUIDANCE_RESCALE_CHUNK, ITERS = CHUNK / (256 * 4), NSUM = 4;
+constexpr int64_t MAX_BLOCKS = 65536;      // more (sample, chunk) pairs than this are walked in a grid-stride loop
+static_assert(CHUNK % (256 * 4) == 0, "a chunk is a whole number of passes of 256 threads x 4 elements");
+
+struct Launch {
+  pd_guidance_rescale_args a;
+  int64_t chunks, items;     // chunks per sample; items = B * chunks
+  double* part;              // [B][chunks][NSUM]
+};
+
+// the first min(cnt, 4) elements at p (cnt <= 0: nothing is read); returns how many are valid
+__device__ __forceinline__ int load_slot(const float* p, int cnt, float (&v)[4]) {
+  if (cnt >= 4 && ((uintptr_t)p & 15) == 0) {
+    const f32x4 q = *(const f32x4*)p;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = q[k];
+    return 4;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = k < cnt ? p[k] : 0.f;
+  return cnt < 0 ? 0 : (cnt < 4 ? cnt : 4);
+}
+
+// where (sample, chunk) pair `item` lies: the row, the offset of the chunk's first element in the tensor, its number of elements
+struct Tile { int64_t b, off; int rem; };
+__device__ __forceinline__ Tile tile_of(const Launch& p, int64_t item) {
+  Tile t;
+  t.b = item / p.chunks;
+  const int64_t j0 = (item - t.b * p.chunks) * CHUNK, left = p.a.per_sample - j0;
+  t.off = t.b * p.a.per_sample + j0;
+  t.rem = left < CHUNK ? (int)left : CHUNK;
+  return t;
+}
+
+__global__ __launch_bounds__(256) void guidance_rescale_partial_kernel(const Launch p) {
+#pragma clang fp contract(off)
+  __shared__ double red[4][NSUM];
+  const pd_guidance_rescale_args& a = p.a;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  for (int64_t item = blockIdx.x; item < p.items; item += gridDim.x) {
+    const Tile tl = tile_of(p, item);
+    const float* co = a.model_out + tl.off;
+    const float* un = a.uncond_out + tl.off;
+    const float w = a.w_per_sample ? a.w[tl.b] : a.w[0];
+    double acc[NSUM] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i) {
+      const int e0 = (i * 256 + t) * 4;
+      float o[4], u[4];
+      const int cnt = load_slot(co + e0, tl.rem - e0, o);
+      load_slot(un + e0, tl.rem - e0, u);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k < cnt) {
+          const double c = (double)o[k], g = (double)guidance_combine(a.guidance_cfg, o[k], u[k], w);
+          acc[0] += c;
+          acc[1] += c * c;      // (exact: 48 significant bits at most)
+          acc[2] += g;
+          acc[3] += g * g;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NSUM; ++i) {
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) acc[i] += __shfl_xor(acc[i], m);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < NSUM; ++i) red[wave][i] = acc[i];
+    }
+    __syncthreads();
+    if (t < NSUM) p.part[item * NSUM + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    __syncthreads();      // (red is written again by the next pair of a grid-stride walk)
+  }
+}
+
+__global__ __launch_bounds__(256) void guidance_rescale_apply_kernel(const Launch p) {
+#pragma clang fp contract(off)
+  __shared__ double red[256][NSUM];
+  __shared__ float g_s;
+  const pd_guidance_rescale_args& a = p.a;
+  const int t = threadIdx.x;
+  const int64_t per = (p.chunks + 255) / 256;
+  const int runs = (int)((p.chunks + per - 1) / per);      // <= 256, every one of them non-empty
+  for (int64_t item = blockIdx.x; item < p.items; item += gridDim.x) {
+    const Tile tl = tile_of(p, item);
+    // the sample's four sums: thread r folds the run of consecutive chunks [r * per, (r + 1) * per) in index order, thread 0 the runs in order
+    if (t < runs) {
+      const int64_t c0 = t * per, c1 = c0 + per < p.chunks ? c0 + per : p.chunks;
+      const double* in = p.part + tl.b * p.chunks * NSUM;
+      double acc[NSUM];
+#pragma unroll
+      for (int i = 0; i < NSUM; ++i) acc[i] = in[c0 * NSUM + i];
+      for (int64_t c = c0 + 1; c < c1; ++c) {
+#pragma unroll
+        for (int i = 0; i < NSUM; ++i) acc[i] += in[c * NSUM + i];
+      }
+#pragma unroll
+      for (int i = 0; i < NSUM; ++i) red[t][i] = acc[i];
+    }
+    __syncthreads();
+    if (t == 0) {
+      double r[NSUM];
+#pragma unroll
+      for (int i = 0; i < NSUM; ++i) r[i] = red[0][i];
+      for (int u = 1; u < runs; ++u) {
+#pragma unroll
+        for (int i = 0; i < NSUM; ++i) r[i] += red[u][i];
+      }
+      const double n = (double)a.per_sample, phi = (double)a.rescale;
+      double var_c = (r[1] - r[0] * r[0] / n) / (n - 1.0), var_g = (r[3] - r[2] * r[2] / n) / (n - 1.0);
+      var_c = var_c < 0.0 ? 0.0 : var_c;      // (rounding below zero of a constant row; a NaN stays)
+      var_g = var_g < 0.0 ? 0.0 : var_g;
+      g_s = (float)(phi * (sqrt(var_c) / sqrt(var_g)) + (1.0 - phi));
+    }
+    __syncthreads();
+    const float g = g_s;
+    const float* co = a.model_out + tl.off;
+    const float* un = a.uncond_out + tl.off;
+    float* out = a.out + tl.off;
+    const float w = a.w_per_sample ? a.w[tl.b] : a.w[0];
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i) {
+      const int e0 = (i * 256 + t) * 4;
+      float o[4], u[4], r[4];
+      const int cnt = load_slot(co + e0, tl.rem - e0, o);      // (out may alias an input: a thread reads its elements before it writes them)
+      load_slot(un + e0, tl.rem - e0, u);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[k] = guidance_combine(a.guidance_cfg, o[k], u[k], w) * g;
+      if (cnt == 4 && ((uintptr_t)(out + e0) & 15) == 0) {
+        *(f32x4*)(out + e0) = (f32x4){r[0], r[1], r[2], r[3]};
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { if (k < cnt) out[e0 + k] = r[k]; }
+      }
+    }
+    // (no barrier here: thread 0 writes g_s, and the others red, only after the next pair's first barrier / after its second one)
+  }
+}
+
+// chunks per sample, or 0 where the sizes are refused
+int64_t chunks_of(int64_t B, int64_t n) {
+  if (B < 1 || n < 2 || n >= (1ll << 62) / B) return 0;
+  const int64_t chunks = (n + CHUNK - 1) / CHUNK;
+  return chunks > ((1ll << 31) - 1) / B ? 0 : chunks;
+}
+
+}  // namespace
+}  // namespace pd
+
+using namespace pd;
+
+extern "C" size_t pd_guidance_rescale_workspace(int64_t B, int64_t n) {
+  return (size_t)(chunks_of(B, n) * (B > 0 ? B : 0)) * NSUM * sizeof(double);
+}
+
+extern "C" int pd_guidance_rescale(const pd_guidance_rescale_args* a, void* stream) {
+  const char* const who = "pd_guidance_rescale";
+  PD_CHECK(a != nullptr, PD_ERR_ARG, "%s: null args", who);
+  PD_CHECK(a->model_out != nullptr, PD_ERR_ARG, "%s: model_out is NULL", who);
+  PD_CHECK(a->uncond_out != nullptr, PD_ERR_ARG, "%s: uncond_out is NULL (the rescale is defined for a guided prediction only)", who);
+  PD_CHECK(a->w != nullptr, PD_ERR_ARG, "%s: guidance without weights (w is NULL)", who);
+  PD_CHECK(a->out != nullptr, PD_ERR_ARG, "%s: out is NULL", who);
+  PD_CHECK(a->workspace != nullptr, PD_ERR_ARG, "%s: null workspace (pd_guidance_rescale_workspace gives its size)", who);
+  PD_CHECK(a->rescale >= 0.0f && a->rescale <= 1.0f, PD_ERR_ARG, "%s: rescale = %g (must lie in [0, 1])", who, (double)a->rescale);
+  PD_CHECK(((uintptr_t)a->model_out % 16 == 0) && ((uintptr_t)a->uncond_out % 16 == 0) && ((uintptr_t)a->out % 16 == 0), PD_ERR_ARG,
+           "%s: tensors must be 16-byte aligned", who);
+  PD_CHECK((uintptr_t)a->w % 4 == 0, PD_ERR_ARG, "%s: w must be 4-byte aligned", who);
+  PD_CHECK((uintptr_t)a->workspace % 8 == 0, PD_ERR_ARG, "%s: workspace must be 8-byte aligned", who);
+  PD_CHECK(a->numel > 0, PD_ERR_SHAPE, "%s: numel = %lld (must be > 0)", who, (long long)a->numel);
+  PD_CHECK(a->per_sample >= 2, PD_ERR_SHAPE, "%s: per_sample = %lld (a standard deviation takes at least two elements)", who,
+           (long long)a->per_sample);
+  PD_CHECK(a->numel % a->per_sample == 0, PD_ERR_SHAPE, "%s: numel %lld is not a multiple of per_sample %lld", who, (long long)a->numel,
+           (long long)a->per_sample);
+  Launch p;
+  p.a = *a;
+  const int64_t B = a->numel / a->per_sample;
+  p.chunks = chunks_of(B, a->per_sample);
+  PD_CHECK(p.chunks > 0, PD_ERR_SHAPE, "%s: more than 2^31 - 1 chunks of %d elements: split the batch", who, CHUNK);
+  p.items = B * p.chunks;
+  p.part = (double*)a->workspace;
+  const unsigned grid = (unsigned)(p.items < MAX_BLOCKS ? p.items : MAX_BLOCKS);
+  hipLaunchKernelGGL(guidance_rescale_partial_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  PD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(guidance_rescale_apply_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(const pd_multistep_
       float out = o[j];
       if (a.uncond_out) {
         const float w = a.w_per_sample ? a.w[row] : a.w[0];
-        out = a.guidance_cfg ? (o[j] + w * (o[j] - u[j])) : (u[j] + w * (o[j] - u[j]));
+        out = guidance_combine(a.guidance_cfg, o[j], u[j], w);
       }
       float x0, eps;
       ddim_x0_eps(a, x[j], out, x0, eps);

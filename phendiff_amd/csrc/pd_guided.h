@@ -37,6 +37,15 @@ __device__ __forceinline__ float ddim_step_elem(const A& a, float x, float out, 
   return ddim_prev(a, x, x0, eps);
 }
 
+// The classifier-free guidance combine of a conditional (o) and an unconditional (u) prediction, both equations: the expression the
+// step kernels (ddim_step_kernel, threshold_kernels.hip, multistep_step_kernel) evaluate, a subtraction, a multiplication and an
+// addition each rounded on its own.  Both passes of pd_guidance_rescale go through it, so the cfg whose standard deviation is taken is
+// bit for bit the cfg that is rescaled -- and the cfg a step kernel would have formed of the same operands.
+__device__ __forceinline__ float guidance_combine(int guidance_cfg, float o, float u, float w) {
+#pragma clang fp contract(off)
+  return guidance_cfg ? (o + w * (o - u)) : (u + w * (o - u));
+}
+
 // images - guidance_loss_scale * guidance_grad (utils_Img2Img.py:747-751).  The sum rounds once, then ONE fused multiply-add: the form
 // the compiler gave guidance_apply_kernel's `x - s * (gd + gu)`, spelled out so that every caller gets it whatever surrounds the call.
 __device__ __forceinline__ float guidance_push(float x, float s, float g_direct, float g_unet) {

@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const pd_ddim_step_args 
     if (a.uncond_out) {
       // (lanes past numel in the tail vector take element i0's weight: (i0 + j) / per_sample would index one past w[B - 1])
       const float w = a.w_per_sample ? a.w[(i0 + (j < cnt ? j : 0)) / a.per_sample] : a.w[0];
-      out = a.guidance_cfg ? (o[j] + w * (o[j] - u[j])) : (u[j] + w * (o[j] - u[j]));
+      out = guidance_combine(a.guidance_cfg, o[j], u[j], w);
     }
     xp[j] = ddim_step_elem(a, x[j], out, x0v[j]);
   }

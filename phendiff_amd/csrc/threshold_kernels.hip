@@ -192,7 +192,7 @@ __device__ __forceinline__ ThresholdOperands threshold_operands(const pd_ddim_st
     r.out[j] = o[j];
     if (a.uncond_out) {
       const float w = a.w_per_sample ? a.w[r.b[j]] : a.w[0];
-      r.out[j] = a.guidance_cfg ? (o[j] + w * (o[j] - u[j])) : (u[j] + w * (o[j] - u[j]));
+      r.out[j] = guidance_combine(a.guidance_cfg, o[j], u[j], w);
     }
   }
   return r;

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .schedulers import check_guidance_rescale
 
 EVAL_SEED = 5742877512           # utils_training.py:698 ("observe the outputs produced from the same Gaussian noise")
 
@@ -131,7 +132,7 @@ def _filenames(local_process_index: int, eval_batch_size: int, batch_idx: int, n
 def generate_images_for_this_class_DDIM(pipeline, class_label: int, batch_sizes: Sequence[int], *, guidance_factor,
                                         num_inference_steps: int, generator, proba_uncond: float = 0.0,
                                         eval_batch_size: Optional[int] = None, local_process_index: int = 0,
-                                        class_name: str = "") -> Iterator[GeneratedBatch]:
+                                        class_name: str = "", guidance_rescale: float = 0.0) -> Iterator[GeneratedBatch]:
     """``_generate_save_images_for_this_class_DDIM`` (``utils_training.py:884-941``) minus the disk / W&B writes."""
     ebs = eval_batch_size if eval_batch_size is not None else (max(batch_sizes) if batch_sizes else 0)
     for batch_idx, bs in enumerate(batch_sizes):
@@ -140,7 +141,7 @@ def generate_images_for_this_class_DDIM(pipeline, class_label: int, batch_sizes:
         else:
             labels, emb = torch.full((bs,), class_label, device=pipeline.device).long(), None
         images = pipeline(labels, emb, guidance_factor, generator=generator, num_inference_steps=num_inference_steps,
-                          output_type="numpy").images
+                          output_type="numpy", guidance_rescale=guidance_rescale).images
         yield GeneratedBatch(class_label, class_name, batch_idx, _filenames(local_process_index, ebs, batch_idx, bs), images)
 
 
@@ -162,7 +163,7 @@ def generate_images_for_this_class_device(runners: dict, device_noise, class_lab
 def generate_images_for_this_class_SD(pipeline, class_label: int, batch_sizes: Sequence[int], *, guidance_factor,
                                       num_inference_steps: int, generator, latent_hw: Tuple[int, int] = (16, 16),
                                       eval_batch_size: Optional[int] = None, local_process_index: int = 0,
-                                      class_name: str = "") -> Iterator[GeneratedBatch]:
+                                      class_name: str = "", guidance_rescale: float = 0.0) -> Iterator[GeneratedBatch]:
     """``_generate_save_images_for_this_class_SD`` (``utils_training.py:806-881``): from-noise latents of the hard-coded
     ``(b, 4, 16, 16)`` shape (a keyword here), ``strength = 1``, ``output_type = "np+latent"``."""
     ebs = eval_batch_size if eval_batch_size is not None else (max(batch_sizes) if batch_sizes else 0)
@@ -171,7 +172,7 @@ def generate_images_for_this_class_SD(pipeline, class_label: int, batch_sizes: S
         images, latents = pipeline(image=None, latent_shape=(bs, 4, *latent_hw),
                                    class_labels=torch.tensor([class_label] * bs, device=dev).long(), strength=1,
                                    num_inference_steps=num_inference_steps, guidance_scale=guidance_factor,
-                                   generator=generator, output_type="np+latent", device=dev)
+                                   generator=generator, output_type="np+latent", device=dev, guidance_rescale=guidance_rescale)
         yield GeneratedBatch(class_label, class_name, batch_idx, _filenames(local_process_index, ebs, batch_idx, bs), images,
                              latents)
 
@@ -193,7 +194,7 @@ def generate_samples(pipeline, *, nb_classes: int, nb_generated_images: int, eva
                      process_index: int = 0, local_process_index: Optional[int] = None, generator=None,
                      latent_hw: Tuple[int, int] = (16, 16),
                      on_class_done: Optional[Callable[[int, str, List[GeneratedBatch]], None]] = None,
-                     device_noise=None, use_graph: bool = True) -> EvalGeneration:
+                     device_noise=None, use_graph: bool = True, guidance_rescale: float = 0.0) -> EvalGeneration:
     """Steps 2–5 of ``_generate_samples_and_compute_metrics`` (``utils_training.py:664-769``).  ``trainer`` (optional): swap
     its EMA weights in for the duration.  ``generator`` defaults to the reference's: a generator on the pipeline's device
     seeded with ``EVAL_SEED``, shared by all classes and batches (so class c's noise depends on the batches drawn before
@@ -203,9 +204,12 @@ def generate_samples(pipeline, *, nb_classes: int, nb_generated_images: int, eva
     runs as one :class:`~phendiff_amd.trajectories.GenerationGraph` per distinct batch size (``use_graph=False``: the same launches,
     eagerly); the batches carry ``images_u8_device``.  Image ``j`` of class ``c`` draws at global index ``c * nb_generated_images + j``
     on whatever process generates it (:func:`generation_indices`) -- give every process a ``DeviceNoise`` of the same seed and rank --
-    and ``generator`` is not used."""
+    and ``generator`` is not used.
+
+    ``guidance_rescale`` (both tiers, eager and captured; 0 = off): the pipelines' argument, passed on with ``guidance_factor``."""
     if model_type not in ("DDIM", "StableDiffusion"):
         raise ValueError(f"Unknown model type {model_type}")
+    check_guidance_rescale(guidance_rescale, "generate_samples")
     if device_noise is not None:
         if model_type != "DDIM":
             raise NotImplementedError("generate_samples(device_noise=...) runs model_type='DDIM' only: the latent tier has no captured "
@@ -234,19 +238,20 @@ def generate_samples(pipeline, *, nb_classes: int, nb_generated_images: int, eva
             if device_noise is not None:
                 from .trajectories import GenerationGraph
                 for bs in set(sizes) - set(runners):      # (built inside ema_weights: a runner captures the weights' pointers as they are)
-                    runners[bs] = GenerationGraph(pipeline, bs, num_inference_steps, device_noise, w=guidance_factor, use_graph=use_graph)
+                    runners[bs] = GenerationGraph(pipeline, bs, num_inference_steps, device_noise, w=guidance_factor, use_graph=use_graph,
+                                                  guidance_rescale=guidance_rescale)
                 it = generate_images_for_this_class_device(runners, device_noise, c, sizes, [k for cc, _, k in plan if cc == c],
                                                            eval_batch_size=eval_batch_size, local_process_index=lpi, class_name=name)
             elif model_type == "DDIM":
                 it = generate_images_for_this_class_DDIM(pipeline, c, sizes, guidance_factor=guidance_factor,
                                                          num_inference_steps=num_inference_steps, generator=generator,
                                                          proba_uncond=proba_uncond, eval_batch_size=eval_batch_size,
-                                                         local_process_index=lpi, class_name=name)
+                                                         local_process_index=lpi, class_name=name, guidance_rescale=guidance_rescale)
             else:
                 it = generate_images_for_this_class_SD(pipeline, c, sizes, guidance_factor=guidance_factor,
                                                        num_inference_steps=num_inference_steps, generator=generator,
                                                        latent_hw=latent_hw, eval_batch_size=eval_batch_size,
-                                                       local_process_index=lpi, class_name=name)
+                                                       local_process_index=lpi, class_name=name, guidance_rescale=guidance_rescale)
             got = list(it)
             out.batches += got
             if on_class_done is not None:

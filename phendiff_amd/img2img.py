@@ -24,7 +24,8 @@ import torch
 from . import _lib as L
 from .pipeline import ConditionalDDIMPipeline, require_pil_channels
 from .schedulers import (MULTISTEP_NOT_GUIDED, MULTISTEP_NOT_LATENT, MULTISTEP_NOT_TILED, THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT,
-                         DDIMInverseScheduler, inverse_scheduler, quantile_rank, refuse_multistep, refuse_thresholding)
+                         DDIMInverseScheduler, check_guidance_rescale, inverse_scheduler, quantile_rank, refuse_multistep,
+                         refuse_thresholding)
 
 
 @torch.no_grad()
@@ -274,19 +275,20 @@ def tiled_inverted_regeneration(pipe, clean_images, orig_class_labels, num_infer
 @torch.no_grad()
 def classifier_free_guidance_forward_start(pipe, clean_images, target_class_labels, guidance_scale: float,
                                            frac_diffusion_skipped: float, num_inference_steps: int, generator=None,
-                                           output_type: str = "numpy"):
+                                           output_type: str = "numpy", guidance_rescale: float = 0.0):
     """``_classifier_free_guidance_forward_start`` (utils_Img2Img.py:615-648), both pipeline branches: noise
     the image up to ``(1 - frac_diffusion_skipped)`` of the trajectory, then denoise under the target class with
-    classifier-free guidance."""
+    classifier-free guidance.  ``guidance_rescale``: the pipelines' argument (0 = off)."""
     from .sd_pipeline import CustomStableDiffusionImg2ImgPipeline
+    check_guidance_rescale(guidance_rescale, "classifier_free_guidance_forward_start")
     if isinstance(pipe, CustomStableDiffusionImg2ImgPipeline):       # :638-645: strength = frac_diffusion_skipped
         refuse_multistep(pipe.scheduler, "classifier_free_guidance_forward_start with a latent-diffusion pipeline", MULTISTEP_NOT_LATENT)
         return pipe(image=clean_images, class_labels=target_class_labels, strength=frac_diffusion_skipped,
                     num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, generator=generator,
-                    output_type={"numpy": "np"}.get(output_type, output_type))
+                    output_type={"numpy": "np"}.get(output_type, output_type), guidance_rescale=guidance_rescale)
     return pipe(class_labels=target_class_labels, w=guidance_scale, num_inference_steps=num_inference_steps,
                 start_image=clean_images, frac_diffusion_skipped=frac_diffusion_skipped, generator=generator,
-                output_type=output_type).images
+                output_type=output_type, guidance_rescale=guidance_rescale).images
 
 
 # fp16 engine: the factor the Lp loss gradient carries through the UNet backward (`custom_guided_generation`).  |d loss / d x0| of an

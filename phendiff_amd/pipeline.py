@@ -5,6 +5,10 @@ Differences that do not change results: the conditional and unconditional UNet p
 guidance feed one fused ``pd_ddim_step`` (guidance combine + scheduler update in one launch); the final
 ``(x/2+.5).clamp(0,1)`` + NCHW->NHWC is one ``pd_postproc`` launch before the single D2H copy.
 
+``guidance_rescale`` (diffusers' argument, arXiv 2305.08891 section 3.4; 0 = off): with guidance on, one ``pd_guidance_rescale`` per step
+forms the guidance combine brought back towards the conditional prediction's per-sample standard deviation, and the scheduler update
+takes it as the model output.
+
 ``generator=DeviceNoise`` (opt-in; not the reference's noise): the initial sample, the forward noise and the variance noise of the
 batch are drawn on the device, row ``b`` from the stream of image ``generator.index + b``, and the object moves on by the batch size.
 """
@@ -20,7 +24,8 @@ import torch
 
 from . import _lib as L
 from .noise import DeviceNoise
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, randn_tensor
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, check_guidance_rescale, randn_tensor
+from .schedulers import guidance_rescale as rescaled_guidance
 
 DEFAULT_NUM_INFERENCE_STEPS = 50
 
@@ -133,7 +138,8 @@ class ConditionalDDIMPipeline:
                  num_inference_steps: int = DEFAULT_NUM_INFERENCE_STEPS, use_clipped_model_output: Optional[bool] = None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, start_image: Optional[torch.Tensor] = None,
                  add_forward_noise_to_image: bool = True, frac_diffusion_skipped: Optional[float] = None,
-                 guidance_eqn: Literal["imagen", "CFG"] = "imagen") -> Union[ImagePipelineOutput, Tuple]:
+                 guidance_eqn: Literal["imagen", "CFG"] = "imagen", guidance_rescale: float = 0.0) -> Union[ImagePipelineOutput, Tuple]:
+        rescale = check_guidance_rescale(guidance_rescale, "ConditionalDDIMPipeline")      # (before anything is packed or launched)
         self.check_inputs(class_labels, class_emb, w, generator, frac_diffusion_skipped, start_image)
         require_pil_channels(self.unet.config.in_channels, output_type)
         if num_inference_steps is None:
@@ -180,6 +186,8 @@ class ConditionalDDIMPipeline:
                 if zeros_emb is None:
                     zeros_emb = torch.zeros((batch_size, self.unet.time_embed_dim), device=device)
                 uncond = self.unet(sample=image, timestep=t, class_labels=None, class_emb=zeros_emb).sample
+                if rescale > 0:      # diffusers' `if do_classifier_free_guidance and guidance_rescale > 0`: the step takes the rescaled combine
+                    cond, uncond = rescaled_guidance(cond, uncond, w, rescale, guidance_cfg=(guidance_eqn == "CFG")), None
             image, _ = self.scheduler._device_step(
                 cond, t, image, eta, bool(use_clipped_model_output), generator,
                 None, uncond_output=uncond, w=w, guidance_cfg=(guidance_eqn == "CFG"), want_x0=False)

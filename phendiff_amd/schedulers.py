@@ -19,6 +19,10 @@ named beta schedule in both.
 ``DDIMScheduler.step(..., eta > 0, generator=DeviceNoise)`` draws the variance noise on the device: one ``pd_stream_noise`` launch in
 place on ``prev_sample`` (after the thresholding, like the host-drawn term), from the stream of the step's position in ``timesteps``
 (:class:`~phendiff_amd.noise.DeviceNoise`).  A ``torch.Generator`` or an explicit ``variance_noise`` keeps the torch arithmetic.
+
+:class:`GuidanceRescale` / :func:`guidance_rescale` (diffusers' ``rescale_noise_cfg``): the classifier-free guidance combine brought back
+towards the conditional prediction's per-sample standard deviation, one ``pd_guidance_rescale`` BEFORE a step, which then takes the
+result as its model output -- no scheduler here knows about it.
 """
 from __future__ import annotations
 
@@ -121,6 +125,97 @@ def refuse_thresholding(scheduler, who: str, why: str) -> None:
     cfg = getattr(scheduler, "config", None)
     if cfg.get("thresholding", False) if isinstance(cfg, dict) else getattr(cfg, "thresholding", False):
         raise ValueError(f"{who} does not run a scheduler with thresholding=True: {why}")
+
+
+# ---- classifier-free guidance rescale (arXiv 2305.08891 section 3.4; diffusers' `guidance_rescale` / rescale_noise_cfg) -------------------
+# Under a zero-terminal-SNR schedule the guided prediction  cfg = u + w (c - u)  is over-scaled, which saturates the images.  The remedy
+# brings cfg back towards the conditional prediction's per-sample standard deviation:  out = cfg (phi std(c) / std(cfg) + 1 - phi).
+# ``pd_guidance_rescale`` does it in two launches (fp64 sums in a fixed order, a sample's result a function of that sample alone, no host
+# read); the scheduler step then runs on ``out`` without an unconditional prediction, so no step kernel knows about it.
+GUIDANCE_RESCALE_CHUNK = L.CONSTANTS["PD_GUIDANCE_RESCALE_CHUNK"]      # the elements one workgroup reduces: a sample has ceil(n / this) partials
+GUIDANCE_RESCALE_SCRATCH_SETS = 4      # workspaces kept for re-use, by last use
+_rescale_workspaces = {}               # (B, n, device, stream) -> workspace; launches on one stream are ordered, so they may share one
+
+
+def check_guidance_rescale(value, who: str) -> float:
+    """``guidance_rescale`` as a float in [0, 1], or a ``ValueError`` -- what every guided entry point says before it packs a weight or
+    launches anything."""
+    try:
+        phi = float(value)
+    except (TypeError, ValueError):
+        phi = math.nan
+    if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
+        raise ValueError(f"{who}: guidance_rescale must be a finite number in [0, 1], got {value!r}")
+    return phi
+
+
+def guidance_weights(w, device) -> torch.Tensor:
+    """The guidance weight(s) as the kernels read them: a dense fp32 (1,) or (B,) tensor on ``device``."""
+    return (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+
+
+class GuidanceRescale:
+    """The launch of one rescaled guidance combine (``pd_guidance_rescale``): the argument struct, the workspace it points at, and
+    :meth:`enqueue`.  ``cond`` / ``uncond``: dense fp32 (B, ...) tensors, the two predictions; ``w``: a dense fp32 (1,) or (B,) tensor on
+    their device; ``out``: where the rescaled guided prediction goes (default: ``cond`` itself -- in place, what the captured
+    trajectories do).  The workspace is one per (B, n, device, stream), made on first use and kept by order of last use
+    (:data:`GUIDANCE_RESCALE_SCRATCH_SETS` of them, 32 bytes per sample and chunk of :data:`GUIDANCE_RESCALE_CHUNK` elements): a capture
+    finds it allocated, and the object holds it, so whoever keeps the object (a runner's captured graph) keeps the memory it launches into."""
+
+    def __init__(self, cond: torch.Tensor, uncond: torch.Tensor, w: torch.Tensor, guidance_rescale: float, guidance_cfg: bool = False,
+                 out: torch.Tensor = None, stream: int = None):
+        phi = check_guidance_rescale(guidance_rescale, "GuidanceRescale")
+        out = cond if out is None else out
+        for name, t in (("cond", cond), ("uncond", uncond), ("out", out)):
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise L.PhenDiffHipError(f"GuidanceRescale: {name} must be a tensor on an MI355X (no CPU fallback)")
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(cond.shape):
+                raise ValueError(f"GuidanceRescale: {name} must be a dense fp32 tensor of cond's shape {tuple(cond.shape)}")
+        B, n = cond.shape[0], cond[0].numel()
+        if not (torch.is_tensor(w) and w.device == cond.device and w.dtype == torch.float32 and w.is_contiguous() and w.numel() in (1, B)):
+            raise ValueError(f"GuidanceRescale: w must be a dense fp32 tensor of 1 or {B} weights on {cond.device} (guidance_weights makes it)")
+        self.stream = int(stream if stream is not None else torch.cuda.current_stream(cond.device).cuda_stream)
+        self.cond, self.uncond, self.w, self.out = cond, uncond, w, out
+        self.workspace = self._workspace(B, n, cond.device, self.stream)
+        self.args = L.GuidanceRescaleArgs(numel=B * n, per_sample=n, model_out=cond.data_ptr(), uncond_out=uncond.data_ptr(),
+                                          w=w.data_ptr(), w_per_sample=int(w.numel() > 1), guidance_cfg=int(bool(guidance_cfg)), rescale=phi,
+                                          out=out.data_ptr(), workspace=self.workspace.data_ptr())
+
+    @staticmethod
+    def _workspace(B: int, n: int, device, stream: int) -> torch.Tensor:
+        key = (B, n, device, stream)
+        ws = _rescale_workspaces.pop(key, None)
+        if ws is None:
+            size = L.lib().pd_guidance_rescale_workspace(B, n)
+            if size == 0:
+                raise ValueError(f"guidance rescale: no per-sample standard deviation over a ({B}, {n}) batch (at least two elements a sample)")
+            ws = torch.empty((size // 8,), dtype=torch.float64, device=device)
+        _rescale_workspaces[key] = ws                           # (re-inserted: the dict's order is the order of last use)
+        while len(_rescale_workspaces) > GUIDANCE_RESCALE_SCRATCH_SETS:
+            del _rescale_workspaces[next(iter(_rescale_workspaces))]
+        return ws
+
+    def enqueue(self, st: int):
+        """The launch on ``st``, which must be the stream the object was built for (its workspace is that stream's own)."""
+        if int(st) != self.stream:
+            raise ValueError(f"GuidanceRescale built for stream {self.stream:#x} enqueued on stream {int(st):#x}")
+        L.check(L.lib().pd_guidance_rescale(C.byref(self.args), st), "pd_guidance_rescale")
+
+
+def guidance_rescale(cond, uncond, w, guidance_rescale: float, guidance_cfg: bool = False, out=None) -> torch.Tensor:
+    """The rescaled guided prediction of a conditional and an unconditional model output, a dense fp32 tensor (``out`` where given; it
+    may be ``cond``): ``cfg = uncond + w (cond - uncond)`` (``guidance_cfg``: ``cond + w (cond - uncond)``) times
+    ``guidance_rescale * std(cond) / std(cfg) + 1 - guidance_rescale`` per sample -- diffusers' ``rescale_noise_cfg``.  ``w``: a number
+    or a (B,) tensor.  One ``pd_guidance_rescale`` on the current stream; a scheduler's ``step`` then takes the result as the model
+    output.  ``guidance_rescale = 0`` returns the plain combine."""
+    phi = check_guidance_rescale(guidance_rescale, "guidance_rescale")
+    if not (torch.is_tensor(cond) and torch.is_tensor(uncond) and cond.is_cuda and uncond.is_cuda):
+        raise L.PhenDiffHipError("phendiff_amd.guidance_rescale runs on MI355X tensors only (no CPU fallback)")
+    c, u = cond.contiguous().float(), uncond.contiguous().float()
+    if out is None:
+        out = torch.empty_like(c)
+    GuidanceRescale(c, u, guidance_weights(w, c.device), phi, guidance_cfg, out).enqueue(torch.cuda.current_stream(c.device).cuda_stream)
+    return out
 
 
 MULTISTEP_NOT_TILED = "the tiled trajectories step DDIM on the canvas; the solver's history is not kept per canvas yet"

@@ -18,7 +18,9 @@ import torch
 
 from . import _lib as L
 from .pipeline import numpy_to_pil
-from .schedulers import MULTISTEP_NOT_LATENT, THRESHOLDING_NOT_LATENT, DDIMScheduler, randn_tensor, refuse_multistep, refuse_thresholding
+from .schedulers import (MULTISTEP_NOT_LATENT, THRESHOLDING_NOT_LATENT, DDIMScheduler, check_guidance_rescale, randn_tensor, refuse_multistep,
+                         refuse_thresholding)
+from .schedulers import guidance_rescale as rescaled_guidance
 from .vae import VaeImageProcessor
 
 DEFAULT_NUM_INFERENCE_STEPS = 50
@@ -228,7 +230,8 @@ class CustomStableDiffusionImg2ImgPipeline:
                  generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None,
                  class_labels_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
-                 cross_attention_kwargs: Optional[Dict[str, Any]] = None, device=None):
+                 cross_attention_kwargs: Optional[Dict[str, Any]] = None, device=None, guidance_rescale: float = 0.0):
+        rescale = check_guidance_rescale(guidance_rescale, type(self).__name__)      # (before anything is packed or launched)
         refuse_thresholding(self.scheduler, type(self).__name__, THRESHOLDING_NOT_LATENT)      # (a scheduler swapped in after construction)
         refuse_multistep(self.scheduler, type(self).__name__, MULTISTEP_NOT_LATENT)
         self.check_inputs(class_labels=class_labels, strength=strength, callback_steps=callback_steps,
@@ -270,9 +273,13 @@ class CustomStableDiffusionImg2ImgPipeline:
                 two[:B].copy_(latents)
                 two[B:].copy_(latents)
                 pred = self.unet(two, t, encoder_hidden_states=ehs, cross_attention_kwargs=cross_attention_kwargs, return_dict=False)[0]
-                # noise_pred_uncond + guidance_scale * (noise_pred_cond - noise_pred_uncond), fused into the scheduler update
-                latents, _ = self.scheduler._device_step(pred[B:], t, latents, extra.get("eta", 0.0) or 0.0, False, step_gen, None,
-                                                         uncond_output=pred[:B], w=guidance_scale, guidance_cfg=False, want_x0=False)
+                # noise_pred_uncond + guidance_scale * (noise_pred_cond - noise_pred_uncond), fused into the scheduler update -- or, with
+                # guidance_rescale > 0 (diffusers' rescale_noise_cfg), formed and rescaled by one pd_guidance_rescale before it
+                cond, uncond = pred[B:], pred[:B]
+                if rescale > 0:
+                    cond, uncond = rescaled_guidance(cond, uncond, guidance_scale, rescale), None
+                latents, _ = self.scheduler._device_step(cond, t, latents, extra.get("eta", 0.0) or 0.0, False, step_gen, None,
+                                                         uncond_output=uncond, w=guidance_scale, guidance_cfg=False, want_x0=False)
             else:
                 pred = self.unet(latents, t, encoder_hidden_states=ehs, cross_attention_kwargs=cross_attention_kwargs, return_dict=False)[0]
                 latents = self.scheduler.step(pred, t, latents, **extra, return_dict=False)[0]

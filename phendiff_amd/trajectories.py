@@ -30,7 +30,8 @@ from .img2img import GUIDANCE_MIN_GRAD_SCALE, _LpGuidance, _check_lp_exponent
 from .noise import DeviceNoise
 from .pipeline import ConditionalDDIMPipeline
 from .schedulers import (MULTISTEP_NOT_GUIDED, MULTISTEP_NOT_LATENT, THRESHOLDING_NOT_GUIDED, THRESHOLDING_NOT_LATENT,
-                         DPMSolverMultistepScheduler, ThresholdStep, inverse_scheduler, randn_tensor, refuse_multistep, refuse_thresholding)
+                         DPMSolverMultistepScheduler, GuidanceRescale, ThresholdStep, check_guidance_rescale, inverse_scheduler, randn_tensor,
+                         refuse_multistep, refuse_thresholding)
 
 
 def _identity_rows(cond: torch.Tensor, B: int, tdim: int, device) -> torch.Tensor:
@@ -312,17 +313,33 @@ class _PixelTrajectory(_TrajectoryRunner):
                                   self.stream.cuda_stream, uncond_out, w, guidance_cfg, first=(k == 0))
                 for k, t in enumerate(timesteps)]
 
-    def _ddim_steps(self, st, step_args, first: int = 0, uncond=None, variance=None):
+    def _guidance(self, do_cfg: bool, w, guidance_cfg: bool, rescale: float):
+        """How a guided runner's steps see the two evaluations: ``(uncond_out, w, rescale)`` for its step arguments and ``_ddim_steps``.
+        Without a rescale the update combines ``model_out`` and ``uncond[1]`` itself; with one (and guidance on) a
+        :class:`~phendiff_amd.schedulers.GuidanceRescale` -- one object for every step: the buffers are the same -- leaves the rescaled
+        combine in ``model_out`` and the update takes that alone."""
+        if not do_cfg:
+            return None, w, None
+        if not rescale > 0:
+            return self.uncond[1], w, None
+        return None, None, GuidanceRescale(self.model_out, self.uncond[1], w, rescale, guidance_cfg, out=self.model_out,
+                                           stream=self.stream.cuda_stream)
+
+    def _ddim_steps(self, st, step_args, first: int = 0, uncond=None, variance=None, rescale=None):
         """Per entry of ``step_args``: the UNet from ``x`` into ``model_out`` under row block ``first + i`` of ``temb``, then its
         ``pd_ddim_step`` (or the launches of its thresholded form, the ones the eager ``step`` enqueues; or, for an entry of
         :meth:`_solver_steps`, its ``pd_multistep_step``: the dispatch is on the argument's type).  ``uncond = (table, out)``: a
-        second evaluation under the same row block of another table before the update.  ``variance``: per entry the ``pd_stream_noise``
-        arguments of the step's variance term (stochastic DDIM), launched after the update."""
+        second evaluation under the same row block of another table before the update.  ``rescale``: the
+        :class:`~phendiff_amd.schedulers.GuidanceRescale` that turns the two evaluations into the rescaled guided prediction, in place in
+        ``model_out``, between them and the update.  ``variance``: per entry the ``pd_stream_noise`` arguments of the step's variance
+        term (stochastic DDIM), launched after the update."""
         step_bytes = self.rows_per_step * self.plan.w.proj_dim * 4
         for i, a in enumerate(step_args, first):
             self._unet(st, self.temb.data_ptr() + i * step_bytes, self.model_out.data_ptr())
             if uncond is not None:
                 self._unet(st, uncond[0].data_ptr() + i * step_bytes, uncond[1].data_ptr())
+            if rescale is not None:
+                rescale.enqueue(st)
             if isinstance(a, ThresholdStep):
                 a.enqueue(st)
             elif isinstance(a, L.MultistepStepArgs):
@@ -496,16 +513,18 @@ class CFGForwardStartGraph(_PixelTrajectory):
     """hipGraph form of the CFG forward-start transfer (utils_Img2Img.py:615-648 +
     pipeline_conditionial_ddim.py:248-347): ``add_noise`` to the first kept timestep, then per step a conditional
     and an unconditional UNet evaluation (``class_emb = 0``, pipeline :310-317) feeding ONE fused
-    guidance-combine + DDIM update; post-processing; all captured once and replayed per batch.
+    guidance-combine + DDIM update; post-processing; all captured once and replayed per batch.  ``guidance_rescale`` > 0 (with
+    guidance on): the combine, rescaled, is one ``pd_guidance_rescale`` in place on the conditional output before the update.
 
     ``run(clean_images, target_labels, noise)``: the forward noise is an input (the reference draws it from the
     caller's generator, ``randn_tensor``), so results are reproducible against the eager pipeline / the oracle."""
 
     def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, guidance_scale: float = 2.5,
                  frac_diffusion_skipped: float = 0.5, guidance_eqn: str = "imagen", height: int = None, width: int = None,
-                 device=None, use_graph: bool = True):
+                 device=None, use_graph: bool = True, guidance_rescale: float = 0.0):
         if guidance_eqn not in ("imagen", "CFG"):
             raise ValueError(f"Unknown guidance equation '{guidance_eqn}'; should be 'imagen' or 'CFG'")
+        phi = check_guidance_rescale(guidance_rescale, "CFGForwardStartGraph")
         super().__init__(pipe, batch_size, num_inference_steps, height, width, device, use_graph, keeps_input=True)
         B, dev = self.B, self.device
         sch = pipe.scheduler
@@ -525,11 +544,11 @@ class CFGForwardStartGraph(_PixelTrajectory):
         self.noise_args = L.AddNoiseArgs(numel=self.x.numel(), per_sample=self.x[0].numel(), velocity=0,
                                          x=self.clean.data_ptr(), noise=self.noise.data_ptr(), sa=sa.data_ptr(),
                                          sb=sb.data_ptr(), out=self.x.data_ptr())
+        uncond_out, w_step, self.rescale = self._guidance(do_cfg, self.w_dev, guidance_eqn == "CFG", phi)
         if self.multistep:
-            self.step_args = self._solver_steps(sch, self.ts, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
+            self.step_args = self._solver_steps(sch, self.ts, uncond_out, w_step, guidance_eqn == "CFG")
         else:
-            self.step_args = [self._forward_step_args(sch, t, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
-                              for t in self.ts]
+            self.step_args = [self._forward_step_args(sch, t, uncond_out, w_step, guidance_eqn == "CFG") for t in self.ts]
         self._capture()
 
     def _enqueue(self, st):
@@ -537,7 +556,7 @@ class CFGForwardStartGraph(_PixelTrajectory):
         if self.uncond is not None:
             self.plan.temb_rows(self.ts_rows, None, self.zero_emb, st, rows=self.ts_rows.numel(), out=self.uncond[0])
         L.check(self.lib.pd_add_noise(C.byref(self.noise_args), st), "pd_add_noise")
-        self._ddim_steps(st, self.step_args, uncond=self.uncond)
+        self._ddim_steps(st, self.step_args, uncond=self.uncond, rescale=self.rescale)
         self._postproc(st)
 
     def _fill(self, clean_images, target_class_labels, noise):
@@ -564,14 +583,17 @@ class GenerationGraph(_PixelTrajectory):
     ``run(class_labels=None, class_emb=None)`` returns the uint8 (B, H, W, C) images on the device (``.images_u8``); ``.images`` holds
     the float32 NHWC images in [0, 1] of the same ``pd_postproc`` launch.  Row ``b`` is image ``noise.index + b`` (the index before
     the run).  ``class_emb``: the (B, time_embed_dim) rows of a ``class_embed_type="identity"`` model.  ``w``: a number or a (B,)
-    tensor; whether guidance runs follows ``__call__``'s rule.  ``start_image`` / ``frac_diffusion_skipped`` are
+    tensor; whether guidance runs follows ``__call__``'s rule.  ``guidance_rescale`` > 0 with guidance on: one ``pd_guidance_rescale``
+    per step, in place on the conditional output between the two evaluations and the update, which then takes no unconditional output
+    (``__call__``'s launches).  ``start_image`` / ``frac_diffusion_skipped`` are
     :class:`CFGForwardStartGraph`'s job (its ``noise`` argument may come from ``DeviceNoise.randn``)."""
 
     def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, noise: DeviceNoise, w=None,
                  guidance_eqn: str = "imagen", eta: float = 0.0, use_clipped_model_output: bool = False, height: int = None,
-                 width: int = None, use_graph: bool = True):
+                 width: int = None, use_graph: bool = True, guidance_rescale: float = 0.0):
         if guidance_eqn not in ("imagen", "CFG"):
             raise ValueError(f"Unknown guidance equation '{guidance_eqn}'; should be 'imagen' or 'CFG'")
+        phi = check_guidance_rescale(guidance_rescale, "GenerationGraph")
         if not isinstance(noise, DeviceNoise):
             raise TypeError(f"GenerationGraph draws from a DeviceNoise, not from a {type(noise).__name__}")
         if torch.is_tensor(w) and (w.ndim != 1 or w.shape[0] != batch_size):
@@ -599,11 +621,12 @@ class GenerationGraph(_PixelTrajectory):
             self.w_dev = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
         per = x[0].numel()
         self.init_args = noise.launch_args(x, B, per, DeviceNoise.PURPOSE_INITIAL_SAMPLE)
+        uncond_out, w_step, self.rescale = self._guidance(do_cfg, self.w_dev, guidance_eqn == "CFG", phi)
         if self.multistep:
-            self.step_args = self._solver_steps(sch, self.ts, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG")
+            self.step_args = self._solver_steps(sch, self.ts, uncond_out, w_step, guidance_eqn == "CFG")
         else:
-            self.step_args = [self._forward_step_args(sch, t, self.uncond[1] if do_cfg else None, self.w_dev, guidance_eqn == "CFG",
-                                                      use_clipped_model_output, self.eta) for t in self.ts]
+            self.step_args = [self._forward_step_args(sch, t, uncond_out, w_step, guidance_eqn == "CFG", use_clipped_model_output, self.eta)
+                              for t in self.ts]
         self.var_args = None
         if self.eta > 0:
             self.var_args = [noise.variance_args(i, x, sch.step_coefficients(t, self.eta)[4]) for i, t in enumerate(self.ts)]
@@ -614,7 +637,7 @@ class GenerationGraph(_PixelTrajectory):
         if self.uncond is not None:
             self.plan.temb_rows(self.ts_rows, None, self.zero_emb, st, rows=self.ts_rows.numel(), out=self.uncond[0])
         L.check(self.lib.pd_stream_noise(C.byref(self.init_args), st), "pd_stream_noise")
-        self._ddim_steps(st, self.step_args, uncond=self.uncond, variance=self.var_args)
+        self._ddim_steps(st, self.step_args, uncond=self.uncond, variance=self.var_args, rescale=self.rescale)
         self._postproc(st)
         L.check(self.lib.pd_stream_advance(self.noise.state.data_ptr(), self.B, st), "pd_stream_advance")
 
