@@ -171,9 +171,39 @@ template <typename T> struct AttnOps {
   // scripts/micro/exp_variants.hip): truncation instead of round-to-nearest.  The row sum l is accumulated by the same MFMA from
   // the same truncated values (the ones row of A), so the -2^-9 mean bias divides out of O = (P V) / l; the random part has the
   // variance of round-to-nearest (one ulp wide either way).  8 of these per 32 x 32 tile: ~14 of its ~217 cycles.
+  // Round 26 priced the two other one-instruction forms (v_pack_b32_f16 with op_sel, v_mov_b32 SDWA in place): 4.47 / 4.45 against
+  // 4.54 SIMD cycles, no cheaper inside the exp mix, and v_pack_b32_f16 quiets signalling NaNs of the f16 view (docs/LAB_r26.md).
   static __device__ __forceinline__ uint32_t pack_p(float lo, float hi) {
     if constexpr (std::is_same<T, bf16_t>::value) return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
     else return Pack16<T>::pack(lo, hi);
+  }
+  // Four packs (one B operand of a PV MFMA) and three of the tile's exponentials as ONE hand-placed group, for the check-free body of
+  // the DMA-staged kernel (bf16): v_exp | 4 x v_perm | v_exp v_exp.  Same instructions and same bits as pack_p and
+  // __builtin_amdgcn_exp2f; what the group fixes is their ORDER, which the scheduler otherwise picks per sub-tile (round 26: -1.0 % in
+  // situ).  The hazard recogniser cannot look inside an asm statement, so the group is safe by its own shape: the exponential in front
+  // reads none of the packs' inputs (a v_exp result may not feed the very next vector instruction), and two more instructions
+  // stand between the last pack and whatever follows (a vector result needs two wait states before an MFMA reads it).  e0..e2 come
+  // back exponentiated.  TAIL (last sub-tile of a tile, nothing left to exponentiate): s_nop in their places.
+  template <bool TAIL>
+  static __device__ __forceinline__ u32x4 pack4(float p0, float p1, float p2, float p3, float p4, float p5, float p6, float p7,
+                                                float& e0, float& e1, float& e2) {
+    static_assert(std::is_same<T, bf16_t>::value, "the truncating pack is the bf16 engine's");
+    uint32_t b0, b1, b2, b3;
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f;      // results in registers of their own: an operand tied to one element of an MFMA result costs a copy
+#define PD_PACKS "v_perm_b32 %[b0], %[p1], %[p0], %[sel]\n\tv_perm_b32 %[b1], %[p3], %[p2], %[sel]\n\t" \
+                 "v_perm_b32 %[b2], %[p5], %[p4], %[sel]\n\tv_perm_b32 %[b3], %[p7], %[p6], %[sel]\n\t"
+    if constexpr (!TAIL) {
+      asm("v_exp_f32 %[r0], %[e0]\n\t" PD_PACKS "v_exp_f32 %[r1], %[e1]\n\tv_exp_f32 %[r2], %[e2]"
+          : [b0] "=&v"(b0), [b1] "=&v"(b1), [b2] "=&v"(b2), [b3] "=&v"(b3), [r0] "=&v"(r0), [r1] "=&v"(r1), [r2] "=&v"(r2)
+          : [p0] "v"(p0), [p1] "v"(p1), [p2] "v"(p2), [p3] "v"(p3), [p4] "v"(p4), [p5] "v"(p5), [p6] "v"(p6), [p7] "v"(p7), [e0] "v"(e0), [e1] "v"(e1), [e2] "v"(e2),
+            [sel] "s"(0x07060302u));
+      e0 = r0; e1 = r1; e2 = r2;
+    } else {
+      asm("s_nop 0\n\t" PD_PACKS "s_nop 1" : [b0] "=&v"(b0), [b1] "=&v"(b1), [b2] "=&v"(b2), [b3] "=&v"(b3)
+          : [p0] "v"(p0), [p1] "v"(p1), [p2] "v"(p2), [p3] "v"(p3), [p4] "v"(p4), [p5] "v"(p5), [p6] "v"(p6), [p7] "v"(p7), [sel] "s"(0x07060302u));
+    }
+#undef PD_PACKS
+    return u32x4{b0, b1, b2, b3};
   }
   // O^T += A . P^T for one 32-key sub-tile; p = exponentiated tile (fp32 accumulator layout)
   static __device__ __forceinline__ f32x16 pv(const VF& a, const f32x16& p, f32x16 o) {
@@ -467,6 +497,8 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
 //     16-lane group supplies key row q, d columns 4p..4p+3 (p < 2) or a block of ones (p >= 2: A rows 8..15 -> l),
 //   * the score bound uses the producer's max |k|^2 per (batch, head) instead of per-tile norms: once
 //     |q| * max|k| - m <= THR every later tile runs the check-free body with no LDS read in front of it.
+//   * bf16 (round 26, docs/LAB_r26.md; no bit moves): the check-free tiles run in a loop of their own, the constant k-slots are a whole
+//     tile of identical rows, and the exponentials and packs of a sub-tile are issued as two hand-placed groups (AttnOps::pack4).
 constexpr int ATTN_DMA_KT = 256;                                                      // keys per LDS tile (one barrier per tile)
 template <typename T>
 __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
@@ -475,10 +507,16 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
   constexpr int KT = ATTN_DMA_KT;
   constexpr int KROW = 16, TILE = KT * KROW;
   // one LDS array, addressed by byte offsets (plain integers keep every access a ds_* instruction):
-  //   K tiles [2][TILE] | V tiles [2][TILE] | constants [ONES] ([1 0 0 0 | 0 0 0 0] per 16 bytes, see voff below) | k-slots 8..15 of every K row (16 B)
+  //   K tiles [2][TILE] | V tiles [2][TILE] | constants [ONES] ([1 0 0 0 | 0 0 0 0] per 16 bytes, see voff below) | k-slots 8..15 of every K row (16 B; bf16: TILE bytes of them)
   constexpr int ONES = TILE + 256;                     // the ones lanes read up to 128 + 8 bytes past a tile-sized block
   constexpr int K_OFF = 0, V_OFF = 2 * TILE, ONES_OFF = 4 * TILE, KCONST_OFF = 4 * TILE + ONES;
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[4 * TILE + ONES + 16];
+  // round 26, bf16 engine only (the fp16 instantiation keeps the code it had): bit-identical re-schedulings of the check-free tiles
+  constexpr bool BF = std::is_same<T, bf16_t>::value;
+  constexpr bool HAND = BF, KC = BF, LOOPS = BF;
+  // KC: the constant k-slots as a whole tile of identical rows, so that the lanes of both halves step through their K fragments with
+  // the SAME stride -- every fragment address of a tile is one register plus an instruction offset, no per-sub-tile address add
+  constexpr int KCONST_BYTES = KC ? TILE : 16;
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[4 * TILE + ONES + KCONST_BYTES];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -505,7 +543,7 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
   float m = 0.f;
 
   // constant LDS content
-  if (tid == 0) Ops::init_const_slot(lds + KCONST_OFF);
+  if (KC ? tid < KT : tid == 0) Ops::init_const_slot(lds + KCONST_OFF + (KC ? tid * KROW : 0));
   for (int i16 = tid; i16 < ONES / 16; i16 += 512) {     // every 16 bytes: [1 0 0 0 | 0 0 0 0]
     T one8[8];
 #pragma unroll
@@ -513,8 +551,8 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
     *(s16x8*)(lds + ONES_OFF + i16 * 16) = *(const s16x8*)one8;
   }
   // K fragment offset in buffer 0: h == 0 -> row r of the sub-tile; h == 1 -> the constant slot (every sub-tile, both buffers)
-  const int koff = h ? KCONST_OFF : K_OFF + r * KROW;
-  const int kst = h ? 0 : 32 * KROW, kbuf = h ? 0 : TILE;
+  const int koff = (h ? KCONST_OFF : K_OFF) + ((KC || !h) ? r * KROW : 0);
+  const int kst = (KC || !h) ? 32 * KROW : 0, kbuf = h ? 0 : TILE;
   // V^T fragment offsets (transposed read; EXEC is all ones wherever they are used).  Key-row lanes sit on banks
   // 16h + 32j .. +15, the ones lanes on 16h + 16 + 32j ..: no conflict inside a 32-lane half; lanes 16..31 of each half repeat
   // lanes 0..15 (A rows 16..31 are never read back)
@@ -576,18 +614,19 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
     // this wave keeps the exact running-maximum path for the whole launch (no unbounded 2^(s - m); costs speed, not results)
     if (tmax > qk_bound) qk_bound = INFINITY;
   }
-  for (int k0 = 0, cur = 0; k0 < N; k0 += KT, cur ^= 1) {
-    if (k0 + KT < N) stage(cur ^ 1, k0 + KT);      // buffer cur^1 was last read before the barrier that ended the previous tile
+  // check-free body, software-pipelined as in attn_kernel
+  auto fast_tile = [&](int cur) {
     const int kl = koff + cur * kbuf;
     const int vb = voff + cur * vbuf;
-    const bool full_tile = k0 + KT <= N;
-    const bool need = qk_bound - m > RESCALE_THR;
-    if (full_tile && !__builtin_amdgcn_ballot_w64(need)) {
-      // check-free body, software-pipelined as in attn_kernel
+    {
       typename Ops::KF kfn = Ops::load_k(lds + kl);
       typename Ops::VF vfn = load_v(vb, 0);
       f32x16 sn = Ops::qk(kfn, qf, zero);
       kfn = Ops::load_k(lds + kl + kst);
+      if constexpr (HAND) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) sn[i] = __builtin_amdgcn_exp2f(sn[i]);
+      }
 #pragma unroll
       for (int sub = 0; sub < KT / 32; ++sub) {
         const typename Ops::VF vf = vfn;
@@ -598,11 +637,40 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
           vfn = load_v(vb, sub + 1);
           __builtin_amdgcn_sched_barrier(0);
         }
+        if constexpr (HAND) {
+          // registers 0..2 were exponentiated by the previous sub-tile's second pack group (the first sub-tile's: above)
+          float e[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = __builtin_amdgcn_exp2f(s[i]);
-        o = Ops::pv(vf, s, o);
+          for (int i = 0; i < 16; ++i) e[i] = s[i];
+#pragma unroll
+          for (int i = 3; i < 8; ++i) e[i] = __builtin_amdgcn_exp2f(e[i]);
+          const u32x4 b0 = Ops::template pack4<false>(e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8], e[9], e[10]);
+          o = Elem<T>::mma16(__builtin_bit_cast(s16x8, vf.v[0]), __builtin_bit_cast(s16x8, b0), o);
+#pragma unroll
+          for (int i = 11; i < 16; ++i) e[i] = __builtin_amdgcn_exp2f(e[i]);
+          u32x4 b1;
+          if (sub + 1 < KT / 32) {
+            float n0 = sn[0], n1 = sn[1], n2 = sn[2];
+            b1 = Ops::template pack4<false>(e[8], e[9], e[10], e[11], e[12], e[13], e[14], e[15], n0, n1, n2);
+            sn[0] = n0; sn[1] = n1; sn[2] = n2;
+          } else {
+            float n0 = 0.f, n1 = 0.f, n2 = 0.f;
+            b1 = Ops::template pack4<true>(e[8], e[9], e[10], e[11], e[12], e[13], e[14], e[15], n0, n1, n2);
+          }
+          o = Elem<T>::mma16(__builtin_bit_cast(s16x8, vf.v[1]), __builtin_bit_cast(s16x8, b1), o);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) s[i] = __builtin_amdgcn_exp2f(s[i]);
+          o = Ops::pv(vf, s, o);
+        }
       }
-    } else {
+    }
+  };
+  // exact running-maximum path: ragged tiles, and full ones while the bound still allows a score above m + THR
+  auto exact_tile = [&](int k0, int cur) {
+    const int kl = koff + cur * kbuf;
+    const int vb = voff + cur * vbuf;
+    {
 #pragma unroll 1
       for (int sub = 0; sub < KT / 32; ++sub) {
         const int kb = sub * 32;
@@ -638,8 +706,33 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
         o = Ops::pv(vf, s, o);
       }
     }
+  };
+  auto begin_tile = [&](int k0, int cur) {
+    if (k0 + KT < N) stage(cur ^ 1, k0 + KT);      // buffer cur^1 was last read before the barrier that ended the previous tile
+  };
+  auto end_tile = [&]() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA piece of the next tile has landed ...
     __syncthreads();                                   // ... and so has everybody's; nobody still reads buffer `cur`
+  };
+  // wave-uniform: may this tile run the check-free body?
+  auto fast_ok = [&](int k0) { return k0 + KT <= N && !__builtin_amdgcn_ballot_w64(qk_bound - m > RESCALE_THR); };
+  if constexpr (LOOPS) {
+    // The same tiles on the same paths as the single loop below, as three loops.  m and qk_bound change in exact tiles only, so once a
+    // full tile may run check-free every later full tile may too: the check-free tiles are ONE run, and in a loop of their own the
+    // accumulator o is loop-carried through one body only and stays in the registers the MFMAs accumulate in (in the single loop the
+    // register allocator merges the two paths with 8 v_mov_b64 and a 9-cycle wait behind every check-free tile).  Every wave passes
+    // ceil(N / KT) barriers whichever loops its tiles fall in.
+    int k0 = 0, cur = 0;
+    for (; k0 < N && !fast_ok(k0); k0 += KT, cur ^= 1) { begin_tile(k0, cur); exact_tile(k0, cur); end_tile(); }
+    for (; k0 + KT <= N; k0 += KT, cur ^= 1) { begin_tile(k0, cur); fast_tile(cur); end_tile(); }
+    for (; k0 < N; k0 += KT, cur ^= 1) { begin_tile(k0, cur); exact_tile(k0, cur); end_tile(); }
+  } else {
+    for (int k0 = 0, cur = 0; k0 < N; k0 += KT, cur ^= 1) {
+      begin_tile(k0, cur);
+      if (fast_ok(k0)) fast_tile(cur);
+      else exact_tile(k0, cur);
+      end_tile();
+    }
   }
 
   if (query < N) {
