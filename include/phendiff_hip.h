@@ -262,6 +262,8 @@ size_t pd_attn_d8_bwd_workspace(const pd_attn_bwd_args* a);
  * The host passes the four coefficients (computed in fp32 exactly as the reference's 0-dim tensors).
  * Optional classifier-free-guidance combine (pipeline_conditionial_ddim.py:324-328):
  *   out = uncond + w*(out - uncond)  [imagen]   or   out + w*(out - uncond)  [CFG]
+ * Refused before any launch (PD_ERR_ARG): null args / sample / model_out / prev_sample, numel < 1, per_sample < 1 or not a divisor of
+ * numel (the kernel divides by it), a prediction type outside the three, guidance without weights, tensors that are not 16-byte aligned.
  */
 typedef struct {
   int64_t numel;            /* B*C*H*W */

@@ -1,7 +1,7 @@
 // pd_guidance_rescale: classifier-free guidance with the guided prediction brought back towards the conditional prediction's per-sample
 // standard deviation (arXiv 2305.08891 section 3.4; diffusers' rescale_noise_cfg), on dense fp32 [B][n] tensors.  Contract:
 // include/phendiff_hip.h.  Host side: phendiff_amd.schedulers.GuidanceRescale.
-//     cfg = guidance_combine(cond, uncond, w)   (pd_guided.h: the step kernels' expression)
+//     cfg = guidance_combine(cond, uncond, w)   (pd_step.h: the step kernels' expression; load_slot is there too)
 //     g_b = phi * std(cond_b) / std(cfg_b) + (1 - phi)   (fp64, rounded to fp32 once)          out = cfg * g_b
 //
 // Two launches on one stream, no host synchronisation, the same tiling in both: a sample is cut into chunks of
@@ -16,7 +16,7 @@
 // Which element a lane takes depends only on the element's index WITHIN ITS SAMPLE, never on the address: the 16-byte access is used
 // where four elements lie whole inside the sample at an aligned address, element accesses everywhere else, and both hand the same values
 // to the same lane.  So a sample's g does not depend on B, on its row in the batch, on its alignment, on the grid or on the replay.
-#include "pd_guided.h"
+#include "pd_step.h"
 
 namespace pd {
 namespace {
@@ -30,19 +30,6 @@ struct Launch {
   int64_t chunks, items;     // chunks per sample; items = B * chunks
   double* part;              // [B][chunks][NSUM]
 };
-
-// the first min(cnt, 4) elements at p (cnt <= 0: nothing is read); returns how many are valid
-__device__ __forceinline__ int load_slot(const float* p, int cnt, float (&v)[4]) {
-  if (cnt >= 4 && ((uintptr_t)p & 15) == 0) {
-    const f32x4 q = *(const f32x4*)p;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = q[k];
-    return 4;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = k < cnt ? p[k] : 0.f;
-  return cnt < 0 ? 0 : (cnt < 4 ? cnt : 4);
-}
 
 // where (sample, chunk) pair `item` lies: the row, the offset of the chunk's first element in the tensor, its number of elements
 struct Tile { int64_t b, off; int rem; };

@@ -4,8 +4,8 @@
 //                           between replays without touching the captured launch)
 //   pd_guided_step        : un-scale + finiteness test + `images - guidance_loss_scale * grad` + DDIMScheduler.step in ONE elementwise
 //                           launch (was: mul_, isfinite().all() read on the host, pd_guidance_apply, pd_ddim_step)
-// Both reuse the per-element arithmetic of the launches they replace (pd_guided.h): the results are those launches', bit for bit.
-#include "pd_common.h"
+// Both reuse the per-element arithmetic of the launches they replace (guidance_push and the lp_* bodies of pd_guided.h; ddim_step_elem of
+// pd_step.h): the results are those launches', bit for bit.
 #include "pd_guided.h"
 
 namespace pd {
@@ -24,7 +24,9 @@ __global__ __launch_bounds__(256) void guided_step_kernel(const pd_guided_step_a
   const int64_t stride = (int64_t)gridDim.x * 1024;
   bool bad = false;
   for (int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i0 < a.numel; i0 += stride) {
-    const int cnt = (int)min((int64_t)4, a.numel - i0);
+    // Four input streams under ONE cnt == 4 branch, two outputs under another: this kernel keeps its own loop shape.  On load_quad /
+    // store_quad (pd_step.h: a branch per stream, the same accesses) it measured 3.6 % slower per launch (docs/LAB_r27.md).
+    const int cnt = quad_count(a.numel, i0);
     float x[4], o[4], gd[4], gu[4], xp[4], ps[4];
     if (cnt == 4) {
       const f32x4 vx = *(const f32x4*)(a.sample + i0), vo = *(const f32x4*)(a.model_out + i0);
@@ -73,19 +75,14 @@ extern "C" int pd_lp_guidance_scaled(const pd_lp_guidance_args* a, const float* 
 }
 
 extern "C" int pd_guided_step(const pd_guided_step_args* a, void* stream) {
-  PD_CHECK(a != nullptr, PD_ERR_ARG, "pd_guided_step: null args");
-  PD_CHECK(a->numel > 0, PD_ERR_ARG, "pd_guided_step: numel = %lld (must be > 0)", (long long)a->numel);
-  PD_CHECK(a->per_sample > 0 && a->numel % a->per_sample == 0, PD_ERR_ARG, "pd_guided_step: numel %lld is not a multiple of per_sample %lld",
-           (long long)a->numel, (long long)a->per_sample);
-  PD_CHECK(a->pred_type >= 0 && a->pred_type <= 2, PD_ERR_ARG, "pd_guided_step: bad prediction type %d", a->pred_type);
-  const void* const ptrs[] = {a->sample, a->g_direct, a->g_unet, a->model_out, a->prev_sample, a->pushed};
-  const char* const names[] = {"sample", "g_direct", "g_unet", "model_out", "prev_sample", "pushed"};
-  for (int i = 0; i < 6; ++i) {
-    PD_CHECK(ptrs[i] != nullptr || i == 5, PD_ERR_ARG, "pd_guided_step: %s is NULL", names[i]);
-    // every tensor goes through f32x4 loads / stores (NULL `pushed` passes: 0 % 16 == 0)
-    PD_CHECK((uintptr_t)ptrs[i] % 16 == 0, PD_ERR_ARG, "pd_guided_step: %s must be 16-byte aligned", names[i]);
-  }
-  PD_CHECK((uintptr_t)a->grad_scale % 4 == 0 && (uintptr_t)a->overflow % 4 == 0, PD_ERR_ARG, "pd_guided_step: grad_scale / overflow must be 4-byte aligned");
+  const char* const who = "pd_guided_step";
+  PD_CHECK(a != nullptr, PD_ERR_ARG, "%s: null args", who);
+  if (const int rc = step_validate_common(a->numel, a->per_sample, a->pred_type, who, PD_ERR_ARG)) return rc;
+  const NamedPtr tensors[] = {{"sample", a->sample}, {"g_direct", a->g_direct}, {"g_unet", a->g_unet}, {"model_out", a->model_out},
+                              {"prev_sample", a->prev_sample}, {"pushed", a->pushed}};
+  for (int i = 0; i < 5; ++i) PD_CHECK(tensors[i].p != nullptr, PD_ERR_ARG, "%s: %s is NULL", who, tensors[i].name);      // pushed: optional
+  if (const int rc = step_check_aligned16(tensors, who)) return rc;
+  PD_CHECK((uintptr_t)a->grad_scale % 4 == 0 && (uintptr_t)a->overflow % 4 == 0, PD_ERR_ARG, "%s: grad_scale / overflow must be 4-byte aligned", who);
   const int64_t blocks = (a->numel + 1023) / 1024;
   const unsigned grid = (unsigned)(blocks < GUIDED_MAX_BLOCKS ? blocks : GUIDED_MAX_BLOCKS);
   hipLaunchKernelGGL(guided_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);

@@ -1,50 +1,13 @@
-// Per-element arithmetic the scheduler update and the gradient-guided transfer share between translation units:
-//   ddim_step_elem  : DDIM(Inverse)Scheduler.step for one element        (ddim_step_kernel, guided_step_kernel)
+// Per-element arithmetic the gradient-guided transfer shares between translation units:
 //   guidance_push   : x - scale * (g_direct + g_unet)                    (guidance_apply_kernel, guided_step_kernel)
 //   lp_x0, lp_reduce_body, lp_grad_body : the two passes of pd_lp_guidance (train_kernels.hip) and of pd_lp_guidance_scaled
 //                                                                        (guided_kernels.hip)
-// One definition each, so a fused kernel rounds exactly like the launches it replaces.
+// One definition each, so a fused kernel rounds exactly like the launches it replaces.  The scheduler update itself (ddim_step_elem and
+// its halves, guidance_combine, the quad walker) lives in pd_step.h, included here.
 #pragma once
-#include "pd_common.h"
+#include "pd_step.h"
 
 namespace pd {
-
-// FP contraction is OFF here: the reference evaluates these formulas as separate fp32 mul / sub / div torch ops,
-// and epsilon-prediction divides by sqrt(alpha_bar) ~ 1e-5 near t = N, which amplifies a fused-vs-separate rounding
-// difference of the numerator by 1e5.  With contraction off every op is the same IEEE operation the CPU performs.
-// `A`: pd_ddim_step_args or pd_guided_step_args (the same eight fields).  Returns prev_sample; `x0` = pred_original_sample.
-// The update in its two halves, around whatever limits x0 (the static clamp below; the dynamic threshold of threshold_kernels.hip, whose
-// struct carries the same fields less clip / clip_range): the unclamped x0 with the predicted noise, and prev_sample from a limited x0.
-template <typename A>
-__device__ __forceinline__ void ddim_x0_eps(const A& a, float x, float out, float& x0, float& eps) {
-#pragma clang fp contract(off)
-  if (a.pred_type == PD_PRED_EPSILON) { x0 = (x - a.sqrt_b * out) / a.sqrt_a; eps = out; }
-  else if (a.pred_type == PD_PRED_SAMPLE) { x0 = out; eps = (x - a.sqrt_a * x0) / a.sqrt_b; }
-  else { x0 = a.sqrt_a * x - a.sqrt_b * out; eps = a.sqrt_a * out + a.sqrt_b * x; }
-}
-template <typename A>
-__device__ __forceinline__ float ddim_prev(const A& a, float x, float x0, float eps) {
-#pragma clang fp contract(off)
-  if (a.use_clipped_model_output) eps = (x - a.sqrt_a * x0) / a.sqrt_b;
-  return a.sqrt_ap * x0 + a.dir_coef * eps;
-}
-template <typename A>
-__device__ __forceinline__ float ddim_step_elem(const A& a, float x, float out, float& x0) {
-#pragma clang fp contract(off)
-  float eps;
-  ddim_x0_eps(a, x, out, x0, eps);
-  if (a.clip) x0 = fminf(fmaxf(x0, -a.clip_range), a.clip_range);
-  return ddim_prev(a, x, x0, eps);
-}
-
-// The classifier-free guidance combine of a conditional (o) and an unconditional (u) prediction, both equations: the expression the
-// step kernels (ddim_step_kernel, threshold_kernels.hip, multistep_step_kernel) evaluate, a subtraction, a multiplication and an
-// addition each rounded on its own.  Both passes of pd_guidance_rescale go through it, so the cfg whose standard deviation is taken is
-// bit for bit the cfg that is rescaled -- and the cfg a step kernel would have formed of the same operands.
-__device__ __forceinline__ float guidance_combine(int guidance_cfg, float o, float u, float w) {
-#pragma clang fp contract(off)
-  return guidance_cfg ? (o + w * (o - u)) : (u + w * (o - u));
-}
 
 // images - guidance_loss_scale * guidance_grad (utils_Img2Img.py:747-751).  The sum rounds once, then ONE fused multiply-add: the form
 // the compiler gave guidance_apply_kernel's `x - s * (gd + gu)`, spelled out so that every caller gets it whatever surrounds the call.

@@ -12,52 +12,12 @@
 // load is used where a slot of VEC elements lies whole inside the sample and is 16-byte aligned, element loads everywhere else, and both
 // deliver the same values to the same lane.  So a sample's results do not depend on B, on its row in the batch or on its alignment.  The
 // histogram uses integer atomics only (LDS, then one global add per non-empty bin and workgroup): order-independent.  No float atomics.
-#include "pd_common.h"
+#include "pd_step.h"      // Slot, load_slot
 
 namespace pd {
 namespace {
 
 constexpr int CHUNK = PD_SAMPLE_STATS_CHUNK, MAX_BINS = PD_SAMPLE_STATS_MAX_BINS, F = PD_SAMPLE_STATS_FIELDS;
-
-// ---- a slot = 16 bytes of elements
-template <typename T> struct Slot;
-template <> struct Slot<float> {
-  static constexpr int VEC = 4;
-  static __device__ __forceinline__ void load16(const float* p, float (&v)[4]) {
-    const f32x4 q = *(const f32x4*)p;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = q[k];
-  }
-};
-template <> struct Slot<bf16_t> {
-  static constexpr int VEC = 8;
-  static __device__ __forceinline__ void load16(const bf16_t* p, float (&v)[8]) {
-    const s16x8 q = *(const s16x8*)p;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = bf2f((bf16_t)q[k]);
-  }
-};
-template <> struct Slot<half_t> {
-  static constexpr int VEC = 8;
-  static __device__ __forceinline__ void load16(const half_t* p, float (&v)[8]) {
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    const h8 q = *(const h8*)p;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = (float)q[k];
-  }
-};
-
-// the first min(cnt, VEC) elements at p (cnt <= 0: nothing is read); returns how many are valid
-template <typename T> __device__ __forceinline__ int load_slot(const T* p, int cnt, float (&v)[Slot<T>::VEC]) {
-  constexpr int VEC = Slot<T>::VEC;
-  if (cnt >= VEC && ((uintptr_t)p & 15) == 0) {
-    Slot<T>::load16(p, v);
-    return VEC;
-  }
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) v[k] = k < cnt ? Elem<T>::to_f(p[k]) : 0.f;
-  return cnt < 0 ? 0 : (cnt < VEC ? cnt : VEC);
-}
 
 // ---- the two sets of per-chunk partials and how each member combines
 enum { OP_ADD, OP_MIN, OP_MAX };

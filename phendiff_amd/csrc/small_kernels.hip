@@ -3,7 +3,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include "pd_common.h"
-#include "pd_guided.h"
+#include "pd_step.h"
 
 namespace pd {
 
@@ -341,40 +341,17 @@ __global__ __launch_bounds__(1024) void gn_finalize3_kernel(const pd_gn_finalize
 // ================================================================================================
 // pd_ddim_step / pd_add_noise / pd_postproc: elementwise on fp32 NCHW
 // ================================================================================================
-// FP contraction is OFF in ddim_step_kernel and add_noise_kernel (ddim_step_elem, pd_guided.h, says why).
+// FP contraction is OFF in ddim_step_kernel and add_noise_kernel (pd_step.h says why).  One pass: 256 threads x 4 elements.
 __global__ __launch_bounds__(256) void ddim_step_kernel(const pd_ddim_step_args a) {
 #pragma clang fp contract(off)
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i0 >= a.numel) return;
-  const int cnt = (int)min((int64_t)4, a.numel - i0);
-  float x[4], o[4], u[4], xp[4], x0v[4];
-  if (cnt == 4) {
-    f32x4 vx = *(const f32x4*)(a.sample + i0), vo = *(const f32x4*)(a.model_out + i0);
+  const StepOperands r = step_operands(a, i0);
+  float xp[4], x0v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { x[j] = vx[j]; o[j] = vo[j]; }
-    if (a.uncond_out) { f32x4 vu = *(const f32x4*)(a.uncond_out + i0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) u[j] = vu[j]; }
-  } else {
-    for (int j = 0; j < 4; ++j) { x[j] = j < cnt ? a.sample[i0 + j] : 0.f; o[j] = j < cnt ? a.model_out[i0 + j] : 0.f;
-      u[j] = (a.uncond_out && j < cnt) ? a.uncond_out[i0 + j] : 0.f; }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float out = o[j];
-    if (a.uncond_out) {
-      // (lanes past numel in the tail vector take element i0's weight: (i0 + j) / per_sample would index one past w[B - 1])
-      const float w = a.w_per_sample ? a.w[(i0 + (j < cnt ? j : 0)) / a.per_sample] : a.w[0];
-      out = guidance_combine(a.guidance_cfg, o[j], u[j], w);
-    }
-    xp[j] = ddim_step_elem(a, x[j], out, x0v[j]);
-  }
-  if (cnt == 4) {
-    *(f32x4*)(a.prev_sample + i0) = (f32x4){xp[0], xp[1], xp[2], xp[3]};
-    if (a.pred_x0) *(f32x4*)(a.pred_x0 + i0) = (f32x4){x0v[0], x0v[1], x0v[2], x0v[3]};
-  } else {
-    for (int j = 0; j < cnt; ++j) { a.prev_sample[i0 + j] = xp[j]; if (a.pred_x0) a.pred_x0[i0 + j] = x0v[j]; }
-  }
+  for (int j = 0; j < 4; ++j) xp[j] = ddim_step_elem(a, r.x[j], r.out[j], x0v[j]);
+  store_quad(a.prev_sample, i0, r.cnt, xp);
+  if (a.pred_x0) store_quad(a.pred_x0, i0, r.cnt, x0v);
 }
 
 __global__ __launch_bounds__(256) void add_noise_kernel(const pd_add_noise_args a) {
@@ -488,14 +465,13 @@ extern "C" int pd_gn_finalize(const pd_gn_finalize_args* a, void* stream) {
 }
 
 extern "C" int pd_ddim_step(const pd_ddim_step_args* a, void* stream) {
-  PD_CHECK(a != nullptr, PD_ERR_ARG, "pd_ddim_step: null args");
-  PD_CHECK(a->numel > 0 && a->sample && a->model_out && a->prev_sample, PD_ERR_ARG, "pd_ddim_step: bad args");
-  PD_CHECK(a->pred_type >= 0 && a->pred_type <= 2, PD_ERR_ARG, "pd_ddim_step: bad prediction type");
-  PD_CHECK(!a->uncond_out || a->w, PD_ERR_ARG, "pd_ddim_step: guidance without weights");
-  // uncond_out and pred_x0 go through the same f32x4 loads / stores as the other three (NULL passes: 0 % 16 == 0)
-  PD_CHECK(((uintptr_t)a->sample % 16 == 0) && ((uintptr_t)a->model_out % 16 == 0) && ((uintptr_t)a->prev_sample % 16 == 0) &&
-           ((uintptr_t)a->uncond_out % 16 == 0) && ((uintptr_t)a->pred_x0 % 16 == 0),
-           PD_ERR_ARG, "pd_ddim_step: tensors must be 16-byte aligned");
+  const char* const who = "pd_ddim_step";
+  PD_CHECK(a != nullptr, PD_ERR_ARG, "%s: null args", who);
+  if (const int rc = step_validate_common(a->numel, a->per_sample, a->pred_type, who, PD_ERR_ARG)) return rc;
+  PD_CHECK(a->sample && a->model_out && a->prev_sample, PD_ERR_ARG, "%s: sample / model_out / prev_sample is NULL", who);
+  PD_CHECK(!a->uncond_out || a->w, PD_ERR_ARG, "%s: guidance without weights", who);
+  if (const int rc = step_check_aligned16({{"sample", a->sample}, {"model_out", a->model_out}, {"uncond_out", a->uncond_out},
+                                           {"prev_sample", a->prev_sample}, {"pred_x0", a->pred_x0}}, who)) return rc;
   const unsigned grid = (unsigned)((a->numel + 1023) / 1024);
   hipLaunchKernelGGL(ddim_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
   PD_LAUNCH_CHECK();

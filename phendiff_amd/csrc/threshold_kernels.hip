@@ -3,10 +3,11 @@
 //   pd_abs_quantile         out[b] = lerp(a_(lo), a_(hi), w) over |x[b][:]|: an exact per-row order statistic, no host read
 //   pd_ddim_step_threshold  pd_ddim_step with  s = min(max(q[b], 1), sample_max_value),  x0 = min(max(x0, -s), s) / s  for the static clamp
 //
-// Which x0 is thresholded: pd_ddim_step_threshold RECOMPUTES x0 from sample / model_out (/ uncond_out) through ddim_x0_eps (pd_guided.h),
+// Which x0 is thresholded: pd_ddim_step_threshold RECOMPUTES x0 from sample / model_out (/ uncond_out) through ddim_x0_eps (pd_step.h),
 // the inline function pd_ddim_raw_x0 went through, under the same contraction setting (off) and after the same guidance combine
-// (threshold_operands below, one definition for both kernels): the same IEEE operations on the same inputs, so the x0 that is thresholded
-// is bit for bit the x0 whose quantile was taken, and the update does not read the scratch buffer again.
+// (step_operands, pd_step.h: one definition for every step kernel): the same IEEE operations on the same inputs, so the x0 that is
+// thresholded is bit for bit the x0 whose quantile was taken, and the update does not read the scratch buffer again.  The clamp is
+// threshold_limit (pd_step.h), the one pd_multistep_step applies.
 //
 // ---- pd_abs_quantile: most-significant-digit radix select over the 31 bits of |v| (11 + 10 + 10) -----------------------------------------
 // For everything that is not a NaN the bit pattern of |v| orders like the value, so the k-th smallest key IS the order statistic.  Per
@@ -27,7 +28,7 @@
 //   pass p = 1, 2.  Zeroed by the entry point on the stream, by a kernel of its own (abs_zero_kernel), and every pass has its own
 //   histogram.  Not hipMemsetAsync: captured, its memset node zeroed the 98 560 bytes of a (4, 3072) workspace on the first replay of a
 //   graph and filled them with a 16-byte pattern of two addresses on every later one (docs/LAB_r19.md) -- a kernel node replays as launched.
-#include "pd_guided.h"
+#include "pd_step.h"
 
 namespace pd {
 
@@ -162,96 +163,48 @@ __global__ __launch_bounds__(AQ_THREADS) void abs_select_kernel(uint32_t* __rest
 }
 
 // ---- the step ------------------------------------------------------------------------------------------------------------------------------
-// What both kernels below do first, so that they cannot differ: four elements' sample and (guidance-combined) model output, exactly as
-// ddim_step_kernel (small_kernels.hip) forms them.  b[j]: the row of element i0 + j (lanes past numel take element i0's).
-struct ThresholdOperands { float x[4], out[4]; int64_t b[4]; int cnt; };
-
-__device__ __forceinline__ ThresholdOperands threshold_operands(const pd_ddim_step_threshold_args& a, const int64_t i0) {
-#pragma clang fp contract(off)
-  ThresholdOperands r;
-  r.cnt = (int)min((int64_t)4, a.numel - i0);
-  float o[4], u[4];
-  if (r.cnt == 4) {
-    const f32x4 vx = *(const f32x4*)(a.sample + i0), vo = *(const f32x4*)(a.model_out + i0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { r.x[j] = vx[j]; o[j] = vo[j]; u[j] = 0.f; }
-    if (a.uncond_out) { const f32x4 vu = *(const f32x4*)(a.uncond_out + i0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) u[j] = vu[j]; }
-  } else {
-    for (int j = 0; j < 4; ++j) { r.x[j] = j < r.cnt ? a.sample[i0 + j] : 0.f; o[j] = j < r.cnt ? a.model_out[i0 + j] : 0.f;
-      u[j] = (a.uncond_out && j < r.cnt) ? a.uncond_out[i0 + j] : 0.f; }
-  }
-  const int64_t b0 = i0 / a.per_sample;
-  int64_t b = b0, rem = i0 - b0 * a.per_sample;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (rem == a.per_sample) { rem = 0; ++b; }
-    ++rem;
-    r.b[j] = j < r.cnt ? b : b0;
-    r.out[j] = o[j];
-    if (a.uncond_out) {
-      const float w = a.w_per_sample ? a.w[r.b[j]] : a.w[0];
-      r.out[j] = guidance_combine(a.guidance_cfg, o[j], u[j], w);
-    }
-  }
-  return r;
-}
-
-// RAW: x0 -> `raw` only.  Otherwise the thresholded update.
+// RAW: x0 -> `raw` only.  Otherwise the thresholded update.  Both take their operands from step_operands and their x0 from ddim_x0_eps
+// (pd_step.h), so that they cannot differ.
 template <bool RAW>
 __global__ __launch_bounds__(256) void threshold_step_kernel(const pd_ddim_step_threshold_args a, float* __restrict__ raw) {
 #pragma clang fp contract(off)
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i0 >= a.numel) return;
-  const ThresholdOperands r = threshold_operands(a, i0);
+  const StepOperands r = step_operands(a, i0);
   float xp[4], x0v[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     float x0, eps;
     ddim_x0_eps(a, r.x[j], r.out[j], x0, eps);
     if (!RAW) {
-      float s = a.quantile[r.b[j]];
-      s = s < 1.0f ? 1.0f : s;                                          // torch.clamp(min = 1, max = sample_max_value): min first; NaN stays
-      s = s > a.sample_max_value ? a.sample_max_value : s;
-      x0 = fminf(fmaxf(x0, -s), s) / s;
+      x0 = threshold_limit(x0, a.quantile[r.row[j]], a.sample_max_value);
       xp[j] = ddim_prev(a, r.x[j], x0, eps);
     }
     x0v[j] = x0;
   }
+  if (!RAW) store_quad(a.prev_sample, i0, r.cnt, xp);
   float* const o0 = RAW ? raw : a.pred_x0;
-  if (r.cnt == 4) {
-    if (!RAW) *(f32x4*)(a.prev_sample + i0) = (f32x4){xp[0], xp[1], xp[2], xp[3]};
-    if (o0) *(f32x4*)(o0 + i0) = (f32x4){x0v[0], x0v[1], x0v[2], x0v[3]};
-  } else {
-    for (int j = 0; j < r.cnt; ++j) { if (!RAW) a.prev_sample[i0 + j] = xp[j]; if (o0) o0[i0 + j] = x0v[j]; }
-  }
+  if (o0) store_quad(o0, i0, r.cnt, x0v);
 }
 
 // what both step entry points refuse; `x0`: pd_ddim_raw_x0's output (then prev_sample / pred_x0 / quantile are not looked at)
 static int threshold_step_validate(const pd_ddim_step_threshold_args* a, const float* x0, bool raw, const char* who) {
   PD_CHECK(a != nullptr, PD_ERR_ARG, "%s: null args", who);
-  PD_CHECK(a->numel > 0, PD_ERR_SHAPE, "%s: numel = %lld (must be > 0)", who, (long long)a->numel);
-  PD_CHECK(a->per_sample > 0 && a->numel % a->per_sample == 0, PD_ERR_SHAPE, "%s: numel %lld is not a multiple of per_sample %lld", who,
-           (long long)a->numel, (long long)a->per_sample);
+  if (const int rc = step_validate_common(a->numel, a->per_sample, a->pred_type, who, PD_ERR_SHAPE)) return rc;
   PD_CHECK(a->numel < (1ll << 41), PD_ERR_SHAPE, "%s: numel %lld overflows the grid (must be below 2^41)", who, (long long)a->numel);
-  PD_CHECK(a->pred_type >= 0 && a->pred_type <= 2, PD_ERR_ARG, "%s: bad prediction type %d", who, a->pred_type);
   PD_CHECK(a->sample && a->model_out, PD_ERR_ARG, "%s: sample / model_out is NULL", who);
   PD_CHECK(!a->uncond_out || a->w, PD_ERR_ARG, "%s: guidance without weights", who);
-  PD_CHECK(((uintptr_t)a->sample % 16 == 0) && ((uintptr_t)a->model_out % 16 == 0) && ((uintptr_t)a->uncond_out % 16 == 0), PD_ERR_ARG,
-           "%s: tensors must be 16-byte aligned", who);
   PD_CHECK((uintptr_t)a->w % 4 == 0, PD_ERR_ARG, "%s: w must be 4-byte aligned", who);
   if (raw) {
     PD_CHECK(x0 != nullptr, PD_ERR_ARG, "%s: x0 is NULL", who);
-    PD_CHECK((uintptr_t)x0 % 16 == 0, PD_ERR_ARG, "%s: tensors must be 16-byte aligned", who);
-    return PD_OK;
+    return step_check_aligned16({{"sample", a->sample}, {"model_out", a->model_out}, {"uncond_out", a->uncond_out}, {"x0", x0}}, who);
   }
   PD_CHECK(a->prev_sample != nullptr, PD_ERR_ARG, "%s: prev_sample is NULL", who);
   PD_CHECK(a->quantile != nullptr, PD_ERR_ARG, "%s: quantile is NULL", who);
-  PD_CHECK(((uintptr_t)a->prev_sample % 16 == 0) && ((uintptr_t)a->pred_x0 % 16 == 0), PD_ERR_ARG, "%s: tensors must be 16-byte aligned", who);
   PD_CHECK((uintptr_t)a->quantile % 4 == 0, PD_ERR_ARG, "%s: quantile must be 4-byte aligned", who);
   PD_CHECK(a->sample_max_value > 0.0f, PD_ERR_ARG, "%s: sample_max_value = %g (must be positive)", who, (double)a->sample_max_value);
-  return PD_OK;
+  return step_check_aligned16({{"sample", a->sample}, {"model_out", a->model_out}, {"uncond_out", a->uncond_out},
+                               {"prev_sample", a->prev_sample}, {"pred_x0", a->pred_x0}}, who);
 }
 
 static int abs_quantile_validate_sizes(int64_t B, int64_t n) {

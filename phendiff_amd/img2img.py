@@ -313,17 +313,15 @@ class _LpGuidance:
         self.d_out, self.d_direct = torch.empty_like(like), torch.empty_like(like)
         self.splits = max(1, min(64, like[0].numel() // 4096))
         self.partial = torch.empty(like.shape[0] * self.splits, dtype=torch.float64, device=like.device)
-        c = sched.config
-        # (the fields `GuidedStepArgs` shares)
-        self.common = dict(numel=like.numel(), per_sample=like[0].numel(), pred_type=L.PD_PRED[c.prediction_type],
-                           clip=int(bool(c.clip_sample)), clip_range=float(c.clip_sample_range))
+        self.sizes = dict(numel=like.numel(), per_sample=like[0].numel())      # (the fields `GuidedStepArgs` shares, with step_fields)
 
     def args(self, t, sample: torch.Tensor, losses: torch.Tensor) -> L.LpGuidanceArgs:
-        sa, sb, _, _, _ = self.sched.step_coefficients(t)
-        return L.LpGuidanceArgs(sqrt_a=sa, sqrt_b=sb, p=self.p, sample=sample.data_ptr(), model_out=self.model_out.data_ptr(),
+        fields = self.sched.step_fields(t)      # x0 is DDIMScheduler.step's: its prediction type, clamp and level; not the update's half
+        del fields["sqrt_ap"], fields["dir_coef"]
+        return L.LpGuidanceArgs(p=self.p, sample=sample.data_ptr(), model_out=self.model_out.data_ptr(),
                                 target=self.target.data_ptr(), partial=self.partial.data_ptr(), splits=self.splits,
                                 d_model_out=self.d_out.data_ptr(), d_sample_direct=self.d_direct.data_ptr(), losses=losses.data_ptr(),
-                                **self.common)
+                                **fields, **self.sizes)
 
 
 @torch.no_grad()

@@ -89,6 +89,31 @@ def quantile_rank(n: int, q: float):
 _PRED = L.PD_PRED
 
 
+def _ptr(b):
+    """A buffer as the structs take it: the device pointer of a dense tensor; a raw device pointer (int) or None as it is."""
+    return b.data_ptr() if torch.is_tensor(b) else b
+
+
+def step_operands(sample, model_out, uncond_out=None, w=None, guidance_cfg=False, numel=None, per_sample=None, w_per_sample=None) -> dict:
+    """The operand fields the step structs share (``pd_ddim_step_args``, ``pd_ddim_step_threshold_args``, ``pd_multistep_step_args``): what
+    ``step_operands`` of csrc/pd_step.h reads.  Buffers are dense fp32 tensors or raw device pointers (ints); ``numel`` / ``per_sample``
+    default to ``sample``'s and ``w_per_sample`` to "``w`` holds more than one weight", so raw pointers need them spelled out."""
+    if numel is None:
+        numel, per_sample = sample.numel(), sample[0].numel()
+    if w_per_sample is None:
+        w_per_sample = torch.is_tensor(w) and w.numel() > 1
+    return dict(numel=numel, per_sample=per_sample, sample=_ptr(sample), model_out=_ptr(model_out), uncond_out=_ptr(uncond_out), w=_ptr(w),
+                w_per_sample=int(w_per_sample), guidance_cfg=int(guidance_cfg))
+
+
+def abs_quantile_args(sample, ratio: float, x0_raw, quant, workspace) -> "L.AbsQuantileArgs":
+    """``pd_abs_quantile`` over the raw x0 of a (B, ...) ``sample``: the per-sample quantile of ``|x0|`` at ``ratio`` into ``quant``."""
+    B, n = sample.shape[0], sample[0].numel()
+    lo, hi, wgt = quantile_rank(n, float(ratio))
+    return L.AbsQuantileArgs(B=B, n=n, rank_lo=lo, rank_hi=hi, weight=wgt, x=x0_raw.data_ptr(), out=quant.data_ptr(),
+                             workspace=workspace.data_ptr())
+
+
 class ThresholdStep:
     """The launches of one dynamically thresholded DDIM update (:meth:`DDIMScheduler.threshold_step` builds it): the argument structs,
     and :meth:`enqueue`, the one place where the sequence is written down.  It holds the three scratch tensors the structs point at
@@ -329,21 +354,24 @@ class _SchedulerBase:
         spelled out.  ``uncond_out`` + ``w``: the guidance combine runs inside the update (``guidance_cfg``: the "CFG" equation)."""
         if getattr(self.config, "thresholding", False):
             raise ValueError("this scheduler thresholds dynamically: a step is DDIMScheduler.threshold_step's launches, not one pd_ddim_step")
-        sa, sb, sap, dirc, _ = self.step_coefficients(timestep, eta)
-        ptr = lambda b: b.data_ptr() if torch.is_tensor(b) else b
-        if numel is None:
-            numel, per_sample = sample.numel(), sample[0].numel()
-        if w_per_sample is None:
-            w_per_sample = torch.is_tensor(w) and w.numel() > 1
-        c = self.config
-        return L.DdimStepArgs(numel=numel, per_sample=per_sample, pred_type=_PRED[c.prediction_type], clip=int(bool(c.clip_sample)),
-                              clip_range=float(c.clip_sample_range), use_clipped_model_output=int(bool(use_clipped_model_output)),
-                              sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=ptr(sample), model_out=ptr(model_out),
-                              uncond_out=ptr(uncond_out), w=ptr(w), w_per_sample=int(w_per_sample), guidance_cfg=int(guidance_cfg),
-                              prev_sample=ptr(prev_sample), pred_x0=ptr(pred_x0))
+        return L.DdimStepArgs(use_clipped_model_output=int(bool(use_clipped_model_output)), prev_sample=_ptr(prev_sample), pred_x0=_ptr(pred_x0),
+                              **self.step_fields(timestep, eta),
+                              **step_operands(sample, model_out, uncond_out, w, guidance_cfg, numel, per_sample, w_per_sample))
 
-    def _device_step(self, model_output, timestep, sample, eta, use_clipped_model_output, generator, variance_noise,
-                     uncond_output=None, w=None, guidance_cfg=False, out=None, want_x0=True, stream=None):
+    def step_fields(self, timestep, eta: float = 0.0, clip: bool = True) -> dict:
+        """The scheduler's part of a DDIM-family struct (``pd_ddim_step_args``, ``pd_guided_step_args``; ``clip=False``:
+        ``pd_ddim_step_threshold_args``, which has no static clamp): prediction type and clipping from the config, the four coefficients
+        of the update at ``timestep`` from :meth:`step_coefficients`."""
+        c = self.config
+        sa, sb, sap, dirc, _ = self.step_coefficients(timestep, eta)
+        fields = dict(pred_type=_PRED[c.prediction_type], sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc)
+        if clip:
+            fields.update(clip=int(bool(c.clip_sample)), clip_range=float(c.clip_sample_range))
+        return fields
+
+    def _prepare_step(self, model_output, sample, uncond_output, w, out, want_x0, stream):
+        """What an eager step works on: ``(x, model_out, prev, x0, uncond, weights, stream)`` -- the kernels read dense fp32; ``prev`` is
+        ``out`` where given, ``x0`` None unless wanted, ``uncond`` / ``weights`` None without guidance."""
         if not (sample.is_cuda and model_output.is_cuda):
             raise L.PhenDiffHipError("phendiff_amd schedulers step on MI355X tensors only (no CPU fallback)")
         if self.num_inference_steps is None:
@@ -354,9 +382,13 @@ class _SchedulerBase:
         x0 = torch.empty_like(x) if want_x0 else None
         wt = uo = None
         if uncond_output is not None:
-            uo = uncond_output.contiguous().float()      # the kernel reads dense fp32, as it does model_output
-            wt = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+            uo, wt = uncond_output.contiguous().float(), guidance_weights(w, x.device)
         st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+        return x, mo, prev, x0, uo, wt, st
+
+    def _device_step(self, model_output, timestep, sample, eta, use_clipped_model_output, generator, variance_noise,
+                     uncond_output=None, w=None, guidance_cfg=False, out=None, want_x0=True, stream=None):
+        x, mo, prev, x0, uo, wt, st = self._prepare_step(model_output, sample, uncond_output, w, out, want_x0, stream)
         if getattr(self.config, "thresholding", False):
             self.threshold_step(timestep, x, mo, prev, st, uo, wt, guidance_cfg, use_clipped_model_output, x0, eta).enqueue(st)
         else:
@@ -477,18 +509,12 @@ class DDIMScheduler(_SchedulerBase):
         :data:`THRESHOLD_SCRATCH_SETS` sets used last (4 (B n + B) + 24 640 B bytes each) and lets older ones go; the returned step
         holds its set itself, so whoever keeps the step (a runner's captured graph) keeps the memory it launches into."""
         c = self.config
-        B, n = sample.shape[0], sample[0].numel()
         x0_raw, quant, workspace = self._threshold_scratch(sample, stream)
-        sa, sb, sap, dirc, _ = self.step_coefficients(timestep, eta)
-        ptr = lambda b: b.data_ptr() if torch.is_tensor(b) else b
         step = L.DdimStepThresholdArgs(
-            numel=B * n, per_sample=n, pred_type=_PRED[c.prediction_type], use_clipped_model_output=int(bool(use_clipped_model_output)),
-            sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc, sample=ptr(sample), model_out=ptr(model_out), uncond_out=ptr(uncond_out),
-            w=ptr(w), w_per_sample=int(torch.is_tensor(w) and w.numel() > 1), guidance_cfg=int(guidance_cfg), prev_sample=ptr(prev_sample),
-            pred_x0=ptr(pred_x0), quantile=quant.data_ptr(), sample_max_value=float(c.sample_max_value))
-        lo, hi, wgt = quantile_rank(n, float(c.dynamic_thresholding_ratio))
-        q = L.AbsQuantileArgs(B=B, n=n, rank_lo=lo, rank_hi=hi, weight=wgt, x=x0_raw.data_ptr(), out=quant.data_ptr(),
-                              workspace=workspace.data_ptr())
+            use_clipped_model_output=int(bool(use_clipped_model_output)), prev_sample=_ptr(prev_sample), pred_x0=_ptr(pred_x0),
+            quantile=quant.data_ptr(), sample_max_value=float(c.sample_max_value), **self.step_fields(timestep, eta, clip=False),
+            **step_operands(sample, model_out, uncond_out, w, guidance_cfg))
+        q = abs_quantile_args(sample, c.dynamic_thresholding_ratio, x0_raw, quant, workspace)
         return ThresholdStep(step, q, x0_raw, quant, workspace, int(stream))
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False,
@@ -679,20 +705,18 @@ class _MultistepBase(_SchedulerBase):
         or raw device pointers (ints), as for ``ddim_step_args``; ``hist_in`` holds the previous step's ``hist_out`` (not read by a
         first-order step, may be None then).  ``quantile``: the (B,) output of ``pd_abs_quantile`` over this step's raw x0 (the dynamic
         threshold replaces the clamp)."""
+        operands = step_operands(sample, model_out, uncond_out, w, guidance_cfg, numel, per_sample, w_per_sample)
+        return self._update_args(i, first, operands, prev_sample, hist_in, hist_out, pred_x0, quantile)
+
+    def _update_args(self, i, first, operands: dict, prev_sample, hist_in, hist_out, pred_x0, quantile):
         sa, sb, a, b, c = self.multistep_coefficients(i, first)
-        ptr = lambda t: t.data_ptr() if torch.is_tensor(t) else t
-        if numel is None:
-            numel, per_sample = sample.numel(), sample[0].numel()
-        if w_per_sample is None:
-            w_per_sample = torch.is_tensor(w) and w.numel() > 1
         cfg = self.config
         clip = self.form == DATA_FORM and bool(getattr(cfg, "clip_sample", False))
-        return L.MultistepStepArgs(numel=numel, per_sample=per_sample, pred_type=_PRED[cfg.prediction_type], form=self.form, clip=int(clip),
+        return L.MultistepStepArgs(pred_type=_PRED[cfg.prediction_type], form=self.form, clip=int(clip),
                                    clip_range=float(getattr(cfg, "clip_sample_range", 1.0)), sqrt_a=sa, sqrt_b=sb, a=a, b=b, c=c,
-                                   sample=ptr(sample), model_out=ptr(model_out), uncond_out=ptr(uncond_out), w=ptr(w),
-                                   w_per_sample=int(w_per_sample), guidance_cfg=int(guidance_cfg), hist_in=ptr(hist_in) if c != 0.0 else None,
-                                   prev_sample=ptr(prev_sample), hist_out=ptr(hist_out), pred_x0=ptr(pred_x0), quantile=ptr(quantile),
-                                   sample_max_value=float(getattr(cfg, "sample_max_value", 1.0)))
+                                   hist_in=_ptr(hist_in) if c != 0.0 else None, prev_sample=_ptr(prev_sample), hist_out=_ptr(hist_out),
+                                   pred_x0=_ptr(pred_x0), quantile=_ptr(quantile), sample_max_value=float(getattr(cfg, "sample_max_value", 1.0)),
+                                   **operands)
 
     def solver_step(self, i: int, sample, model_out, prev_sample, hist_in, hist_out, stream: int, uncond_out=None, w=None,
                     guidance_cfg=False, pred_x0=None, first: bool = False):
@@ -702,18 +726,14 @@ class _MultistepBase(_SchedulerBase):
         cfg = self.config
         if not (self.form == DATA_FORM and getattr(cfg, "thresholding", False)):
             return self.multistep_step_args(i, sample, model_out, prev_sample, hist_in, hist_out, uncond_out, w, guidance_cfg, pred_x0, first)
-        B, n = sample.shape[0], sample[0].numel()
         x0_raw, quant, workspace = self._threshold_scratch(sample, stream)
-        update = self.multistep_step_args(i, sample, model_out, prev_sample, hist_in, hist_out, uncond_out, w, guidance_cfg, pred_x0, first,
-                                          quantile=quant)
-        raw = L.DdimStepThresholdArgs(
-            numel=B * n, per_sample=n, pred_type=update.pred_type, use_clipped_model_output=0, sqrt_a=update.sqrt_a, sqrt_b=update.sqrt_b,
-            sqrt_ap=0.0, dir_coef=0.0, sample=update.sample, model_out=update.model_out, uncond_out=update.uncond_out, w=update.w,
-            w_per_sample=update.w_per_sample, guidance_cfg=update.guidance_cfg, prev_sample=update.prev_sample, pred_x0=None,
-            quantile=quant.data_ptr(), sample_max_value=update.sample_max_value)
-        lo, hi, wgt = quantile_rank(n, float(cfg.dynamic_thresholding_ratio))
-        q = L.AbsQuantileArgs(B=B, n=n, rank_lo=lo, rank_hi=hi, weight=wgt, x=x0_raw.data_ptr(), out=quant.data_ptr(),
-                              workspace=workspace.data_ptr())
+        operands = step_operands(sample, model_out, uncond_out, w, guidance_cfg)      # one dict: both structs name the same operands
+        update = self._update_args(i, first, operands, prev_sample, hist_in, hist_out, pred_x0, quant)
+        sa, sb = self.multistep_coefficients(i, first)[:2]
+        raw = L.DdimStepThresholdArgs(pred_type=_PRED[cfg.prediction_type], use_clipped_model_output=0, sqrt_a=sa, sqrt_b=sb, sqrt_ap=0.0,
+                                      dir_coef=0.0, prev_sample=_ptr(prev_sample), pred_x0=None, quantile=quant.data_ptr(),
+                                      sample_max_value=float(cfg.sample_max_value), **operands)
+        q = abs_quantile_args(sample, cfg.dynamic_thresholding_ratio, x0_raw, quant, workspace)
         return MultistepThresholdStep(update, raw, q, x0_raw, quant, workspace, int(stream))
 
     def _device_step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None, variance_noise=None,
@@ -724,24 +744,12 @@ class _MultistepBase(_SchedulerBase):
         here and is ignored; ``generator`` is not read (eta = 0: no variance noise)."""
         if eta != 0 or variance_noise is not None:
             raise ValueError(f"{type(self).__name__} is a deterministic ODE solver: eta = {eta} / variance noise has no SDE variant here")
-        if not (sample.is_cuda and model_output.is_cuda):
-            raise L.PhenDiffHipError("phendiff_amd schedulers step on MI355X tensors only (no CPU fallback)")
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        x, mo, prev, x0, uo, wt, st = self._prepare_step(model_output, sample, uncond_output, w, out, want_x0 and self.form == DATA_FORM, stream)
         i = self.step_index(timestep)
-        x = sample.contiguous().float()
-        mo = model_output.contiguous().float()
-        prev = torch.empty_like(x) if out is None else out
-        x0 = torch.empty_like(x) if (want_x0 and self.form == DATA_FORM) else None
-        wt = uo = None
-        if uncond_output is not None:
-            uo = uncond_output.contiguous().float()
-            wt = (w if torch.is_tensor(w) else torch.tensor([float(w)])).to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
         hist = self._hist
         first = hist is None or self._next_index != i or hist[0].shape != x.shape or hist[0].device != x.device
         if hist is None or hist[0].shape != x.shape or hist[0].device != x.device:
             hist = self._hist = (torch.empty_like(x), torch.empty_like(x))
-        st = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
         a = self.solver_step(i, x, mo, prev, hist[(i + 1) % 2], hist[i % 2], st, uo, wt, guidance_cfg, x0, first)
         if isinstance(a, ThresholdStep):
             a.enqueue(st)

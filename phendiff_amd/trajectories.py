@@ -186,14 +186,10 @@ class _GuidedSteps:
         self.ts_rows = torch.tensor(timesteps, dtype=torch.float32).repeat_interleave(B).to(dev)
         self.losses = torch.zeros((len(timesteps), B), dtype=torch.float32, device=dev)
         self.lp_args = [lp.args(t, x, self.losses[i]) for i, t in enumerate(timesteps)]
-        self.step_args = []
-        for t in timesteps:
-            sa, sb, sap, dirc, _ = sched.step_coefficients(t)
-            self.step_args.append(L.GuidedStepArgs(use_clipped_model_output=0, sqrt_a=sa, sqrt_b=sb, sqrt_ap=sap, dir_coef=dirc,
-                                                   guidance_scale=float(guidance_loss_scale), grad_scale=L.ptr(self.scale_dev),
-                                                   sample=x.data_ptr(), g_direct=lp.d_direct.data_ptr(), g_unet=plan.dsample.data_ptr(),
-                                                   model_out=model_out.data_ptr(), prev_sample=x.data_ptr(), pushed=None,
-                                                   overflow=L.ptr(self.overflow), **lp.common))
+        self.step_args = [L.GuidedStepArgs(use_clipped_model_output=0, guidance_scale=float(guidance_loss_scale), grad_scale=L.ptr(self.scale_dev),
+                                           sample=x.data_ptr(), g_direct=lp.d_direct.data_ptr(), g_unet=plan.dsample.data_ptr(),
+                                           model_out=model_out.data_ptr(), prev_sample=x.data_ptr(), pushed=None,
+                                           overflow=L.ptr(self.overflow), **sched.step_fields(t), **lp.sizes) for t in timesteps]
         plan._side_streams(torch.cuda.current_stream(dev).cuda_stream)      # (anything the backward creates lazily exists before a capture)
 
     def enqueue(self, st):

@@ -161,6 +161,10 @@ def test_argument_validation_without_gpu():
     assert lib.pd_conv(C.byref(a), None) == -2 and b"multiples of 32" in lib.pd_last_error()
     assert lib.pd_attn_d8(C.byref(L.AttnArgs(dtype=1, B=0)), None) == -2
     assert lib.pd_ddim_step(C.byref(L.DdimStepArgs(numel=0)), None) == -1
+    # per_sample < 1 or no divisor of numel (the kernel divides by it): refused like its siblings, before the pointers are looked at
+    for per_sample in (0, -8, 3):
+        assert lib.pd_ddim_step(C.byref(L.DdimStepArgs(numel=8, per_sample=per_sample, pred_type=2)), None) == L.CONSTANTS["PD_ERR_ARG"]
+        assert b"per_sample" in lib.pd_last_error() and lib.pd_last_error().startswith(b"pd_ddim_step:")
     # every tensor of pd_ddim_step goes through 16-byte loads / stores: each of the five pointers in turn at 16k + 4, the others
     # aligned, is refused before any launch (the addresses are never dereferenced)
     base = dict(sample=0x10000, model_out=0x20000, uncond_out=0x30000, prev_sample=0x40000, pred_x0=0x50000)
