@@ -184,20 +184,28 @@ template <typename T> struct AttnOps {
   // reads none of the packs' inputs (a v_exp result may not feed the very next vector instruction), and two more instructions
   // stand between the last pack and whatever follows (a vector result needs two wait states before an MFMA reads it).  e0..e2 come
   // back exponentiated.  TAIL (last sub-tile of a tile, nothing left to exponentiate): s_nop in their places.
-  template <bool TAIL>
+  template <bool TAIL, bool INPLACE = true>
   static __device__ __forceinline__ u32x4 pack4(float p0, float p1, float p2, float p3, float p4, float p5, float p6, float p7,
                                                 float& e0, float& e1, float& e2) {
     static_assert(std::is_same<T, bf16_t>::value, "the truncating pack is the bf16 engine's");
     uint32_t b0, b1, b2, b3;
-    float r0 = 0.f, r1 = 0.f, r2 = 0.f;      // results in registers of their own: an operand tied to one element of an MFMA result costs a copy
+    // INPLACE (round 28): e0..e2 are exponentiated in place, three registers fewer at the kernel's peak.  The group reads e0..e2 where it
+    // always did, so the distance to the MFMA that produced them is unchanged.  Otherwise the results get registers of their own: tied
+    // to elements of an MFMA result that has just been issued, an operand costs a copy (and the wait for that MFMA).
 #define PD_PACKS "v_perm_b32 %[b0], %[p1], %[p0], %[sel]\n\tv_perm_b32 %[b1], %[p3], %[p2], %[sel]\n\t" \
                  "v_perm_b32 %[b2], %[p5], %[p4], %[sel]\n\tv_perm_b32 %[b3], %[p7], %[p6], %[sel]\n\t"
-    if constexpr (!TAIL) {
+    if constexpr (!TAIL && !INPLACE) {
+      float r0, r1, r2;
       asm("v_exp_f32 %[r0], %[e0]\n\t" PD_PACKS "v_exp_f32 %[r1], %[e1]\n\tv_exp_f32 %[r2], %[e2]"
           : [b0] "=&v"(b0), [b1] "=&v"(b1), [b2] "=&v"(b2), [b3] "=&v"(b3), [r0] "=&v"(r0), [r1] "=&v"(r1), [r2] "=&v"(r2)
           : [p0] "v"(p0), [p1] "v"(p1), [p2] "v"(p2), [p3] "v"(p3), [p4] "v"(p4), [p5] "v"(p5), [p6] "v"(p6), [p7] "v"(p7), [e0] "v"(e0), [e1] "v"(e1), [e2] "v"(e2),
             [sel] "s"(0x07060302u));
       e0 = r0; e1 = r1; e2 = r2;
+    } else if constexpr (!TAIL) {
+      asm("v_exp_f32 %[e0], %[e0]\n\t" PD_PACKS "v_exp_f32 %[e1], %[e1]\n\tv_exp_f32 %[e2], %[e2]"
+          : [b0] "=&v"(b0), [b1] "=&v"(b1), [b2] "=&v"(b2), [b3] "=&v"(b3), [e0] "+v"(e0), [e1] "+v"(e1), [e2] "+v"(e2)
+          : [p0] "v"(p0), [p1] "v"(p1), [p2] "v"(p2), [p3] "v"(p3), [p4] "v"(p4), [p5] "v"(p5), [p6] "v"(p6), [p7] "v"(p7),
+            [sel] "s"(0x07060302u));
     } else {
       asm("s_nop 0\n\t" PD_PACKS "s_nop 1" : [b0] "=&v"(b0), [b1] "=&v"(b1), [b2] "=&v"(b2), [b3] "=&v"(b3)
           : [p0] "v"(p0), [p1] "v"(p1), [p2] "v"(p2), [p3] "v"(p3), [p4] "v"(p4), [p5] "v"(p5), [p6] "v"(p6), [p7] "v"(p7), [sel] "s"(0x07060302u));
@@ -499,27 +507,48 @@ __global__ __launch_bounds__(WPB * 64) void attn_kernel(const pd_attn_args a) {
 //     |q| * max|k| - m <= THR every later tile runs the check-free body with no LDS read in front of it.
 //   * bf16 (round 26, docs/LAB_r26.md; no bit moves): the check-free tiles run in a loop of their own, the constant k-slots are a whole
 //     tile of identical rows, and the exponentials and packs of a sub-tile are issued as two hand-placed groups (AttnOps::pack4).
+//   * bf16 (round 28, docs/LAB_r28.md; no bit moves): the whole kernel fits 80 VGPRs without scratch, so THREE workgroups are resident
+//     per CU (6 waves per SIMD; 34 816 B of LDS each) where 94 registers held two: the vector port is the binding resource and the
+//     extra waves fill cycles in which all four of a SIMD's waves sat in s_waitcnt or at the tile barrier.  What was given up: the V^T
+//     fragments are read inside their sub-tile instead of one ahead, the first pack group exponentiates in place, the two staging buffers are
+//     twin images one wave-uniform offset apart, the DMA's global base is scalar (VIN / TWIN / SBASE below).
+//     The register target is DECLARED (amdgpu_waves_per_eu minimum 6): a change that grows the kernel shows as scratch in
+//     scripts/kernel_resource_usage.py instead of silently losing the third workgroup.  fp16: the default (2), its code is untouched.
 constexpr int ATTN_DMA_KT = 256;                                                      // keys per LDS tile (one barrier per tile)
 template <typename T>
-__global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(std::is_same<T, bf16_t>::value ? 6 : 2)))
+void attn_glds_kernel(const pd_attn_args a) {
   static_assert(sizeof(T) == 2, "16-bit element types");
   using Ops = AttnOps<T>;
   constexpr int KT = ATTN_DMA_KT;
   constexpr int KROW = 16, TILE = KT * KROW;
   // one LDS array, addressed by byte offsets (plain integers keep every access a ds_* instruction):
-  //   K tiles [2][TILE] | V tiles [2][TILE] | constants [ONES] ([1 0 0 0 | 0 0 0 0] per 16 bytes, see voff below) | k-slots 8..15 of every K row (16 B; bf16: TILE bytes of them)
+  //   K tiles [2][TILE] | V tiles [2][TILE] | constants [ONES] ([1 0 0 0 | 0 0 0 0] per 16 bytes, see voff below) | k-slots 8..15 of every K row (16 B)
+  //   bf16 (TWIN): [2] x { K tile | V tile | constants [ONES] | k-slots 8..15 as TILE bytes of identical rows | pad to 1 KiB }
   constexpr int ONES = TILE + 256;                     // the ones lanes read up to 128 + 8 bytes past a tile-sized block
-  constexpr int K_OFF = 0, V_OFF = 2 * TILE, ONES_OFF = 4 * TILE, KCONST_OFF = 4 * TILE + ONES;
   // round 26, bf16 engine only (the fp16 instantiation keeps the code it had): bit-identical re-schedulings of the check-free tiles
   constexpr bool BF = std::is_same<T, bf16_t>::value;
   constexpr bool HAND = BF, KC = BF, LOOPS = BF;
+  // round 28, bf16 engine only: the kernel fits 80 VGPRs, so that three workgroups (6 waves per SIMD) are resident per CU.
+  //   VIN:  the V^T fragments of a sub-tile are read inside that sub-tile instead of being carried across the iteration (8 registers)
+  //   TWIN: the two staging buffers are two identical images [K tile | V tile | constants | constant K rows], BUF bytes apart, so the flip
+  //         is one wave-uniform offset for every lane (the constants exist twice; no lane-varying stride registers)
+  //   SBASE: the DMA's global base is a scalar pair advanced per tile; the lane supplies a 32-bit offset inside the tile
+  //   G1IN: the FIRST pack group of a sub-tile exponentiates its three scores in place (pack4); the second group, whose three scores
+  //         belong to the next sub-tile's fresh MFMA result, keeps registers of its own (in place it cost four copies per tile)
+  //   LATE: the lane's half, its query index and the half exchange of the exact path hold no register across the check-free loop
+  //         (re-derived behind it; v_permlane32_swap instead of a bpermute with an address register)
+  constexpr bool VIN = BF, TWIN = BF, SBASE = BF, G1IN = BF, G2IN = false, LATE = BF;
+  constexpr int BUF = TWIN ? (3 * TILE + ONES + 1023) / 1024 * 1024 : TILE;     // bytes between the two staging buffers
+  constexpr int K_OFF = 0, V_OFF = TWIN ? TILE : 2 * TILE, ONES_OFF = TWIN ? 2 * TILE : 4 * TILE, KCONST_OFF = ONES_OFF + ONES;
   // KC: the constant k-slots as a whole tile of identical rows, so that the lanes of both halves step through their K fragments with
   // the SAME stride -- every fragment address of a tile is one register plus an instruction offset, no per-sub-tile address add
   constexpr int KCONST_BYTES = KC ? TILE : 16;
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[4 * TILE + ONES + KCONST_BYTES];
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[TWIN ? 2 * BUF : 4 * TILE + ONES + KCONST_BYTES];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
+  const int r = lane & 31;
+  int h = lane >> 5;                                   // (re-derived behind the check-free loop: LATE)
   const int nqb = (a.N + 255) / 256;
   const int total = nqb * a.heads * a.B;
   int item = blockIdx.x;
@@ -532,7 +561,7 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
 
   const float qscale = 0.35355339059327373f * 1.4426950408889634f;
   constexpr float RESCALE_THR = Ops::RESCALE_THR;
-  const int query = qb * 256 + wave * 32 + r;
+  int query = qb * 256 + wave * 32 + r;
   typename Ops::QF qf = Ops::load_q(qp + (size_t)min(query, N - 1) * 8, h, qscale);
   float qn = Ops::q_norm2(qf);
   qn += __shfl_xor(qn, 32);
@@ -543,16 +572,18 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
   float m = 0.f;
 
   // constant LDS content
-  if (KC ? tid < KT : tid == 0) Ops::init_const_slot(lds + KCONST_OFF + (KC ? tid * KROW : 0));
+  if constexpr (TWIN) Ops::init_const_slot(lds + (tid >> 8) * BUF + KCONST_OFF + (tid & 255) * KROW);      // 512 threads: 256 rows, twice
+  else if (KC ? tid < KT : tid == 0) Ops::init_const_slot(lds + KCONST_OFF + (KC ? tid * KROW : 0));
   for (int i16 = tid; i16 < ONES / 16; i16 += 512) {     // every 16 bytes: [1 0 0 0 | 0 0 0 0]
     T one8[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) one8[i] = Elem<T>::from_f(i == 0 ? 1.0f : 0.0f);
     *(s16x8*)(lds + ONES_OFF + i16 * 16) = *(const s16x8*)one8;
+    if constexpr (TWIN) *(s16x8*)(lds + BUF + ONES_OFF + i16 * 16) = *(const s16x8*)one8;
   }
   // K fragment offset in buffer 0: h == 0 -> row r of the sub-tile; h == 1 -> the constant slot (every sub-tile, both buffers)
   const int koff = (h ? KCONST_OFF : K_OFF) + ((KC || !h) ? r * KROW : 0);
-  const int kst = (KC || !h) ? 32 * KROW : 0, kbuf = h ? 0 : TILE;
+  const int kst = (KC || !h) ? 32 * KROW : 0, kbuf = TWIN ? BUF : h ? 0 : TILE;
   // V^T fragment offsets (transposed read; EXEC is all ones wherever they are used).  Key-row lanes sit on banks
   // 16h + 32j .. +15, the ones lanes on 16h + 16 + 32j ..: no conflict inside a 32-lane half; lanes 16..31 of each half repeat
   // lanes 0..15 (A rows 16..31 are never read back)
@@ -562,7 +593,7 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
   // 22 rows of live data (power, i.e. clock, on a kernel that runs DVFS-limited)
   const bool vrow = (lane & 16) == 0 && tp < 2;
   const int voff = vrow ? V_OFF + (4 * h + tq) * KROW + 8 * tp : ONES_OFF + (16 * h + 16) * 4 + ((lane & 16) ? 8 : 0);
-  const int vbuf = vrow ? TILE : 0;
+  const int vbuf = TWIN ? BUF : vrow ? TILE : 0;
   auto load_v = [&](int base, int sub) {      // A operands of the two PV MFMAs of 32-key sub-tile `sub`
     typedef short v4s __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) v4s* lp;
@@ -584,12 +615,27 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
   const unsigned char* gsrc = (const unsigned char*)((const T*)(wave < 4 ? a.k : a.v) + bh * 8);
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
   const unsigned sdst = __builtin_amdgcn_readfirstlane(lds_base + (wave < 4 ? K_OFF : V_OFF) + (wave & 3) * 1024);
+  // SBASE: the operand's base is wave-uniform (the wave index is), so it lives in a scalar pair
+  const unsigned long long gbase = (unsigned long long)(size_t)gsrc;
+  const unsigned long long sbase = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gbase >> 32)) << 32)
+                                   | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)gbase);
   auto stage = [&](int b2, int k0) {
+    if constexpr (SBASE) {
+      static_assert(KT == 256, "one piece per wave and operand");
+      // the same rows as below: key = min(k0 + (tid & 255), N - 1) = k0 + min(tid & 255, N - 1 - k0)   (k0 < N)
+      const unsigned off = (unsigned)min(tid & 255, N - 1 - k0) * 16u;
+      const unsigned long long src = sbase + (unsigned long long)k0 * 16u;
+      const unsigned dst = sdst + b2 * BUF;
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(off), "s"(dst), "s"(src) : "memory");
+      return;
+    }
     #pragma unroll
     for (int pc = 0; pc < KT / 256; ++pc) {       // KT / 64 pieces per operand tile, 4 waves per operand
       const int key = min(k0 + ((wave & 3) + 4 * pc) * 64 + lane, N - 1);
       const unsigned char* src = gsrc + (size_t)key * 16;
-      const unsigned dst = sdst + b2 * TILE + pc * 4096;
+      const unsigned dst = sdst + b2 * BUF + pc * 4096;
       unsigned keep;
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                    : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
@@ -620,7 +666,8 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
     const int vb = voff + cur * vbuf;
     {
       typename Ops::KF kfn = Ops::load_k(lds + kl);
-      typename Ops::VF vfn = load_v(vb, 0);
+      typename Ops::VF vfn;
+      if constexpr (!VIN) vfn = load_v(vb, 0);
       f32x16 sn = Ops::qk(kfn, qf, zero);
       kfn = Ops::load_k(lds + kl + kst);
       if constexpr (HAND) {
@@ -629,12 +676,14 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
       }
 #pragma unroll
       for (int sub = 0; sub < KT / 32; ++sub) {
-        const typename Ops::VF vf = vfn;
+        typename Ops::VF vf;
+        if constexpr (VIN) vf = load_v(vb, sub);
+        else vf = vfn;
         f32x16 s = sn;
         if (sub + 1 < KT / 32) {
           sn = Ops::qk(kfn, qf, zero);
           if (sub + 2 < KT / 32) kfn = Ops::load_k(lds + kl + (sub + 2) * kst);
-          vfn = load_v(vb, sub + 1);
+          if constexpr (!VIN) vfn = load_v(vb, sub + 1);
           __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (HAND) {
@@ -644,14 +693,14 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
           for (int i = 0; i < 16; ++i) e[i] = s[i];
 #pragma unroll
           for (int i = 3; i < 8; ++i) e[i] = __builtin_amdgcn_exp2f(e[i]);
-          const u32x4 b0 = Ops::template pack4<false>(e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8], e[9], e[10]);
+          const u32x4 b0 = Ops::template pack4<false, G1IN>(e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8], e[9], e[10]);
           o = Elem<T>::mma16(__builtin_bit_cast(s16x8, vf.v[0]), __builtin_bit_cast(s16x8, b0), o);
 #pragma unroll
           for (int i = 11; i < 16; ++i) e[i] = __builtin_amdgcn_exp2f(e[i]);
           u32x4 b1;
           if (sub + 1 < KT / 32) {
             float n0 = sn[0], n1 = sn[1], n2 = sn[2];
-            b1 = Ops::template pack4<false>(e[8], e[9], e[10], e[11], e[12], e[13], e[14], e[15], n0, n1, n2);
+            b1 = Ops::template pack4<false, G2IN>(e[8], e[9], e[10], e[11], e[12], e[13], e[14], e[15], n0, n1, n2);
             sn[0] = n0; sn[1] = n1; sn[2] = n2;
           } else {
             float n0 = 0.f, n1 = 0.f, n2 = 0.f;
@@ -665,6 +714,14 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
         }
       }
     }
+  };
+  // the value the lane 32 away holds.  bf16: v_permlane32_swap instead of a bpermute, whose lane-varying address register would stay
+  // live across the check-free loop for the ragged tile behind it (pure data movement either way)
+  auto other_half = [&](float x) {
+    if constexpr (LATE) {
+      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+      return __uint_as_float(h ? sw[0] : sw[1]);     // lanes 32..63 find lanes 0..31 in the first result, lanes 0..31 their partner in the second
+    } else return __shfl_xor(x, 32);
   };
   // exact running-maximum path: ragged tiles, and full ones while the bound still allows a score above m + THR
   auto exact_tile = [&](int k0, int cur) {
@@ -690,7 +747,7 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
 #pragma unroll
           for (int i = 1; i < 16; ++i) tmax = fmaxf(tmax, s[i]);
           if (__builtin_amdgcn_ballot_w64(tmax > RESCALE_THR)) {
-            const float t2 = fmaxf(tmax, __shfl_xor(tmax, 32));
+            const float t2 = fmaxf(tmax, other_half(tmax));
             const float m_new = Ops::set_m(qf, zero, h, m + fmaxf(t2, 0.f));
             const float delta = m_new - m;
             const float sc = __builtin_amdgcn_exp2f(-delta);
@@ -725,6 +782,14 @@ __global__ __launch_bounds__(512) void attn_glds_kernel(const pd_attn_args a) {
     int k0 = 0, cur = 0;
     for (; k0 < N && !fast_ok(k0); k0 += KT, cur ^= 1) { begin_tile(k0, cur); exact_tile(k0, cur); end_tile(); }
     for (; k0 + KT <= N; k0 += KT, cur ^= 1) { begin_tile(k0, cur); fast_tile(cur); end_tile(); }
+    if constexpr (LATE) {
+      // what the ragged tile and the epilogue need of the lane's position is derived again from the thread index, through a copy the
+      // compiler cannot see through: the values of the prologue die in front of the check-free loop instead of occupying registers in it
+      int t2 = tid;
+      asm volatile("" : "+v"(t2));
+      h = (t2 >> 5) & 1;
+      query = qb * 256 + (t2 >> 6) * 32 + (t2 & 31);
+    }
     for (; k0 < N; k0 += KT, cur ^= 1) { begin_tile(k0, cur); exact_tile(k0, cur); end_tile(); }
   } else {
     for (int k0 = 0, cur = 0; k0 < N; k0 += KT, cur ^= 1) {
@@ -1245,7 +1310,10 @@ extern "C" int pd_attn_d8(const pd_attn_args* a, void* stream) {
   PD_CHECK(a->q && a->k && a->v && a->out, PD_ERR_ARG, "pd_attn_d8: null pointer");
   // One query block per wave (attn_kernel QB = 1).  QB = 2 (K / V^T fragments shared by two independent chains, 2 waves/SIMD) measured 3 %
   // slower at N = 4096: the tile time is pinned by the exp + MFMA issue mix (scripts/micro/), not by LDS traffic or occupancy.
-  // 8-wave workgroups (256 queries share each staged tile) once there are enough query blocks to fill the chip with them
+  // 8-wave workgroups (256 queries share each staged tile) once there are enough query blocks to fill the chip with them.
+  // Register budget of the DMA-staged kernel: a workgroup is 2 waves per SIMD, so resident workgroups per CU = floor(waves per SIMD / 2).
+  // bf16: 78 VGPRs (80 allocated) -> 6 waves per SIMD -> three workgroups (3 x 34 816 B of LDS); fp16: 118 -> 4 -> two.  A bf16 body
+  // above 80 registers falls back to two workgroups: the kernel declares the target, so the compiler spills instead (docs/LAB_r28.md).
   const bool wpb4_only = diag_env("PD_ATTN_WPB4", 0) != 0;      // diagnostic: same-box A/B
   const bool wide = !wpb4_only && a->N >= 1024 && (long long)(a->N / 256) * a->heads * a->B >= 1024;
   const int qpb = wide ? 256 : 128;
