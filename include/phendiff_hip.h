@@ -43,7 +43,8 @@ extern "C" {
  * args structs), pd_tile_gather, pd_tile_blend (+ their args structs), pd_ssim (+ pd_ssim_args, pd_ssim_workspace),
  * pd_knn_radii (+ pd_knn_radii_args, pd_knn_radii_workspace), pd_manifold_query (+ pd_manifold_query_args, pd_manifold_query_workspace),
  * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance, pd_multistep_step (+ pd_multistep_step_args), pd_guidance_rescale
- * (+ pd_guidance_rescale_args, pd_guidance_rescale_workspace). */
+ * (+ pd_guidance_rescale_args, pd_guidance_rescale_workspace), pd_class_contrast, pd_contrast_mask, pd_mask_blend (+ their args structs,
+ * pd_contrast_mask_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -922,6 +923,85 @@ typedef struct {
 } pd_guidance_rescale_args;
 size_t pd_guidance_rescale_workspace(int64_t B, int64_t n);
 int pd_guidance_rescale(const pd_guidance_rescale_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Class-contrast masks and the masked blend (added under ABI 8; csrc/mask_kernels.hip, host side phendiff_amd.masked): the DiffEdit recipe
+ * (arXiv 2210.11427; diffusers' StableDiffusionDiffEditPipeline.generate_mask) on the pixel tier.  All tensors dense, NCHW, fp32 unless
+ * said otherwise; per_pixel = H * W.  No atomics, no host read, no allocation, capturable; every sample's result is a function of that
+ * sample alone -- not of B, of its row in the batch, of the grid or of the replay.
+ *
+ * pd_class_contrast: one noise draw's contribution to the contrast map, from the two noise predictions a [B][C][per_pixel] (target class)
+ * and b (source class):
+ *     acc[s][p] = (first ? 0 : acc[s][p]) + (sum over c ascending of |a[s][c][p] - b[s][c][p]|) / C
+ * every operation rounded to fp32 on its own, the division once at the end.  first != 0: acc is not read (it may hold anything, NaN
+ * included).  One launch per draw; one thread per four consecutive elements of acc, the partial last quad and sample boundaries inside a
+ * quad included (16-byte loads where four pixels lie whole inside a channel plane at an aligned address, element loads elsewhere).
+ * Refused before the launch: null args / a / b / acc, pointers that are not 16-byte aligned (PD_ERR_ARG); B < 1, C outside 1..32,
+ * per_pixel < 1, B * C * per_pixel >= 2^62 (PD_ERR_SHAPE).
+ *
+ * pd_contrast_mask: the accumulated map -> the binary mask.  Per sample s:
+ *     mean  = (sum over p of acc[s][p]) / per_pixel       summed and divided in fp64, rounded to fp32 once
+ *     limit = ratio * mean                                  fp32
+ *     map[s][p]  = fminf(acc[s][p], limit) / limit          (diffusers: clamp(0, mean * ratio) / (mean * ratio))
+ *     mask[s][p] = map[s][p] > 0.5f ? 1 : 0
+ *     stats[s]   = {mean, limit, (number of pixels with mask 1) / per_pixel}     the count in integers, divided in fp64, rounded to fp32 once
+ * A sample whose limit is not a finite positive number -- the classes differ nowhere (limit = 0), or the sample holds a NaN or an
+ * infinity -- gets map = 0 and mask = 0 everywhere and the fraction 0; no other sample changes.
+ * THE MEAN IS PER SAMPLE.  diffusers takes .mean() over the whole batch of maps, which makes an image's mask depend on its neighbours in
+ * the batch; that contradicts the rule above, and at B = 1 both definitions are the same number.  (The sum over draws is not divided by
+ * their number: map is invariant to a scaling of acc.)
+ * Two launches on one tiling, as pd_guidance_rescale: per-chunk partial sums -- one workgroup of 256 threads per (sample, chunk of
+ * PD_CONTRAST_MASK_CHUNK pixels), in the fixed order lane (ascending index), wave (xor butterfly 32 ... 1), workgroup (waves 0..3) -- then
+ * the apply pass, in which every workgroup folds its own sample's partials (256 runs of consecutive chunks in index order, then the runs in
+ * index order) and writes its chunk; the workgroup of a sample's first chunk also counts the sample's mask for stats.  Which element a lane
+ * takes depends on the element's index within its sample only.  More than 65536 (sample, chunk) pairs are walked in a grid-stride loop.
+ *   map, stats: optional (NULL: not written).  workspace: pd_contrast_mask_workspace(B, per_pixel) bytes (0 for sizes the call refuses),
+ *   8-byte aligned, contents irrelevant before and after.
+ * Refused before any launch: null args / acc / mask / workspace, ratio that is not a finite positive number, acc or map not 16-byte
+ * aligned, stats not 4-byte aligned, a workspace that is not 8-byte aligned (PD_ERR_ARG); B < 1, per_pixel < 1, more than 2^31 - 1
+ * (sample, chunk) pairs (PD_ERR_SHAPE).
+ *
+ * pd_mask_blend: out[s][c][p] = mask[s][p] ? x[s][c][p] : keep[s][c][p], mask [B][per_pixel] bytes broadcast over the channels.  A
+ * SELECTION, not m * x + (1 - m) * keep: the element not taken never enters the result (a NaN or an infinity there does not reach out) and
+ * a kept element is keep's, bit for bit.  Any non-zero mask byte takes x.  out may alias x (or keep): a thread reads its four elements
+ * before it writes them.  One launch, one thread per four consecutive elements.
+ * Refused before the launch: null args / x / keep / mask / out, x / keep / out not 16-byte aligned (PD_ERR_ARG); B < 1, C outside 1..32,
+ * per_pixel < 1, B * C * per_pixel >= 2^62 (PD_ERR_SHAPE). */
+#define PD_CONTRAST_MASK_CHUNK 2048
+typedef struct {
+  int64_t B;
+  int C;                    /* 1..32 */
+  int64_t per_pixel;        /* H*W */
+  const float* a;           /* [B][C][per_pixel]: the prediction under the target class */
+  const float* b;           /* [B][C][per_pixel]: the prediction under the source class */
+  float* acc;               /* [B][per_pixel]: in (unless first) and out */
+  int first;                /* != 0: the first draw, acc is written without being read */
+} pd_class_contrast_args;
+int pd_class_contrast(const pd_class_contrast_args* a, void* stream);
+
+typedef struct {
+  int64_t B;
+  int64_t per_pixel;        /* H*W */
+  const float* acc;         /* [B][per_pixel]: the accumulated contrast of all draws */
+  float ratio;              /* threshold_ratio > 0: the map saturates at ratio * mean (diffusers' mask_thresholding_ratio, 3) */
+  uint8_t* mask;            /* [B][per_pixel]: 0 / 1 */
+  float* map;               /* [B][per_pixel] in [0, 1], or NULL */
+  float* stats;             /* [B][3]: mean, limit, masked fraction; or NULL */
+  void* workspace;          /* pd_contrast_mask_workspace(B, per_pixel) bytes */
+} pd_contrast_mask_args;
+size_t pd_contrast_mask_workspace(int64_t B, int64_t per_pixel);
+int pd_contrast_mask(const pd_contrast_mask_args* a, void* stream);
+
+typedef struct {
+  int64_t B;
+  int C;                    /* 1..32 */
+  int64_t per_pixel;        /* H*W */
+  const float* x;           /* [B][C][per_pixel]: taken where mask != 0 */
+  const float* keep;        /* [B][C][per_pixel]: taken where mask == 0 */
+  const uint8_t* mask;      /* [B][per_pixel] */
+  float* out;               /* [B][C][per_pixel] (may alias x or keep) */
+} pd_mask_blend_args;
+int pd_mask_blend(const pd_mask_blend_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Tiled trajectories (added under ABI 8; csrc/tile_kernels.hip, host side phendiff_amd.tiling): the working sample is a canvas

@@ -18,6 +18,8 @@ from .img2img import (inversion, ddib, inverted_regeneration, classifier_free_gu
 from .noise import DeviceNoise  # noqa: F401
 from .trajectories import DDIBGraph, CFGForwardStartGraph, SDDDIBGraph, GuidedTransferGraph, SDGuidedTransferGraph, TiledDDIBGraph  # noqa: F401
 from .trajectories import GenerationGraph  # noqa: F401
+from .masked import (class_contrast_mask, mask_blend, masked_ddib, MaskedDDIBGraph, MaskedTransferOutput, blend_state_index,  # noqa: F401
+                     encode_timestep, check_mask, ContrastMask)
 from .tiling import TileGrid  # noqa: F401
 from . import tiling  # noqa: F401
 from .configs import UNET_CONFIGS, SCHEDULER_CONFIGS, SD15_UNET_CONFIG  # noqa: F401

@@ -117,8 +117,9 @@ class DeviceNoise:
         return out
 
     @torch.no_grad()
-    def add_noise(self, scheduler, x: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
-        """``scheduler.add_noise(x, z, timesteps)`` with ``z`` the images' forward noise, drawn inside the launch."""
+    def add_noise(self, scheduler, x: torch.Tensor, timesteps: torch.Tensor, elem_base: int = 0) -> torch.Tensor:
+        """``scheduler.add_noise(x, z, timesteps)`` with ``z`` the images' forward noise, drawn inside the launch.  ``elem_base``: where in
+        each image's forward-noise stream the draw starts (draw ``k`` of several noisings of one image: ``k * per_sample``)."""
         self._on_device(x, "x")
         x = x.contiguous().float()
         B = x.shape[0]
@@ -126,7 +127,7 @@ class DeviceNoise:
             timesteps = timesteps.reshape(1).expand(B)
         sa, sb = scheduler._per_sample_coefs(timesteps, x.device)
         out = torch.empty_like(x)
-        self.enqueue(self.launch_args(out, B, x[0].numel(), self.PURPOSE_FORWARD_NOISE, x=x, sa=sa, sb=sb))
+        self.enqueue(self.launch_args(out, B, x[0].numel(), self.PURPOSE_FORWARD_NOISE, x=x, sa=sa, sb=sb, elem_base=elem_base))
         return out
 
     def variance_noise(self, i: int, shape) -> torch.Tensor:

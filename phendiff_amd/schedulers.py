@@ -246,6 +246,8 @@ def guidance_rescale(cond, uncond, w, guidance_rescale: float, guidance_cfg: boo
 MULTISTEP_NOT_TILED = "the tiled trajectories step DDIM on the canvas; the solver's history is not kept per canvas yet"
 MULTISTEP_NOT_GUIDED = ("the gradient-guided transfer pushes the sample between two steps, which invalidates the previous step's prediction "
                         "a multistep update reuses")
+MULTISTEP_NOT_MASKED = ("the masked transfer puts the inversion's state back outside the mask between two steps, which invalidates the previous "
+                        "step's prediction a multistep update reuses")
 MULTISTEP_NOT_LATENT = "the multistep solvers are wired into the pixel tier (ConditionalDDIMPipeline) only"
 
 

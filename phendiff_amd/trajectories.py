@@ -11,6 +11,8 @@ no Python launch cost (~120 launches x 2*S per batch otherwise).  Same arithmeti
     position in device memory that the graph's last node advances), so a replay takes no noise input and returns uint8 images;
   * :class:`TiledDDIBGraph` is :class:`DDIBGraph`'s string of phases on a canvas larger than the training size: its UNet phase
     (``_unet``) is ``img2img._TiledForward`` -- gather the tiles, the plan over them, blend -- and its class table has a row per tile.
+  * ``masked.MaskedDDIBGraph`` (its own module) is :class:`DDIBGraph`'s string of phases with an inversion that keeps its states and a
+    ``pd_mask_blend`` after every denoising step (``_ddim_steps``' ``inputs`` / ``after``).
 
 A pipeline whose scheduler is a ``DPMSolverMultistepScheduler`` runs the pixel runners but the tiled and the gradient-guided one: the
 inversion is then ``DPMSolverMultistepInverseScheduler`` (``_schedules`` chooses by the forward scheduler's type), a step is
@@ -257,9 +259,10 @@ class _PixelTrajectory(_TrajectoryRunner):
 
     rows_per_step = property(lambda self: self.B, doc="conditioning rows of one step: one per UNet sample (the images of the batch)")
 
-    def _unet(self, st, temb_ptr, out_ptr):
-        """One UNet evaluation of ``x`` under the row block at ``temb_ptr`` into the canvas-sized tensor at ``out_ptr``."""
-        self.plan.run(self.x.data_ptr(), temb_ptr, out_ptr, st)
+    def _unet(self, st, temb_ptr, out_ptr, x_ptr=None):
+        """One UNet evaluation of ``x`` (``x_ptr``: of another tensor of its shape) under the row block at ``temb_ptr`` into the
+        canvas-sized tensor at ``out_ptr``."""
+        self.plan.run(self.x.data_ptr() if x_ptr is None else x_ptr, temb_ptr, out_ptr, st)
 
     def _image_outputs(self):
         """``.images`` (NHWC float in [0, 1]) and ``.images_u8`` of the whole batch."""
@@ -321,17 +324,19 @@ class _PixelTrajectory(_TrajectoryRunner):
         return None, None, GuidanceRescale(self.model_out, self.uncond[1], w, rescale, guidance_cfg, out=self.model_out,
                                            stream=self.stream.cuda_stream)
 
-    def _ddim_steps(self, st, step_args, first: int = 0, uncond=None, variance=None, rescale=None):
+    def _ddim_steps(self, st, step_args, first: int = 0, uncond=None, variance=None, rescale=None, inputs=None, after=None):
         """Per entry of ``step_args``: the UNet from ``x`` into ``model_out`` under row block ``first + i`` of ``temb``, then its
         ``pd_ddim_step`` (or the launches of its thresholded form, the ones the eager ``step`` enqueues; or, for an entry of
         :meth:`_solver_steps`, its ``pd_multistep_step``: the dispatch is on the argument's type).  ``uncond = (table, out)``: a
         second evaluation under the same row block of another table before the update.  ``rescale``: the
         :class:`~phendiff_amd.schedulers.GuidanceRescale` that turns the two evaluations into the rescaled guided prediction, in place in
         ``model_out``, between them and the update.  ``variance``: per entry the ``pd_stream_noise`` arguments of the step's variance
-        term (stochastic DDIM), launched after the update."""
+        term (stochastic DDIM), launched after the update.  ``inputs``: per entry the pointer of the tensor the UNet reads instead of
+        ``x`` (a trajectory that keeps its states steps from one into the next: the step's own arguments name the same tensor).
+        ``after``: per entry a callable ``(st)`` enqueued last (the masked transfer's blend)."""
         step_bytes = self.rows_per_step * self.plan.w.proj_dim * 4
         for i, a in enumerate(step_args, first):
-            self._unet(st, self.temb.data_ptr() + i * step_bytes, self.model_out.data_ptr())
+            self._unet(st, self.temb.data_ptr() + i * step_bytes, self.model_out.data_ptr(), None if inputs is None else inputs[i - first])
             if uncond is not None:
                 self._unet(st, uncond[0].data_ptr() + i * step_bytes, uncond[1].data_ptr())
             if rescale is not None:
@@ -344,6 +349,8 @@ class _PixelTrajectory(_TrajectoryRunner):
                 L.check(self.lib.pd_ddim_step(C.byref(a), st), "pd_ddim_step")
             if variance is not None:
                 L.check(self.lib.pd_stream_noise(C.byref(variance[i - first]), st), "pd_stream_noise")
+            if after is not None:
+                after[i - first](st)
 
     def _postproc(self, st):
         L.check(self.lib.pd_postproc(C.byref(self.post_args), st), "pd_postproc")
@@ -482,8 +489,8 @@ class TiledDDIBGraph(_PixelTrajectory):
 
     rows_per_step = property(lambda self: self.tiled.T, doc="conditioning rows of one step: one per tile")
 
-    def _unet(self, st, temb_ptr, out_ptr):
-        assert out_ptr == self.model_out.data_ptr(), "the blend writes the model output the runner was bound to"
+    def _unet(self, st, temb_ptr, out_ptr, x_ptr=None):
+        assert out_ptr == self.model_out.data_ptr() and x_ptr is None, "the gather reads the canvas, the blend writes the model output, the runner was bound to"
         self.tiled.evaluate(temb_ptr, st)
 
     def _enqueue(self, st):

@@ -10,6 +10,8 @@ RULES = [
     (r"linear_fold_gn_kernel<", "conv1x1_fold"),             # the per-sample weight fold in front of the pixel q/k/v projection (same plan op as its GEMM)
     (r"gn_finalize", "gn_finalize"),
     (r"temb_kernel", "temb"), (r"ddim_step_kernel", "ddim_step"), (r"postproc_kernel", "postproc"), (r"add_noise_kernel", "add_noise"),
+    # the masked transfer (scripts/bench_masked_ddib.py): pd_class_contrast, both kernels of pd_contrast_mask, pd_mask_blend
+    (r"class_contrast_kernel", "class_contrast"), (r"contrast_mask_(partial|apply)_kernel", "contrast_mask"), (r"mask_blend_kernel", "mask_blend"),
 ]
 
 
