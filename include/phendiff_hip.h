@@ -44,7 +44,8 @@ extern "C" {
  * pd_knn_radii (+ pd_knn_radii_args, pd_knn_radii_workspace), pd_manifold_query (+ pd_manifold_query_args, pd_manifold_query_workspace),
  * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance, pd_multistep_step (+ pd_multistep_step_args), pd_guidance_rescale
  * (+ pd_guidance_rescale_args, pd_guidance_rescale_workspace), pd_class_contrast, pd_contrast_mask, pd_mask_blend (+ their args structs,
- * pd_contrast_mask_workspace). */
+ * pd_contrast_mask_workspace), pd_mask_distance, pd_mask_morph, pd_mask_components, pd_mask_filter (+ their args structs,
+ * pd_mask_morph_workspace, pd_mask_components_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -1002,6 +1003,136 @@ typedef struct {
   float* out;               /* [B][C][per_pixel] (may alias x or keep) */
 } pd_mask_blend_args;
 int pd_mask_blend(const pd_mask_blend_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mask refinement (added under ABI 8; csrc/mask_morph.hip, host side phendiff_amd.mask_ops): disc morphology through an exact
+ * Euclidean distance transform, connected components, hole filling and small-component removal -- the clean-up of a per-pixel contrast
+ * mask.  Every mask is a dense uint8 [B][H][W] tensor, nonzero = set; 1 <= H, W <= PD_MASK_MAX_SIDE, so H^2 + W^2 < 2^30 and every
+ * sum below fits an int32.  A sample's result is a function of that sample alone; nothing is read back by the host; every entry
+ * point is a fixed number of launches for given (B, H, W, parameters): capturable.  All arithmetic is in integers, so the results
+ * are exact whatever the schedule.  INTEGER atomics (min, add, or) are used: their result does not depend on the order (the house
+ * rule "no atomics" is about floating-point sums); floating-point atomics are not.
+ *
+ * pd_mask_distance: d2[s][y][x] = min over the pixels (y', x') of sample s with (mask != 0) == (to_set != 0) of (y - y')^2 + (x - x')^2;
+ * PD_MASK_FAR where the sample holds no such pixel.  Pixels outside the image are neither set nor clear: nothing is padded in.
+ * limit > 0: every value above limit -- the PD_MASK_FAR of a sample without such a pixel included -- is written as limit + 1, and
+ * the row pass looks at most floor(sqrt(limit)) pixels to either side.  limit = 0: no saturation.  Two launches: the column pass (one
+ * thread per (sample, column) scans down, then up, and writes the squared vertical distance into d2) and the row pass (one workgroup
+ * per (sample, row) stages the row of d2 in LDS -- 4 W bytes -- and takes min over dx of dx^2 + g2[x + dx], walking outwards from
+ * dx = 0 until dx^2 reaches the best so far; neighbouring lanes read neighbouring LDS words), which rewrites the row in place.
+ * Refused before any launch: null args / mask / d2, d2 not 4-byte aligned (PD_ERR_ARG); B < 1, H or W outside 1..PD_MASK_MAX_SIDE,
+ * limit outside [0, PD_MASK_FAR) (PD_ERR_SHAPE).
+ *
+ * pd_mask_morph: dilation or erosion by the disc {dy^2 + dx^2 <= r2}, r2 = floor(radius^2) (the host computes it in float64: radius
+ * 1 is the 4-neighbour cross, 1.5 the 3 x 3 square, 2 the 13-pixel disc), by thresholding the distance (limit = r2, so O(radius) per
+ * pixel):   PD_MORPH_DILATE  out = d2 to the nearest set pixel <= r2      PD_MORPH_ERODE  out = mask && d2 to the nearest clear pixel > r2
+ * As the outside of the image is neither set nor clear, an object the image edge cuts is not eroded from the edge and a closing does
+ * not pull the border in: scipy.ndimage.binary_dilation(border_value=0) / binary_erosion(border_value=1) under that element.  out is
+ * 0 / 1 and may NOT alias mask.  Two launches (the column pass into the workspace, the row pass into out).  workspace:
+ * pd_mask_morph_workspace(B, H, W) bytes (int32 [B][H][W]; 0 for sizes the call refuses).  stats (optional): the stats rows of
+ * pd_mask_filter (PD_MASK_STATS_FIELDS words per sample, stats_stride words apart), so that an opening or a closing -- two calls --
+ * fills one row: with PD_MORPH_STATS_IN in stats_mode the first launch zeroes the whole row and the second adds the set pixels of
+ * mask to PD_MS_PIXELS_IN; with PD_MORPH_STATS_OUT the second launch adds the set pixels of out to PD_MS_PIXELS_OUT (integer
+ * atomics).  The other three words stay 0.
+ * Refused before any launch: null args / mask / out / workspace, out aliasing mask (the two byte ranges overlap), workspace or
+ * stats not 4-byte aligned, an op that is not one of the two, a stats_mode outside 0..3 (PD_ERR_ARG); the sizes pd_mask_distance
+ * refuses, r2 outside [0, PD_MASK_FAR), stats with stats_stride < PD_MASK_STATS_FIELDS (PD_ERR_SHAPE).
+ *
+ * pd_mask_components: connected components of one phase (phase = 1: the set pixels, 0: the clear pixels) under connectivity 4 or 8.
+ * Outputs (each optional, at least one of the first four required):
+ *     label  int32 [B][H][W]   1 + the smallest within-sample linear index y * W + x among the component's pixels; 0 on the other phase
+ *     area   int32 [B][H][W]   the pixel count of the pixel's component; 0 on the other phase
+ *     border uint8 [B][H][W]   1 where the pixel's component touches row 0, row H - 1, column 0 or column W - 1; 0 on the other phase
+ *     count  int32 [B]         the number of components
+ *     status int32 [B]         0; nonzero where a device loop met its hard cap (see below) -- the sample's outputs are then unusable
+ * Label-equivalence union-find in global memory (Komura 2015; Playne & Hawick 2018; the pointer jumping of Jaiganesh & Burtscher's
+ * ECL-CC, 2018), four launches: init (parent[i] = i), merge (a pixel unions with its W and N neighbours, under 8-connectivity also NW
+ * and NE, where they share its phase; a pixel at a row's end is no neighbour of the next row's first pixel, a sample's last row none
+ * of the next sample's first), flatten (parent[i] = find(i), and at the root an integer atomicAdd for the area and atomicOr for the
+ * border flag), broadcast.  parent[i] <= i always and only ever decreases, so the smallest index of a component ends as its root.
+ * TERMINATION: find follows parents strictly smaller than the node and ends at a fixed point; union retries only after another
+ * thread's atomicMin lowered the root it was about to link, and the larger of its two roots strictly decreases with every retry.
+ * Both loops also carry a hard cap of H * W iterations; a loop that meets it stops and sets the sample's status word.  Reads of parent
+ * that race with atomicMin are relaxed atomic loads.
+ * workspace: pd_mask_components_workspace(B, H, W) bytes (two int32 [B][H * W]: parent, and area + border flag at the roots).
+ * Refused before any launch: null args / mask / workspace, no output at all, pointers not aligned to their element (PD_ERR_ARG);
+ * the sizes pd_mask_distance refuses, connectivity not 4 or 8, phase not 0 or 1 (PD_ERR_SHAPE).
+ *
+ * pd_mask_filter: elementwise over mask and the label / area / border of one labelled phase:
+ *     PD_FILTER_DROP_SMALL (phase 1)  out = mask && area >= area_limit                          (clears components below min_area)
+ *     PD_FILTER_FILL_HOLES (phase 0)  out = mask || (clear && !border && (area_limit < 0 || area <= area_limit))
+ * A hole is a component of clear pixels that does not touch the image border; holes are labelled with the connectivity dual to the
+ * foreground's (foreground 8: holes 4, foreground 4: holes 8 -- what scipy.ndimage.binary_fill_holes implies).  out is 0 / 1 and may
+ * alias mask.  stats (optional) int32, PD_MASK_STATS_FIELDS words per sample, stats_stride words apart: pixels in, pixels out,
+ * components seen (pixels with label = index + 1), components kept (DROP_SMALL) or filled (FILL_HOLES), status (copied from
+ * `status`, the word pd_mask_components wrote; 0 where status is NULL).  Two launches: the stats rows are initialised, then one
+ * workgroup per (sample, 1024 pixels) writes out and adds its four counts with integer atomics.
+ * Refused before any launch: null args / mask / label / area / border / out, pointers not aligned to their element, a rule that is
+ * not one of the two (PD_ERR_ARG); the sizes pd_mask_distance refuses, DROP_SMALL with area_limit < 0, stats with stats_stride <
+ * PD_MASK_STATS_FIELDS (PD_ERR_SHAPE). */
+#define PD_MASK_FAR 1073741824
+#define PD_MASK_MAX_SIDE 16384
+#define PD_MASK_STATS_FIELDS 5
+enum { PD_MORPH_DILATE = 0, PD_MORPH_ERODE = 1 };
+enum { PD_MORPH_STATS_IN = 1, PD_MORPH_STATS_OUT = 2 };
+enum { PD_FILTER_DROP_SMALL = 0, PD_FILTER_FILL_HOLES = 1 };
+enum { PD_MS_PIXELS_IN = 0, PD_MS_PIXELS_OUT = 1, PD_MS_COMPONENTS = 2, PD_MS_SELECTED = 3, PD_MS_STATUS = 4 };
+typedef struct {
+  int64_t B;
+  int H, W;                 /* 1..PD_MASK_MAX_SIDE */
+  const uint8_t* mask;      /* [B][H][W] */
+  int to_set;               /* nonzero: distance to the nearest set pixel; 0: to the nearest clear pixel */
+  int limit;                /* 0: exact everywhere; > 0: values above limit are written as limit + 1 */
+  int32_t* d2;              /* [B][H][W] */
+} pd_mask_distance_args;
+int pd_mask_distance(const pd_mask_distance_args* a, void* stream);
+
+typedef struct {
+  int64_t B;
+  int H, W;
+  const uint8_t* mask;      /* [B][H][W] */
+  int op;                   /* PD_MORPH_DILATE / PD_MORPH_ERODE */
+  int r2;                   /* floor(radius^2) */
+  uint8_t* out;             /* [B][H][W]: 0 / 1; may not alias mask */
+  void* workspace;          /* pd_mask_morph_workspace(B, H, W) bytes */
+  int32_t* stats;           /* [B] rows of PD_MASK_STATS_FIELDS words, stats_stride words apart; or NULL */
+  int64_t stats_stride;
+  int stats_mode;           /* PD_MORPH_STATS_IN | PD_MORPH_STATS_OUT */
+} pd_mask_morph_args;
+size_t pd_mask_morph_workspace(int64_t B, int H, int W);
+int pd_mask_morph(const pd_mask_morph_args* a, void* stream);
+
+typedef struct {
+  int64_t B;
+  int H, W;
+  const uint8_t* mask;      /* [B][H][W] */
+  int phase;                /* 1: label the set pixels; 0: the clear pixels */
+  int connectivity;         /* 4 or 8 */
+  int32_t* label;           /* [B][H][W] or NULL */
+  int32_t* area;            /* [B][H][W] or NULL */
+  uint8_t* border;          /* [B][H][W] or NULL */
+  int32_t* count;           /* [B] or NULL */
+  int32_t* status;          /* [B] or NULL */
+  void* workspace;          /* pd_mask_components_workspace(B, H, W) bytes */
+} pd_mask_components_args;
+size_t pd_mask_components_workspace(int64_t B, int H, int W);
+int pd_mask_components(const pd_mask_components_args* a, void* stream);
+
+typedef struct {
+  int64_t B;
+  int H, W;
+  const uint8_t* mask;      /* [B][H][W] */
+  const int32_t* label;     /* [B][H][W]: of the phase the rule reads (DROP_SMALL: 1, FILL_HOLES: 0) */
+  const int32_t* area;      /* [B][H][W] */
+  const uint8_t* border;    /* [B][H][W] */
+  const int32_t* status;    /* [B] or NULL */
+  int rule;                 /* PD_FILTER_DROP_SMALL / PD_FILTER_FILL_HOLES */
+  int area_limit;           /* DROP_SMALL: min_area >= 0; FILL_HOLES: max_area, < 0 = any size */
+  uint8_t* out;             /* [B][H][W]: 0 / 1; may alias mask */
+  int32_t* stats;           /* [B] rows of PD_MASK_STATS_FIELDS words, stats_stride words apart; or NULL */
+  int64_t stats_stride;
+} pd_mask_filter_args;
+int pd_mask_filter(const pd_mask_filter_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Tiled trajectories (added under ABI 8; csrc/tile_kernels.hip, host side phendiff_amd.tiling): the working sample is a canvas

@@ -20,6 +20,9 @@ from .trajectories import DDIBGraph, CFGForwardStartGraph, SDDDIBGraph, GuidedTr
 from .trajectories import GenerationGraph  # noqa: F401
 from .masked import (class_contrast_mask, mask_blend, masked_ddib, MaskedDDIBGraph, MaskedTransferOutput, blend_state_index,  # noqa: F401
                      encode_timestep, check_mask, ContrastMask)
+from . import mask_ops  # noqa: F401
+from .mask_ops import (mask_distance, mask_dilate, mask_erode, mask_open, mask_close, mask_components, remove_small_components,  # noqa: F401
+                       fill_holes, MaskRefine, refine_mask, disc_r2)
 from .tiling import TileGrid  # noqa: F401
 from . import tiling  # noqa: F401
 from .configs import UNET_CONFIGS, SCHEDULER_CONFIGS, SD15_UNET_CONFIG  # noqa: F401

@@ -12,10 +12,16 @@
 The mean of a map is taken PER SAMPLE (diffusers takes ``.mean()`` over the whole batch; equal at B = 1): a sample's mask is a function of
 that sample alone, like everything else here.
 
+``refine=dict(...)`` (the parameters of :class:`~phendiff_amd.mask_ops.MaskRefine`: ``close``, ``open``, ``fill_holes``, ``min_area``,
+``dilate``, ``connectivity``) cleans the mask up on the device before it is used: a per-pixel contrast mask is a thresholded noise
+difference, with specks on the background, pin-holes inside cells and ragged outlines.  ``.mask`` is then the refined mask, ``.raw_mask``
+what the refinement read and ``.refine_stats`` its stats; with ``refine=None`` the launches are exactly those without it.
+
 Out of scope: the latent tier, the tiled and the gradient-guided transfers, classifier-free guidance during the masked generation, soft
-masks, morphological clean-up of the mask.  Refused before anything is packed or launched: ``DPMSolverMultistep*`` schedulers
+(fractional) masks and feathered blends.  Refused before anything is packed or launched: ``DPMSolverMultistep*`` schedulers
 (:data:`~phendiff_amd.schedulers.MULTISTEP_NOT_MASKED`), the latent-diffusion pipeline, batches beyond ``unet.max_batch`` (no sliced form), a
-mask of the wrong shape, dtype or device, ``num_maps < 1``, ``threshold_ratio <= 0``.
+mask of the wrong shape, dtype or device, ``num_maps < 1``, ``threshold_ratio <= 0``, ``refine`` parameters ``MaskRefine.check_params``
+refuses.
 """
 from __future__ import annotations
 
@@ -26,6 +32,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib as L
+from .mask_ops import MaskRefine
 from .noise import DeviceNoise
 from .pipeline import ConditionalDDIMPipeline, numpy_to_pil, require_pil_channels
 from .schedulers import MULTISTEP_NOT_MASKED, randn_tensor, refuse_multistep
@@ -80,6 +87,18 @@ def _check_map_request(num_maps, threshold_ratio, who: str):
     if not (math.isfinite(ratio) and ratio > 0.0):
         raise ValueError(f"{who}: threshold_ratio must be a finite positive number, got {threshold_ratio!r}")
     return ratio
+
+
+def _check_refine_request(refine, who: str):
+    """``refine`` as the normalised parameters of :class:`MaskRefine` (``None`` stays ``None``); a ``ValueError`` names the entry point."""
+    if refine is None:
+        return None
+    if not isinstance(refine, dict):
+        raise ValueError(f"{who}: refine must be a dict of MaskRefine parameters or None, got {type(refine).__name__}")
+    try:
+        return MaskRefine.check_params(**refine)
+    except ValueError as e:
+        raise ValueError(f"{who}: refine: {e}") from None
 
 
 def _check_masked_request(pipe, shape, who: str):
@@ -187,7 +206,7 @@ def mask_blend(x: torch.Tensor, keep: torch.Tensor, mask: torch.Tensor, out: tor
 @torch.no_grad()
 def class_contrast_mask(pipe, images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor,
                         num_inference_steps: int = 50, num_maps: int = 10, encode_strength: float = 0.5, threshold_ratio: float = 3.0,
-                        generator=None) -> SimpleNamespace:
+                        generator=None, refine: dict = None) -> SimpleNamespace:
     """Where the model's noise prediction under ``target_class_labels`` differs from the one under ``orig_class_labels`` (DiffEdit's mask;
     diffusers' ``generate_mask``).  Returns a namespace: ``.mask`` (B, 1, H, W) uint8 and ``.map`` (B, 1, H, W) fp32 in [0, 1] on the
     device, ``.stats`` (B, 3) -- per sample the mean of the accumulated contrast, ``threshold_ratio`` times it, and the masked fraction --
@@ -197,11 +216,16 @@ def class_contrast_mask(pipe, images: torch.Tensor, orig_class_labels: torch.Ten
     with the forward-noise purpose at element ``k * C * H * W`` of each image's own stream, so image ``j``'s noise is a function of
     ``(seed, index + j, k)`` alone; from a ``torch.Generator`` (or none) with ``randn_tensor``.  Then two UNet evaluations (target class,
     source class) and one ``pd_class_contrast``; after the last draw one ``pd_contrast_mask``.  The mean is per sample (see the module's
-    note).  The ``DeviceNoise`` position is not advanced: draws never do."""
+    note).  The ``DeviceNoise`` position is not advanced: draws never do.
+
+    ``refine`` (a dict of :class:`~phendiff_amd.mask_ops.MaskRefine` parameters): the recipe's launches follow ``pd_contrast_mask``;
+    ``.mask`` is the refined mask, ``.raw_mask`` the thresholded one and ``.refine_stats`` the recipe's (B, stages, 5) int32 stats (both
+    ``None`` without ``refine``; ``.map`` and ``.stats`` always describe the raw mask)."""
     who = "class_contrast_mask"
     shape = tuple(images.shape) if torch.is_tensor(images) else ()
     _check_masked_request(pipe, shape, who)
     ratio = _check_map_request(num_maps, threshold_ratio, who)
+    refine = _check_refine_request(refine, who)
     t = encode_timestep(pipe.scheduler, num_inference_steps, encode_strength)
     _require_cuda(images, who)
     x = images.detach().to(torch.float32).contiguous()
@@ -219,18 +243,23 @@ def class_contrast_mask(pipe, images: torch.Tensor, orig_class_labels: torch.Ten
         L.check(L.lib().pd_class_contrast(C.byref(class_contrast_args(eps_target, eps_source, acc, k == 0)), st), "pd_class_contrast")
     cm = ContrastMask(acc, ratio)
     cm.enqueue(st)
-    return SimpleNamespace(mask=cm.mask, map=cm.map, stats=cm.stats, timestep=t)
+    if refine is None:
+        return SimpleNamespace(mask=cm.mask, map=cm.map, stats=cm.stats, timestep=t, raw_mask=None, refine_stats=None)
+    r = MaskRefine(B, H, W, x.device, **refine).enqueue(st, cm.mask)
+    return SimpleNamespace(mask=r.mask, map=cm.map, stats=cm.stats, timestep=t, raw_mask=cm.mask, refine_stats=r.stats)
 
 
 # ---- the eager transfer ------------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def masked_ddib(pipe, clean_images: torch.Tensor, orig_class_labels: torch.Tensor, target_class_labels: torch.Tensor,
                 num_inference_steps: int, mask: torch.Tensor = None, variant: str = "0.18.2", output_type: str = "numpy",
-                **mask_kw) -> MaskedTransferOutput:
+                refine: dict = None, **mask_kw) -> MaskedTransferOutput:
     """:func:`~phendiff_amd.img2img.ddib` that changes the image inside ``mask`` only -- the eager form (the reference-style Python loops
     over the inverse scheduler's and the forward scheduler's ``step``).  ``mask``: (B, 1, H, W) or (B, H, W), bool or uint8, on the images'
     device; ``None`` computes it first with :func:`class_contrast_mask` (``**mask_kw``: ``num_maps``, ``encode_strength``,
-    ``threshold_ratio``, ``generator``).
+    ``threshold_ratio``, ``generator``).  ``refine`` (a dict of :class:`~phendiff_amd.mask_ops.MaskRefine` parameters) cleans the mask up
+    -- the computed one or the given one -- before the inversion: the blend reads the refined mask, ``.mask`` is the refined mask,
+    ``.raw_mask`` what the refinement read and ``.refine_stats`` its stats (both ``None`` without ``refine``).
 
     The inversion keeps its states: ``traj[0]`` is the input and ``traj[i]`` the state after ``i`` inverse steps, (S + 1, B, C, H, W)
     fp32 -- ``4 (S + 1) B C H W`` bytes, 1.3 GB at batch 32, S = 50, 3 x 256 x 256.  Generation starts from ``traj[S]``; after forward
@@ -253,7 +282,8 @@ def masked_ddib(pipe, clean_images: torch.Tensor, orig_class_labels: torch.Tenso
     require_pil_channels(shape[1], output_type)
     S = int(num_inference_steps)
     B, Cc, H, W = shape
-    info = None
+    info = raw_mask = refine_stats = None
+    refine = _check_refine_request(refine, who)
     if mask is None:
         _check_map_request(mask_kw.get("num_maps", 10), mask_kw.get("threshold_ratio", 3.0), who)
     else:
@@ -263,9 +293,13 @@ def masked_ddib(pipe, clean_images: torch.Tensor, orig_class_labels: torch.Tenso
     inv, fwd, inv_ts, gen_ts = _transfer_schedules(pipe, S, variant, who)
     _require_cuda(clean_images, who)
     if mask is None:
-        info = class_contrast_mask(pipe, clean_images, orig_class_labels, target_class_labels, S, **mask_kw)
+        info = class_contrast_mask(pipe, clean_images, orig_class_labels, target_class_labels, S, refine=refine, **mask_kw)
         mask = info.mask      # (it set the forward scheduler to the same S steps: the grid above stands)
+        raw_mask, refine_stats = info.raw_mask, info.refine_stats
     mask = _as_bytes(mask)
+    if refine is not None and info is None:      # a given mask: refined here, before the inversion
+        r = MaskRefine(B, H, W, mask.device, **refine).enqueue(torch.cuda.current_stream(mask.device).cuda_stream, mask)
+        raw_mask, mask, refine_stats = mask.view(B, 1, H, W), r.mask, r.stats
     traj = torch.empty((S + 1, B, Cc, H, W), dtype=torch.float32, device=clean_images.device)
     traj[0].copy_(clean_images)
     for i, t in enumerate(inv_ts):
@@ -284,7 +318,8 @@ def masked_ddib(pipe, clean_images: torch.Tensor, orig_class_labels: torch.Tenso
         if output_type == "pil":
             images = numpy_to_pil(images)
     return MaskedTransferOutput(images=images, mask=mask.view(B, 1, H, W), inverted=traj[S], sample=x,
-                                map=None if info is None else info.map, stats=None if info is None else info.stats)
+                                map=None if info is None else info.map, stats=None if info is None else info.stats, raw_mask=raw_mask,
+                                refine_stats=refine_stats)
 
 
 def _transfer_schedules(pipe, S: int, variant: str, who: str):
@@ -307,6 +342,9 @@ class MaskedDDIBGraph(_PixelTrajectory):
         buffer, the UNet under the target and under the source class, ``pd_class_contrast``; then ``pd_contrast_mask``.  What
         :func:`class_contrast_mask` ``(generator=noise)`` launches.  The graph's last node is ``pd_stream_advance(batch_size)``.
       * ``mask="given"``: ``run(..., mask=...)`` copies the mask into a static buffer.
+      * ``refine=dict(...)``: the launches of :class:`~phendiff_amd.mask_ops.MaskRefine` close the mask phase, inside the graph, over the
+        contrast mask or the given one; ``.mask`` is the refined mask (what every blend reads), ``.raw_mask`` what the refinement read,
+        ``.refine_stats`` its stats.  ``refine=None``: no launch is added, ``.raw_mask`` and ``.refine_stats`` are ``None``.
       * The inversion WITHOUT snapshots: inverse step ``i`` has the UNet read ``traj[i]`` and ``pd_ddim_step`` write ``traj[i + 1]`` --
         exactly the launches of ``DDIBGraph``'s inversion, on other pointers; ``.inverted`` is ``traj[S]``.  ``traj``:
         (S + 1, B, C, H, W) fp32, ``4 (S + 1) B C H W`` bytes.
@@ -321,7 +359,8 @@ class MaskedDDIBGraph(_PixelTrajectory):
 
     def __init__(self, pipe: ConditionalDDIMPipeline, batch_size: int, num_inference_steps: int, height: int = None, width: int = None,
                  variant: str = "0.18.2", mask: str = "contrast", noise: DeviceNoise = None, num_maps: int = 10,
-                 encode_strength: float = 0.5, threshold_ratio: float = 3.0, use_graph: bool = True, private_plan: bool = False):
+                 encode_strength: float = 0.5, threshold_ratio: float = 3.0, use_graph: bool = True, private_plan: bool = False,
+                 refine: dict = None):
         who = "MaskedDDIBGraph"
         unet = getattr(pipe, "unet", None)
         channels = getattr(getattr(unet, "config", None), "in_channels", 0)
@@ -330,6 +369,7 @@ class MaskedDDIBGraph(_PixelTrajectory):
         if mask not in ("contrast", "given"):
             raise ValueError(f'{who}: mask must be "contrast" or "given", got {mask!r}')
         S = int(num_inference_steps)
+        refine = _check_refine_request(refine, who)
         self.mask_mode, self.noise, self.t_enc = mask, noise, None
         if mask == "contrast":
             ratio = _check_map_request(num_maps, threshold_ratio, who)
@@ -363,6 +403,11 @@ class MaskedDDIBGraph(_PixelTrajectory):
         else:
             self.mask = torch.zeros((B, 1, self.H, self.W), dtype=torch.uint8, device=dev)
             self.map = self.stats = None
+        self._mask_in = self.mask      # where pd_contrast_mask writes, or run() copies, the mask
+        self.refine, self.raw_mask, self.refine_stats = None, None, None
+        if refine is not None:
+            self.refine = MaskRefine(B, self.H, self.W, dev, **refine)
+            self.raw_mask, self.mask, self.refine_stats = self._mask_in, self.refine.mask, self.refine.stats
         self.inv_args = [inv.ddim_step_args(t, self.traj[i], self.model_out, self.traj[i + 1]) for i, t in enumerate(inv_ts)]
         self.inv_inputs = [self.traj[i].data_ptr() for i in range(S)]
         self.gen_args = [self._forward_step_args(fwd, t) for t in gen_ts]
@@ -373,7 +418,7 @@ class MaskedDDIBGraph(_PixelTrajectory):
     def _mask_phase(self, st):
         """Per draw: the images noised to the encode level into ``x``, the UNet under the target class (row block ``k``) into
         ``model_out`` and under the source class (row block ``num_maps + k``) into ``source_out``, their contrast into ``acc``; then the
-        mask."""
+        mask (``mask="given"``: none of these) and, with ``refine``, the recipe over it."""
         step_bytes = self.rows_per_step * self.plan.w.proj_dim * 4
         M = self.n_mask // 2
         for k in range(M):
@@ -381,11 +426,14 @@ class MaskedDDIBGraph(_PixelTrajectory):
             self._unet(st, self.temb.data_ptr() + k * step_bytes, self.model_out.data_ptr())
             self._unet(st, self.temb.data_ptr() + (M + k) * step_bytes, self.source_out.data_ptr())
             L.check(self.lib.pd_class_contrast(C.byref(self.contrast_args[k]), st), "pd_class_contrast")
-        self.contrast.enqueue(st)
+        if M:
+            self.contrast.enqueue(st)
+        if self.refine is not None:
+            self.refine.enqueue(st, self._mask_in)
 
     def _enqueue(self, st):
         self.class_rows.temb(self.ts_rows, st, self.temb)
-        if self.mask_mode == "contrast":
+        if self.mask_mode == "contrast" or self.refine is not None:
             self._mask_phase(st)
         self._ddim_steps(st, self.inv_args, first=self.n_mask, inputs=self.inv_inputs)
         self.x.copy_(self.traj[self.S])      # generation works in place in x; every state of the inversion stays for the blends
@@ -398,7 +446,7 @@ class MaskedDDIBGraph(_PixelTrajectory):
         B, M, n_inv, n_gen = self.B, self.n_mask // 2, len(self.inv_ts), len(self.gen_ts)
         self.traj[0].copy_(clean_images, non_blocking=True)
         if mask is not None:
-            self.mask.copy_(mask, non_blocking=True)
+            self._mask_in.copy_(mask, non_blocking=True)
         if M:
             self.class_rows.fill(slice(0, M * B), M, B, target_class_labels)
             self.class_rows.fill(slice(M * B, 2 * M * B), M, B, orig_class_labels)

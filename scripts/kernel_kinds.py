@@ -12,6 +12,10 @@ RULES = [
     (r"temb_kernel", "temb"), (r"ddim_step_kernel", "ddim_step"), (r"postproc_kernel", "postproc"), (r"add_noise_kernel", "add_noise"),
     # the masked transfer (scripts/bench_masked_ddib.py): pd_class_contrast, both kernels of pd_contrast_mask, pd_mask_blend
     (r"class_contrast_kernel", "class_contrast"), (r"contrast_mask_(partial|apply)_kernel", "contrast_mask"), (r"mask_blend_kernel", "mask_blend"),
+    # the mask refinement (scripts/bench_mask_refine.py): both passes of pd_mask_distance / pd_mask_morph, the four kernels of
+    # pd_mask_components, both kernels of pd_mask_filter
+    (r"mask_(column|row)_kernel", "mask_distance"), (r"comp_(init|merge|flatten|broadcast)_kernel", "mask_components"),
+    (r"filter_(init_)?kernel", "mask_filter"),
 ]
 
 
