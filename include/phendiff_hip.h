@@ -45,7 +45,8 @@ extern "C" {
  * pd_stream_noise (+ pd_stream_noise_args), pd_stream_advance, pd_multistep_step (+ pd_multistep_step_args), pd_guidance_rescale
  * (+ pd_guidance_rescale_args, pd_guidance_rescale_workspace), pd_class_contrast, pd_contrast_mask, pd_mask_blend (+ their args structs,
  * pd_contrast_mask_workspace), pd_mask_distance, pd_mask_morph, pd_mask_components, pd_mask_filter (+ their args structs,
- * pd_mask_morph_workspace, pd_mask_components_workspace). */
+ * pd_mask_morph_workspace, pd_mask_components_workspace), pd_object_index, pd_object_geometry, pd_object_intensity (+ their args structs,
+ * pd_object_index_workspace). */
 #define PD_ABI_VERSION 8
 
 typedef enum { PD_OK = 0, PD_ERR_ARG = -1, PD_ERR_SHAPE = -2, PD_ERR_LAUNCH = -3, PD_ERR_UNSUPPORTED = -4 } pd_status;
@@ -1133,6 +1134,104 @@ typedef struct {
   int64_t stats_stride;
 } pd_mask_filter_args;
 int pd_mask_filter(const pd_mask_filter_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-object measurements (added under ABI 8: three entry points, no existing struct changes; csrc/object_stats.hip, host side
+ * phendiff_amd.objects): from the sparse labels of pd_mask_components to one table row per object -- dense labels, integer geometry,
+ * intensity sums of an image stack under the labels.  Sizes as for the masks: 1 <= H, W <= PD_MASK_MAX_SIDE, so a sample has at most
+ * 2^28 pixels.  K = max_objects (1..2^28) is the number of table rows per sample.  The house rules of the mask section hold: integers
+ * are exact (INTEGER atomics only: 64-bit add / min / max / or, whose result has no order), floating-point sums are fp64 in a fixed
+ * order with no floating-point atomic anywhere, a sample's result is a function of that sample alone, nothing is read back by the
+ * host, and every entry point is a fixed number of launches for given (B, H, W, K, C): capturable.  No device loop is unbounded: every
+ * trip count is fixed by the sizes (or, in pd_object_intensity, by a bounding box clamped to the image).
+ *
+ * pd_object_index: label (int32 [B][H][W] as pd_mask_components writes it: 1 + the smallest within-sample linear index of the pixel's
+ * component, 0 on the other phase) -> dense labels.  A ROOT is a pixel with label == y * W + x + 1.
+ *     index  int32 [B][H][W]   0 on the other phase; else k in 1..count, the rank of the component's root in raster order among the
+ *                              sample's roots -- the numbering scipy.ndimage.label gives.  Components of rank > K get index 0
+ *     count  int32 [B]         the TRUE number of components (roots), also where it exceeds K
+ *     status int32 [B]         PD_OBJ_OVERFLOW where count > K (components 1..K stay correct); PD_OBJ_BAD_LABEL where a nonzero label lies
+ *                              outside 1..H * W or names a pixel that is no root (such a pixel gets index 0; nothing is read out of
+ *                              bounds); PD_OBJ_LABEL_STATUS where label_status[s] != 0 (optional input: the status word of
+ *                              pd_mask_components, so that one word tells whether the sample's table can be used)
+ * A per-sample exclusive prefix sum of the root flags in four launches: per tile of 1024 pixels the number of roots; per sample the
+ * exclusive scan of its tile counts (256 at a time with a carry: ceil(tiles / 256) steps) and count / status; per tile again the rank
+ * 1 + offset + (roots before the pixel in the tile) written at every pixel of the workspace (0 where the pixel is no root); the gather
+ * index = rank[label - 1].  Integer adds in a fixed order.  workspace: pd_object_index_workspace(B, H, W) bytes (int32 [B][H * W]
+ * ranks, then int32 [B][ceil(H * W / 1024)] tile offsets; 0 for sizes the call refuses).  index may alias label.
+ * Refused before any launch: null args / label / index / count / status / workspace, pointers not 4-byte aligned (PD_ERR_ARG); B < 1,
+ * H or W outside 1..PD_MASK_MAX_SIDE, max_objects outside 1..2^28 (PD_ERR_SHAPE).
+ *
+ * pd_object_geometry: index -> geometry, int64 [B][K][PD_OBJ_GEOM_FIELDS], row k - 1 for index k (an index outside 0..K is read as 0):
+ *     PD_OG_AREA  PD_OG_Y0 PD_OG_Y1 PD_OG_X0 PD_OG_X1 (the bounding box, inclusive)  PD_OG_SUM_Y PD_OG_SUM_X PD_OG_SUM_YY PD_OG_SUM_XX
+ *     PD_OG_SUM_YX (raw moments of the pixel coordinates)  PD_OG_EDGES  PD_OG_BORDER
+ * edges: the number of unit pixel edges between the object and anything that is not that object -- per pixel, the 4-neighbours whose
+ * index differs, the outside of the image included (an a x b rectangle: 2 (a + b)).  border: 1 if the object has a pixel in row 0,
+ * row H - 1, column 0 or column W - 1.  Rows without an object (k > min(count, K)) are all zero.  Every sum fits: area <= 2^28,
+ * y, x < 2^14, so sum_yy, sum_xx, sum_yx < 2^28 * 2^28 = 2^56.
+ * Three launches: every word initialised (0; the two minima to INT64_MAX); one wave per (sample, row, 64 columns): the lanes of a RUN
+ * of equal index are combined before any atomic -- a run is contiguous in one row, so its length comes from one ballot, its x sums
+ * from closed forms, its edges from a segmented wave sum -- and the run's first lane issues the row's 64-bit integer atomics (7 adds,
+ * 2 min, 2 max, at most one or); then the minima of empty rows are set to 0.
+ * Refused before any launch: null args / index / geometry, index not 4-byte or geometry not 8-byte aligned (PD_ERR_ARG); the sizes
+ * pd_object_index refuses (PD_ERR_SHAPE).
+ *
+ * pd_object_intensity: images (dense NCHW [B][C][H][W]; PD_OBJ_F32, PD_OBJ_U8 or PD_OBJ_U16 -- every value converts to double exactly)
+ * under index -> out, double [B][K][C][PD_OBJ_INTENSITY_FIELDS]: PD_OI_SUM, PD_OI_SUMSQ (squares formed in fp64: exact for all three
+ * types), PD_OI_MIN, PD_OI_MAX over the object's pixels, per channel.  One launch, one workgroup per (sample, table row, channel): it
+ * reads the row's area and bounding box from `geometry` (area <= 0: writes four zeros and exits; the box is clamped to the image, so a
+ * table that is not pd_object_geometry's cannot send a read out of bounds), walks the box in raster order -- thread t takes positions
+ * t, t + 256, ... -- SELECTS the pixels whose index equals k (nothing is multiplied by zero: a NaN outside the object cannot reach it),
+ * adds them in that order and reduces the 256 partial results in a fixed tree (wave butterfly, then the four waves in order).  The
+ * result is a function of the object's box, its pixels and their values alone: bitwise reproducible, independent of the batch, the
+ * schedule and the other objects.  A NaN inside an object reaches that object's row only (sum and sumsq by arithmetic; min and max
+ * are both NaN then).  COST: C * (sum over the objects of their box area) pixel reads -- about the objects' area for compact cells, at
+ * most K * H * W * C (objects whose boxes are the whole image).
+ * Refused before any launch: null args / index / geometry / images / out, pointers not aligned to their element (PD_ERR_ARG); the
+ * sizes pd_object_index refuses, C < 1, B * K * C above 2^31 - 1 workgroups, a dtype that is not one of the three (PD_ERR_SHAPE). */
+#define PD_OBJ_GEOM_FIELDS 12
+#define PD_OBJ_INTENSITY_FIELDS 4
+#define PD_OBJ_MAX_OBJECTS 268435456
+enum { PD_OBJ_OVERFLOW = 1, PD_OBJ_BAD_LABEL = 2, PD_OBJ_LABEL_STATUS = 4 };
+enum { PD_OBJ_F32 = 0, PD_OBJ_U8 = 1, PD_OBJ_U16 = 2 };
+enum { PD_OG_AREA = 0, PD_OG_Y0 = 1, PD_OG_Y1 = 2, PD_OG_X0 = 3, PD_OG_X1 = 4, PD_OG_SUM_Y = 5, PD_OG_SUM_X = 6, PD_OG_SUM_YY = 7,
+       PD_OG_SUM_XX = 8, PD_OG_SUM_YX = 9, PD_OG_EDGES = 10, PD_OG_BORDER = 11 };
+enum { PD_OI_SUM = 0, PD_OI_SUMSQ = 1, PD_OI_MIN = 2, PD_OI_MAX = 3 };
+typedef struct {
+  int64_t B;
+  int H, W;                     /* 1..PD_MASK_MAX_SIDE */
+  int max_objects;              /* K: 1..PD_OBJ_MAX_OBJECTS */
+  const int32_t* label;         /* [B][H][W] */
+  const int32_t* label_status;  /* [B] or NULL */
+  int32_t* index;               /* [B][H][W] (may alias label) */
+  int32_t* count;               /* [B] */
+  int32_t* status;              /* [B] */
+  void* workspace;              /* pd_object_index_workspace(B, H, W) bytes */
+} pd_object_index_args;
+size_t pd_object_index_workspace(int64_t B, int H, int W);
+int pd_object_index(const pd_object_index_args* a, void* stream);
+
+typedef struct {
+  int64_t B;
+  int H, W;
+  int max_objects;              /* K */
+  const int32_t* index;         /* [B][H][W] */
+  int64_t* geometry;            /* [B][K][PD_OBJ_GEOM_FIELDS] */
+} pd_object_geometry_args;
+int pd_object_geometry(const pd_object_geometry_args* a, void* stream);
+
+typedef struct {
+  int64_t B;
+  int H, W;
+  int max_objects;              /* K */
+  int C;                        /* channels, >= 1 */
+  int dtype;                    /* PD_OBJ_F32 / PD_OBJ_U8 / PD_OBJ_U16 */
+  const int32_t* index;         /* [B][H][W] */
+  const int64_t* geometry;      /* [B][K][PD_OBJ_GEOM_FIELDS]: area and bounding box are read */
+  const void* images;           /* [B][C][H][W] */
+  double* out;                  /* [B][K][C][PD_OBJ_INTENSITY_FIELDS] */
+} pd_object_intensity_args;
+int pd_object_intensity(const pd_object_intensity_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Tiled trajectories (added under ABI 8; csrc/tile_kernels.hip, host side phendiff_amd.tiling): the working sample is a canvas

@@ -23,6 +23,8 @@ from .masked import (class_contrast_mask, mask_blend, masked_ddib, MaskedDDIBGra
 from . import mask_ops  # noqa: F401
 from .mask_ops import (mask_distance, mask_dilate, mask_erode, mask_open, mask_close, mask_components, remove_small_components,  # noqa: F401
                        fill_holes, MaskRefine, refine_mask, disc_r2)
+from . import objects  # noqa: F401
+from .objects import label_objects, measure_intensity, ObjectMeasure, ObjectLabels, object_change, measure_transfer  # noqa: F401
 from .tiling import TileGrid  # noqa: F401
 from . import tiling  # noqa: F401
 from .configs import UNET_CONFIGS, SCHEDULER_CONFIGS, SD15_UNET_CONFIG  # noqa: F401

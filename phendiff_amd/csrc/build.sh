@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 if [ "$1" = "--clean" ]; then rm -rf "$HERE/build"; rm -f "$OUT" "$OUT.manifest.json"; fi
 mkdir -p "$HERE/build"
 pids=()
-SRCS="conv_igemm attn_d8 small_kernels train_kernels backward_kernels wgrad sd_kernels attn_hd attn_hd_bwd vae_kernels sd_bwd_kernels linear_gemm linear_p8 metric_kernels data_kernels data16_kernels sample_kernels stream_noise sample_stats ssim metric_stats manifold_stats guided_kernels threshold_kernels multistep_kernels guidance_rescale mask_kernels mask_morph tile_kernels comm_rccl"
+SRCS="conv_igemm attn_d8 small_kernels train_kernels backward_kernels wgrad sd_kernels attn_hd attn_hd_bwd vae_kernels sd_bwd_kernels linear_gemm linear_p8 metric_kernels data_kernels data16_kernels sample_kernels stream_noise sample_stats ssim metric_stats manifold_stats guided_kernels threshold_kernels multistep_kernels guidance_rescale mask_kernels mask_morph object_stats tile_kernels comm_rccl"
 for f in $SRCS; do
   X=""
   # attention (forward d = 8, backward d = 64, forward and backward of the templated head dimensions): keep MFMA accumulators in VGPRs (the softmax / its derivative

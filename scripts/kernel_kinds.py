@@ -16,6 +16,10 @@ RULES = [
     # pd_mask_components, both kernels of pd_mask_filter
     (r"mask_(column|row)_kernel", "mask_distance"), (r"comp_(init|merge|flatten|broadcast)_kernel", "mask_components"),
     (r"filter_(init_)?kernel", "mask_filter"),
+    # the per-object measurements (scripts/bench_objects.py): the four kernels of pd_object_index, the three of pd_object_geometry,
+    # pd_object_intensity's one
+    (r"index_(count|scan|rank|gather)_kernel", "object_index"), (r"geom_(init|accum|final)_kernel", "object_geometry"),
+    (r"intensity_kernel<", "object_intensity"),
 ]
 
 
