@@ -11,17 +11,17 @@
 // The fold is repeated by each of a sample's workgroups instead of being a launch of its own: it reads 32 bytes per chunk (768 bytes for a
 // 3 x 256 x 256 image) from L2, against the 96 KiB the workgroup streams.  Traffic per element: cond and uncond read twice, out written once.
 //
-// Determinism (sample_stats.hip's rule): every reduction runs in one fixed order -- lane (a thread's elements by ascending index), wave
-// (xor butterfly 32, 16, ... 1), workgroup (waves 0..3), chunk (runs of consecutive chunks in index order, then the runs in index order).
-// Which element a lane takes depends only on the element's index WITHIN ITS SAMPLE, never on the address: the 16-byte access is used
-// where four elements lie whole inside the sample at an aligned address, element accesses everywhere else, and both hand the same values
-// to the same lane.  So a sample's g does not depend on B, on its row in the batch, on its alignment, on the grid or on the replay.
+// Determinism: the reductions run in the one fixed order of pd_reduce.h, and which element a lane takes depends only on the element's
+// index WITHIN ITS SAMPLE (load_slot / store_slot).  So a sample's g does not depend on B, on its row in the batch, on its alignment, on
+// the grid or on the replay.
+#include "pd_reduce.h"
 #include "pd_step.h"
 
 namespace pd {
 namespace {
 
 constexpr int CHUNK = PD_GUIDANCE_RESCALE_CHUNK, ITERS = CHUNK / (256 * 4), NSUM = 4;
+using Sums = Ops<Sum, Sum, Sum, Sum>;      // sum cond, sum cond^2, sum cfg, sum cfg^2
 constexpr int64_t MAX_BLOCKS = 65536;      // more (sample, chunk) pairs than this are walked in a grid-stride loop
 static_assert(CHUNK % (256 * 4) == 0, "a chunk is a whole number of passes of 256 threads x 4 elements");
 
@@ -31,26 +31,16 @@ struct Launch {
   double* part;              // [B][chunks][NSUM]
 };
 
-// where (sample, chunk) pair `item` lies: the row, the offset of the chunk's first element in the tensor, its number of elements
-struct Tile { int64_t b, off; int rem; };
-__device__ __forceinline__ Tile tile_of(const Launch& p, int64_t item) {
-  Tile t;
-  t.b = item / p.chunks;
-  const int64_t j0 = (item - t.b * p.chunks) * CHUNK, left = p.a.per_sample - j0;
-  t.off = t.b * p.a.per_sample + j0;
-  t.rem = left < CHUNK ? (int)left : CHUNK;
-  return t;
-}
-
 __global__ __launch_bounds__(256) void guidance_rescale_partial_kernel(const Launch p) {
 #pragma clang fp contract(off)
   __shared__ double red[4][NSUM];
   const pd_guidance_rescale_args& a = p.a;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   for (int64_t item = blockIdx.x; item < p.items; item += gridDim.x) {
-    const Tile tl = tile_of(p, item);
-    const float* co = a.model_out + tl.off;
-    const float* un = a.uncond_out + tl.off;
+    const ChunkTile tl = chunk_tile(item, p.chunks, a.per_sample, CHUNK);
+    const int64_t off = tl.b * a.per_sample + tl.j0;
+    const float* co = a.model_out + off;
+    const float* un = a.uncond_out + off;
     const float w = a.w_per_sample ? a.w[tl.b] : a.w[0];
     double acc[NSUM] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -70,17 +60,11 @@ __global__ __launch_bounds__(256) void guidance_rescale_partial_kernel(const Lau
         }
       }
     }
+    block_reduce(Sums(), acc, red);
+    if (t == 0) {
 #pragma unroll
-    for (int i = 0; i < NSUM; ++i) {
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) acc[i] += __shfl_xor(acc[i], m);
+      for (int i = 0; i < NSUM; ++i) p.part[item * NSUM + i] = acc[i];
     }
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < NSUM; ++i) red[wave][i] = acc[i];
-    }
-    __syncthreads();
-    if (t < NSUM) p.part[item * NSUM + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
     __syncthreads();      // (red is written again by the next pair of a grid-stride walk)
   }
 }
@@ -91,44 +75,23 @@ __global__ __launch_bounds__(256) void guidance_rescale_apply_kernel(const Launc
   __shared__ float g_s;
   const pd_guidance_rescale_args& a = p.a;
   const int t = threadIdx.x;
-  const int64_t per = (p.chunks + 255) / 256;
-  const int runs = (int)((p.chunks + per - 1) / per);      // <= 256, every one of them non-empty
   for (int64_t item = blockIdx.x; item < p.items; item += gridDim.x) {
-    const Tile tl = tile_of(p, item);
-    // the sample's four sums: thread r folds the run of consecutive chunks [r * per, (r + 1) * per) in index order, thread 0 the runs in order
-    if (t < runs) {
-      const int64_t c0 = t * per, c1 = c0 + per < p.chunks ? c0 + per : p.chunks;
-      const double* in = p.part + tl.b * p.chunks * NSUM;
-      double acc[NSUM];
-#pragma unroll
-      for (int i = 0; i < NSUM; ++i) acc[i] = in[c0 * NSUM + i];
-      for (int64_t c = c0 + 1; c < c1; ++c) {
-#pragma unroll
-        for (int i = 0; i < NSUM; ++i) acc[i] += in[c * NSUM + i];
-      }
-#pragma unroll
-      for (int i = 0; i < NSUM; ++i) red[t][i] = acc[i];
-    }
-    __syncthreads();
+    const ChunkTile tl = chunk_tile(item, p.chunks, a.per_sample, CHUNK);
+    const int64_t off = tl.b * a.per_sample + tl.j0;
+    double s[NSUM];      // the sample's four sums, in thread 0
+    run_fold(Sums(), p.part + tl.b * p.chunks * NSUM, p.chunks, red, s);
     if (t == 0) {
-      double r[NSUM];
-#pragma unroll
-      for (int i = 0; i < NSUM; ++i) r[i] = red[0][i];
-      for (int u = 1; u < runs; ++u) {
-#pragma unroll
-        for (int i = 0; i < NSUM; ++i) r[i] += red[u][i];
-      }
       const double n = (double)a.per_sample, phi = (double)a.rescale;
-      double var_c = (r[1] - r[0] * r[0] / n) / (n - 1.0), var_g = (r[3] - r[2] * r[2] / n) / (n - 1.0);
+      double var_c = (s[1] - s[0] * s[0] / n) / (n - 1.0), var_g = (s[3] - s[2] * s[2] / n) / (n - 1.0);
       var_c = var_c < 0.0 ? 0.0 : var_c;      // (rounding below zero of a constant row; a NaN stays)
       var_g = var_g < 0.0 ? 0.0 : var_g;
       g_s = (float)(phi * (sqrt(var_c) / sqrt(var_g)) + (1.0 - phi));
     }
     __syncthreads();
     const float g = g_s;
-    const float* co = a.model_out + tl.off;
-    const float* un = a.uncond_out + tl.off;
-    float* out = a.out + tl.off;
+    const float* co = a.model_out + off;
+    const float* un = a.uncond_out + off;
+    float* out = a.out + off;
     const float w = a.w_per_sample ? a.w[tl.b] : a.w[0];
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
@@ -138,22 +101,10 @@ __global__ __launch_bounds__(256) void guidance_rescale_apply_kernel(const Launc
       load_slot(un + e0, tl.rem - e0, u);
 #pragma unroll
       for (int k = 0; k < 4; ++k) r[k] = guidance_combine(a.guidance_cfg, o[k], u[k], w) * g;
-      if (cnt == 4 && ((uintptr_t)(out + e0) & 15) == 0) {
-        *(f32x4*)(out + e0) = (f32x4){r[0], r[1], r[2], r[3]};
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { if (k < cnt) out[e0 + k] = r[k]; }
-      }
+      store_slot(out + e0, cnt, r);
     }
     // (no barrier here: thread 0 writes g_s, and the others red, only after the next pair's first barrier / after its second one)
   }
-}
-
-// chunks per sample, or 0 where the sizes are refused
-int64_t chunks_of(int64_t B, int64_t n) {
-  if (B < 1 || n < 2 || n >= (1ll << 62) / B) return 0;
-  const int64_t chunks = (n + CHUNK - 1) / CHUNK;
-  return chunks > ((1ll << 31) - 1) / B ? 0 : chunks;
 }
 
 }  // namespace
@@ -162,7 +113,7 @@ int64_t chunks_of(int64_t B, int64_t n) {
 using namespace pd;
 
 extern "C" size_t pd_guidance_rescale_workspace(int64_t B, int64_t n) {
-  return (size_t)(chunks_of(B, n) * (B > 0 ? B : 0)) * NSUM * sizeof(double);
+  return (size_t)(n >= 2 ? chunks_of(B, n, CHUNK) * B : 0) * NSUM * sizeof(double);
 }
 
 extern "C" int pd_guidance_rescale(const pd_guidance_rescale_args* a, void* stream) {
@@ -186,7 +137,7 @@ extern "C" int pd_guidance_rescale(const pd_guidance_rescale_args* a, void* stre
   Launch p;
   p.a = *a;
   const int64_t B = a->numel / a->per_sample;
-  p.chunks = chunks_of(B, a->per_sample);
+  p.chunks = chunks_of(B, a->per_sample, CHUNK);
   PD_CHECK(p.chunks > 0, PD_ERR_SHAPE, "%s: more than 2^31 - 1 chunks of %d elements: split the batch", who, CHUNK);
   p.items = B * p.chunks;
   p.part = (double*)a->workspace;

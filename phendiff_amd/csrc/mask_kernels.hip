@@ -4,7 +4,7 @@
 //     pd_contrast_mask    mean_s (fp64 sum, rounded once), limit = ratio * mean, map = fminf(acc, limit) / limit, mask = map > 0.5
 //     pd_mask_blend       out[s][c][p] = mask[s][p] ? x[s][c][p] : keep[s][c][p]                                   a selection
 //
-// The house rules of pd_step.h, sample_stats.hip and guidance_rescale.hip: fixed-order reductions and no atomics; a sample's result is a
+// The house rules of pd_step.h and pd_reduce.h: fixed-order reductions and no atomics; a sample's result is a
 // function of that sample alone; contraction off wherever a formula is restated on the CPU (tests/contrast_mask_ref.py); everything is
 // validated before the launch; quads (quad_count, load_quad, store_quad, quad_rows) over the flat tensors of the two elementwise
 // kernels, slots (load_slot: the index WITHIN A SAMPLE decides what a lane takes, never the address) in the reduction.
@@ -14,9 +14,9 @@
 //   partial: the chunk's sum of acc in fp64 -> workspace [B][chunks]
 //   apply:   every workgroup folds ITS sample's partials (all of them, in one order), makes mean and limit, and writes map / mask of its
 //            chunk; the workgroup of a sample's chunk 0 walks the whole sample once more to count its mask (integers) for stats.
-// Reduction order: lane (a thread's elements by ascending index), wave (xor butterfly 32, 16, ... 1), workgroup (waves 0..3), chunk (runs
-// of consecutive chunks in index order, then the runs in index order).  Traffic per pixel: acc read twice (three times with stats: the
-// count reads 4 bytes per pixel from L2 -- 256 KiB per 256 x 256 sample), map and mask written once.
+// Reduction order: pd_reduce.h's.  Traffic per pixel: acc read twice (three times with stats: the count reads 4 bytes per pixel from
+// L2 -- 256 KiB per 256 x 256 sample), map and mask written once.
+#include "pd_reduce.h"
 #include "pd_step.h"
 
 namespace pd {
@@ -77,17 +77,6 @@ struct MaskLaunch {
   double* part;              // [B][chunks]
 };
 
-// where (sample, chunk) pair `item` lies: the row, the chunk's first pixel within the row, its number of pixels
-struct Tile { int64_t b, j0; int rem; };
-__device__ __forceinline__ Tile tile_of(const MaskLaunch& p, int64_t item) {
-  Tile t;
-  t.b = item / p.chunks;
-  t.j0 = (item - t.b * p.chunks) * CHUNK;
-  const int64_t left = p.a.per_pixel - t.j0;
-  t.rem = left < CHUNK ? (int)left : CHUNK;
-  return t;
-}
-
 // the one place where a pixel's map value is formed: the apply pass's chunk and the count of stats see the same bits
 __device__ __forceinline__ float contrast_map(float v, float limit, bool usable) {
 #pragma clang fp contract(off)
@@ -97,9 +86,9 @@ __device__ __forceinline__ float contrast_map(float v, float limit, bool usable)
 __global__ __launch_bounds__(256) void contrast_mask_partial_kernel(const MaskLaunch p) {
 #pragma clang fp contract(off)
   __shared__ double red[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   for (int64_t item = blockIdx.x; item < p.items; item += gridDim.x) {
-    const Tile tl = tile_of(p, item);
+    const ChunkTile tl = chunk_tile(item, p.chunks, p.a.per_pixel, CHUNK);
     const float* in = p.a.acc + tl.b * p.a.per_pixel + tl.j0;
     double acc = 0.0;
 #pragma unroll
@@ -110,39 +99,25 @@ __global__ __launch_bounds__(256) void contrast_mask_partial_kernel(const MaskLa
 #pragma unroll
       for (int k = 0; k < 4; ++k) { if (k < cnt) acc += (double)v[k]; }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    if (t == 0) p.part[item] = ((red[0] + red[1]) + red[2]) + red[3];
+    acc = block_reduce<Sum>(acc, red);
+    if (t == 0) p.part[item] = acc;
     __syncthreads();      // (red is written again by the next pair of a grid-stride walk)
   }
 }
 
 __global__ __launch_bounds__(256) void contrast_mask_apply_kernel(const MaskLaunch p) {
 #pragma clang fp contract(off)
-  __shared__ double red[256];
+  __shared__ double red[256][1];
   __shared__ float mean_s, limit_s;
   __shared__ long long count_s[4];
   const pd_contrast_mask_args& a = p.a;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t per = (p.chunks + 255) / 256;
-  const int runs = (int)((p.chunks + per - 1) / per);      // <= 256, every one of them non-empty
+  const int t = threadIdx.x;
   for (int64_t item = blockIdx.x; item < p.items; item += gridDim.x) {
-    const Tile tl = tile_of(p, item);
-    // the sample's sum: thread r folds the run of consecutive chunks [r * per, (r + 1) * per) in index order, thread 0 the runs in order
-    if (t < runs) {
-      const int64_t c0 = t * per, c1 = c0 + per < p.chunks ? c0 + per : p.chunks;
-      const double* in = p.part + tl.b * p.chunks;
-      double acc = in[c0];
-      for (int64_t c = c0 + 1; c < c1; ++c) acc += in[c];
-      red[t] = acc;
-    }
-    __syncthreads();
+    const ChunkTile tl = chunk_tile(item, p.chunks, a.per_pixel, CHUNK);
+    double sum[1];      // the sample's sum, in thread 0
+    run_fold(Ops<Sum>(), p.part + tl.b * p.chunks, p.chunks, red, sum);
     if (t == 0) {
-      double r = red[0];
-      for (int u = 1; u < runs; ++u) r += red[u];
-      const float mean = (float)(r / (double)a.per_pixel);
+      const float mean = (float)(sum[0] / (double)a.per_pixel);
       mean_s = mean;
       limit_s = a.ratio * mean;
     }
@@ -163,14 +138,7 @@ __global__ __launch_bounds__(256) void contrast_mask_apply_kernel(const MaskLaun
         m[k] = contrast_map(v[k], limit, usable);
         bits |= (m[k] > 0.5f ? 1u : 0u) << (8 * k);
       }
-      if (map) {
-        if (cnt == 4 && ((uintptr_t)(map + e0) & 15) == 0) {
-          *(f32x4*)(map + e0) = (f32x4){m[0], m[1], m[2], m[3]};
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) { if (k < cnt) map[e0 + k] = m[k]; }
-        }
-      }
+      if (map) store_slot(map + e0, cnt, m);
       if (cnt == 4 && ((uintptr_t)(mask + e0) & 3) == 0) {
         *(uint32_t*)(mask + e0) = bits;
       } else {
@@ -187,12 +155,8 @@ __global__ __launch_bounds__(256) void contrast_mask_apply_kernel(const MaskLaun
 #pragma unroll
         for (int k = 0; k < 4; ++k) { if (k < cnt && contrast_map(v[k], limit, usable) > 0.5f) ++count; }
       }
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) count += __shfl_xor(count, m);
-      if (lane == 0) count_s[wave] = count;
-      __syncthreads();
+      const long long total = block_reduce<Sum>(count, count_s);
       if (t == 0) {
-        const long long total = ((count_s[0] + count_s[1]) + count_s[2]) + count_s[3];
         float* st = a.stats + tl.b * 3;
         st[0] = mean;
         st[1] = limit;
@@ -201,13 +165,6 @@ __global__ __launch_bounds__(256) void contrast_mask_apply_kernel(const MaskLaun
     }
     __syncthreads();      // (red, mean_s, limit_s and count_s are written again by the next pair of a grid-stride walk)
   }
-}
-
-// chunks per sample, or 0 where the sizes are refused
-int64_t chunks_of(int64_t B, int64_t n) {
-  if (B < 1 || n < 1 || n >= (1ll << 62) / B) return 0;
-  const int64_t chunks = (n + CHUNK - 1) / CHUNK;
-  return chunks > ((1ll << 31) - 1) / B ? 0 : chunks;
 }
 
 // ---- pd_mask_blend -----------------------------------------------------------------------------------------------------------------------
@@ -279,7 +236,7 @@ extern "C" int pd_class_contrast(const pd_class_contrast_args* a, void* stream) 
 }
 
 extern "C" size_t pd_contrast_mask_workspace(int64_t B, int64_t per_pixel) {
-  return (size_t)(chunks_of(B, per_pixel) * (B > 0 ? B : 0)) * sizeof(double);
+  return (size_t)(chunks_of(B, per_pixel, CHUNK) * B) * sizeof(double);
 }
 
 extern "C" int pd_contrast_mask(const pd_contrast_mask_args* a, void* stream) {
@@ -296,7 +253,7 @@ extern "C" int pd_contrast_mask(const pd_contrast_mask_args* a, void* stream) {
   PD_CHECK(a->per_pixel >= 1, PD_ERR_SHAPE, "%s: per_pixel = %lld (must be >= 1)", who, (long long)a->per_pixel);
   MaskLaunch p;
   p.a = *a;
-  p.chunks = chunks_of(a->B, a->per_pixel);
+  p.chunks = chunks_of(a->B, a->per_pixel, CHUNK);
   PD_CHECK(p.chunks > 0, PD_ERR_SHAPE, "%s: more than 2^31 - 1 chunks of %d pixels: split the batch", who, CHUNK);
   p.items = a->B * p.chunks;
   p.part = (double*)a->workspace;

@@ -18,7 +18,7 @@
 //
 // TERMINATION of the device loops is argued next to each of them; each also carries a hard cap it can never meet while parent[] holds
 // what this file writes there, and sets the sample's status word instead of spinning if it does.
-#include "pd_common.h"
+#include "pd_reduce.h"      // wave_reduce
 
 namespace pd {
 namespace {
@@ -111,8 +111,8 @@ __global__ __launch_bounds__(256) void mask_row_kernel(const DistLaunch p) {
       }
     }
     if (p.stats && p.stats_mode) {      // (uniform) the row's two counts: wave butterfly, then one integer atomicAdd per wave and count
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) { n_in += __shfl_xor(n_in, m); n_out += __shfl_xor(n_out, m); }
+      n_in = wave_reduce<Sum>(n_in);
+      n_out = wave_reduce<Sum>(n_out);
       if (lane == 0) {
         if ((p.stats_mode & PD_MORPH_STATS_IN) && n_in) atomicAdd(p.stats + s * p.stats_stride + PD_MS_PIXELS_IN, n_in);
         if ((p.stats_mode & PD_MORPH_STATS_OUT) && n_out) atomicAdd(p.stats + s * p.stats_stride + PD_MS_PIXELS_OUT, n_out);
@@ -303,8 +303,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const pd_mask_filter_args a
     if (a.stats) {      // (uniform)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) n[k] += __shfl_xor(n[k], m);
+        n[k] = wave_reduce<Sum>(n[k]);
         if (lane == 0) red[k][wave] = n[k];
       }
       __syncthreads();

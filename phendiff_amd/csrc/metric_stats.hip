@@ -15,12 +15,12 @@
 //                       64 x 64 tile of the covariance, contracting over ALL rows (16 at a time, centred in fp64 before they enter LDS),
 //                       which writes its tile and the mirrored one from the same registers (cov is bitwise symmetric).
 //
-// Determinism (the rule sample_stats.hip states): no atomics; every sum runs in one fixed order -- the MFMA's k order, a lane's 16
-// results, the wave's xor butterfly, waves 0..3, tiles / chunks by index.  A subset's tiles read only that subset's rows of the index
+// Determinism: no atomics; every sum runs in one fixed order -- the MFMA's k order, a lane's 16 results, pd_reduce.h's wave and
+// workgroup reduction, tiles / chunks by index.  A subset's tiles read only that subset's rows of the index
 // tables, so its result does not depend on S or on the other subsets.  Rows at or past m (resp. N) of a ragged tile are not read (zeros are
 // staged) and what they would contribute is SELECTED away, never multiplied by zero.
 #include <math.h>
-#include "pd_common.h"
+#include "pd_reduce.h"
 
 namespace pd {
 namespace {
@@ -32,12 +32,6 @@ constexpr int TILE = PD_METRIC_STATS_TILE;      // 64 x 64 results per workgroup
 constexpr int KC = 32, LDP = KC + 4;            // KID: fp32 columns staged per step; LDS row pitch in floats (144 bytes: 16-byte aligned rows)
 constexpr int RK = 16, LDK = TILE + 16;         // moments: rows contracted per step; LDS row pitch in doubles
 constexpr int MEAN_ROWS = PD_FEATURE_MOMENTS_CHUNK;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- pd_kid_mmd
 struct KidLaunch {
@@ -139,10 +133,8 @@ __global__ __launch_bounds__(256) void kid_tile_kernel(const KidLaunch p) {
         sum += keep ? pw : 0.0;
       }
   if (kind != 2 && ti != tj) sum *= 2.0;      // the mirrored tile (exact)
-  sum = wave_sum(sum);
-  if (lane == 0) red[wave] = sum;
-  __syncthreads();
-  if (t == 0) p.part[s * p.tiles + tile] = ((red[0] + red[1]) + red[2]) + red[3];
+  sum = block_reduce<Sum>(sum, red);
+  if (t == 0) p.part[s * p.tiles + tile] = sum;
 }
 
 // one workgroup per subset: thread k < 3 folds the partials of matrix k in tile order; thread 0 then forms MMD^2

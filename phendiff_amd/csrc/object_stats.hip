@@ -7,13 +7,13 @@
 //
 // The house rules of mask_morph.hip and sample_stats.hip hold.  Integers are exact: the only atomics are INTEGER ones (64-bit add /
 // min / max / or on a geometry row, a 32-bit or on a status word), whose result has no order.  Floating-point sums are fp64, added in
-// an order the sizes fix, reduced in a fixed tree: no floating-point atomic.  A sample's result is a function of that sample alone
+// an order the sizes fix, reduced in pd_reduce.h's fixed tree: no floating-point atomic.  A sample's result is a function of that sample alone
 // (every index is formed within the sample; a pixel at a row's end is no neighbour of the next row's first pixel).  Everything is
 // validated before the first launch; no host read, no allocation: capturable.  No loop is unbounded: every trip count below is a
 // function of the sizes, or of a bounding box clamped to the image.
 #include <limits.h>
 
-#include "pd_common.h"
+#include "pd_reduce.h"
 
 namespace pd {
 namespace {
@@ -212,13 +212,14 @@ __global__ __launch_bounds__(256) void geom_final_kernel(const pd_object_geometr
 
 // ---- intensity -------------------------------------------------------------------------------------------------------------------------
 // One workgroup per (sample, table row, channel).  Thread t adds the selected pixels at box positions t, t + 256, ... in that order;
-// the 256 partial results are reduced by a butterfly inside each wave (a + b is commutative, so every lane holds the same bits) and the
-// four waves in order: the tree depends on the box alone.
+// the 256 partial results go through pd_reduce.h's workgroup reduction: the tree depends on the box alone.  Minimum and maximum are
+// the compare-and-select forms, which never take a NaN: the flag says whether one was seen.
 template <typename T>
 __global__ __launch_bounds__(256) void intensity_kernel(const pd_object_intensity_args a) {
+  using Vals = Ops<Sum, Sum, SelectMin, SelectMax>;      // sum, sum of squares, min, max
   __shared__ double red[4][4];
-  __shared__ int flag[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, H = a.H, W = a.W, K = a.max_objects, Cn = a.C;
+  __shared__ int flag[4][1];
+  const int t = threadIdx.x, H = a.H, W = a.W, K = a.max_objects, Cn = a.C;
   const int64_t item = blockIdx.x;                        // (s * K + k - 1) * C + c
   const int64_t sk = item / Cn;
   const int c = (int)(item - sk * Cn);
@@ -249,27 +250,20 @@ __global__ __launch_bounds__(256) void intensity_kernel(const pd_object_intensit
       seen |= v != v ? 3 : 1;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    sum += __shfl_xor(sum, m);
-    sq += __shfl_xor(sq, m);
-    const double on = __shfl_xor(mn, m), ox = __shfl_xor(mx, m);
-    mn = on < mn ? on : mn;
-    mx = ox > mx ? ox : mx;
-    seen |= __shfl_xor(seen, m);
-  }
-  if (lane == 0) { red[0][wave] = sum; red[1][wave] = sq; red[2][wave] = mn; red[3][wave] = mx; flag[wave] = seen; }
+  double v[4] = {sum, sq, mn, mx};
+  int all[1] = {seen};
+  block_put(Vals(), v, red);
+  block_put(Ops<Or>(), all, flag);
   __syncthreads();
   if (t == 0) {
-    const int all = flag[0] | flag[1] | flag[2] | flag[3];
-    double lo = red[2][0], hi = red[3][0];
-    for (int w = 1; w < 4; ++w) { lo = red[2][w] < lo ? red[2][w] : lo; hi = red[3][w] > hi ? red[3][w] : hi; }
-    if (all & 2) lo = hi = __builtin_nan("");
-    if (!(all & 1)) lo = hi = 0.0;                        // (a table row that names no pixel of this index)
-    out[PD_OI_SUM] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-    out[PD_OI_SUMSQ] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    out[PD_OI_MIN] = lo;
-    out[PD_OI_MAX] = hi;
+    block_get(Vals(), v, red);
+    block_get(Ops<Or>(), all, flag);
+    if (all[0] & 2) v[2] = v[3] = __builtin_nan("");
+    if (!(all[0] & 1)) v[2] = v[3] = 0.0;                 // (a table row that names no pixel of this index)
+    out[PD_OI_SUM] = v[0];
+    out[PD_OI_SUMSQ] = v[1];
+    out[PD_OI_MIN] = v[2];
+    out[PD_OI_MAX] = v[3];
   }
 }
 

@@ -4,9 +4,10 @@
 //   ddim_x0_eps, ddim_prev, ddim_step_elem      : DDIM(Inverse)Scheduler.step for one element
 //   threshold_limit                             : the dynamic clamp of DDIMScheduler(thresholding=True)
 //   step_validate_common, step_check_aligned16  : what every step entry point refuses before it launches
-//   Slot, load_slot                             : a 16-byte slot addressed by the index WITHIN A SAMPLE (pd_sample_stats, pd_guidance_rescale)
+//   Slot, load_slot, store_slot                 : a 16-byte slot addressed by the index WITHIN A SAMPLE
 // Users: ddim_step_kernel, threshold_step_kernel<RAW>, multistep_step_kernel; guided_step_kernel (ddim_step_elem and quad_count, around
-// a loop of its own); pd_guidance_rescale (guidance_combine, load_slot); pd_sample_stats (load_slot).
+// a loop of its own); pd_guidance_rescale (guidance_combine, load_slot, store_slot); pd_contrast_mask (load_slot, store_slot; the quads in
+// pd_class_contrast and pd_mask_blend); pd_sample_stats (load_slot).  The reductions those three share: pd_reduce.h.
 //
 // FP contraction is OFF in every function here, by a pragma of its own: the pragma is lexical and does not follow a function into its
 // caller.  The reference evaluates these formulas as separate fp32 mul / sub / div torch ops, and epsilon-prediction divides by
@@ -148,7 +149,7 @@ template <int N> static inline int step_check_aligned16(const NamedPtr (&tensors
 // ---- a slot = 16 bytes of elements, addressed by the index within a sample ------------------------------------------------------------------
 // Which element a lane takes depends only on the element's index within its sample, never on the address: the 16-byte load is used where
 // a slot of VEC elements lies whole inside the sample and is 16-byte aligned, element loads everywhere else, and both deliver the same
-// values to the same lane (the determinism rule of sample_stats.hip and guidance_rescale.hip).
+// values to the same lane (the lane level of pd_reduce.h's determinism rule).
 template <typename T> struct Slot;
 template <> struct Slot<float> {
   static constexpr int VEC = 4;
@@ -186,6 +187,17 @@ template <typename T> __device__ __forceinline__ int load_slot(const T* p, int c
 #pragma unroll
   for (int k = 0; k < VEC; ++k) v[k] = k < cnt ? Elem<T>::to_f(p[k]) : 0.f;
   return cnt < 0 ? 0 : (cnt < VEC ? cnt : VEC);
+}
+
+// its counterpart for an fp32 output: the 16-byte store where the slot's four elements are all valid and p is 16-byte aligned, element
+// stores of the first cnt elsewhere
+__device__ __forceinline__ void store_slot(float* p, int cnt, const float (&v)[4]) {
+  if (cnt == 4 && ((uintptr_t)p & 15) == 0) {
+    *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { if (k < cnt) p[k] = v[k]; }
+  }
 }
 
 }  // namespace pd

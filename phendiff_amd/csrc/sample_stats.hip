@@ -6,12 +6,11 @@
 // sample's sum, hence its mean) -> pass B (per-chunk sums of d^2 d^3 d^4 with d = x - mean, the error sums, the histogram) -> fold B.
 // A sample is tiled into chunks of PD_SAMPLE_STATS_CHUNK elements, one workgroup of 256 threads per (sample, chunk).
 //
-// Determinism (the rule attn_hd_bwd.hip states): every floating-point reduction runs in one fixed order -- lane (a thread's elements by
-// ascending index), wave (xor butterfly 32, 16, ... 1), workgroup (waves 0..3), chunk (runs of consecutive chunks in index order, then the
-// runs in index order).  Which element a lane takes depends only on the element's index WITHIN ITS SAMPLE, never on the address: the 16-byte
-// load is used where a slot of VEC elements lies whole inside the sample and is 16-byte aligned, element loads everywhere else, and both
-// deliver the same values to the same lane.  So a sample's results do not depend on B, on its row in the batch or on its alignment.  The
-// histogram uses integer atomics only (LDS, then one global add per non-empty bin and workgroup): order-independent.  No float atomics.
+// Determinism: every floating-point reduction runs in the one fixed order of pd_reduce.h.  Which element a lane takes depends only on the
+// element's index WITHIN ITS SAMPLE, never on the address (load_slot), so a sample's results do not depend on B, on its row in the batch
+// or on its alignment.  The histogram uses integer atomics only (LDS, then one global add per non-empty bin and workgroup):
+// order-independent.  No float atomics.
+#include "pd_reduce.h"
 #include "pd_step.h"      // Slot, load_slot
 
 namespace pd {
@@ -19,41 +18,17 @@ namespace {
 
 constexpr int CHUNK = PD_SAMPLE_STATS_CHUNK, MAX_BINS = PD_SAMPLE_STATS_MAX_BINS, F = PD_SAMPLE_STATS_FIELDS;
 
-// ---- the two sets of per-chunk partials and how each member combines
-enum { OP_ADD, OP_MIN, OP_MAX };
+// ---- the two sets of per-chunk partials and how each member combines (fmin / fmax: a NaN operand loses)
 template <int PASS> struct Part;
-template <> struct Part<0> {      // sum, min, max, non-finite count
-  static constexpr int N = 4;
-  static __device__ __forceinline__ constexpr int op(int i) { return i == 1 ? OP_MIN : i == 2 ? OP_MAX : OP_ADD; }
-};
-template <> struct Part<1> {      // sum d^2, sum d^3, sum d^4, sum |e|, sum e^2, max |e|
-  static constexpr int N = 6;
-  static __device__ __forceinline__ constexpr int op(int i) { return i == 5 ? OP_MAX : OP_ADD; }
-};
-__device__ __forceinline__ double identity(int op) { return op == OP_ADD ? 0.0 : op == OP_MIN ? (double)INFINITY : -(double)INFINITY; }
-__device__ __forceinline__ double combine(int op, double a, double b) { return op == OP_ADD ? a + b : op == OP_MIN ? fmin(a, b) : fmax(a, b); }
+template <> struct Part<0> : Ops<Sum, Fmin, Fmax, Sum> {};                // sum, min, max, non-finite count
+template <> struct Part<1> : Ops<Sum, Sum, Sum, Sum, Sum, Fmax> {};       // sum d^2, sum d^3, sum d^4, sum |e|, sum e^2, max |e|
 
-// lane -> wave -> workgroup, fixed order; thread 0 writes the N results to out
-template <int PASS> __device__ __forceinline__ void block_reduce(double (&acc)[Part<PASS>::N], double (*red)[Part<PASS>::N], double* out) {
-  constexpr int N = Part<PASS>::N;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc[i] = combine(Part<PASS>::op(i), acc[i], __shfl_xor(acc[i], m));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) red[wave][i] = acc[i];
-  }
-  __syncthreads();
+// lane -> wave -> workgroup; thread 0 writes the N results to out
+template <int PASS> __device__ __forceinline__ void block_reduce_to(double (&acc)[Part<PASS>::N], double (*red)[Part<PASS>::N], double* out) {
+  block_reduce(Part<PASS>(), acc, red);
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      double r = red[0][i];
-      for (int w = 1; w < 4; ++w) r = combine(Part<PASS>::op(i), r, red[w][i]);
-      out[i] = r;
-    }
+    for (int i = 0; i < Part<PASS>::N; ++i) out[i] = acc[i];
   }
 }
 
@@ -70,9 +45,10 @@ __global__ __launch_bounds__(256) void zero_u32_kernel(uint32_t* p, int64_t coun
 template <typename T> __global__ __launch_bounds__(256) void pass_a_kernel(const Launch p) {
   constexpr int VEC = Slot<T>::VEC, ITERS = CHUNK / (256 * VEC);
   __shared__ double red[4][Part<0>::N];
-  const int64_t blk = blockIdx.x, b = blk / p.chunks, c = blk - b * p.chunks, j0 = c * CHUNK;
-  const int64_t left = p.a.n - j0;
-  const int rem = left < CHUNK ? (int)left : CHUNK;
+  const int64_t blk = blockIdx.x;
+  const ChunkTile tl = chunk_tile(blk, p.chunks, p.a.n, CHUNK);
+  const int64_t b = tl.b, j0 = tl.j0;
+  const int rem = tl.rem;
   const T* x = (const T*)p.a.x + b * p.a.n + j0;
   double acc[4] = {0.0, (double)INFINITY, -(double)INFINITY, 0.0};
   uint32_t bad = 0;
@@ -93,38 +69,17 @@ template <typename T> __global__ __launch_bounds__(256) void pass_a_kernel(const
     }
   }
   acc[3] = (double)bad;
-  block_reduce<0>(acc, red, p.part[0] + blk * Part<0>::N);
+  block_reduce_to<0>(acc, red, p.part[0] + blk * Part<0>::N);
 }
 
-// one workgroup per sample: thread t folds the run of consecutive chunks [t * per, (t + 1) * per) in index order, thread 0 the runs in order
+// one workgroup per sample folds its chunks' partials
 template <int PASS> __global__ __launch_bounds__(256) void fold_kernel(const Launch p) {
   constexpr int N = Part<PASS>::N;
   __shared__ double red[256][N];
-  const int64_t b = blockIdx.x, per = (p.chunks + 255) / 256;
-  const int t = threadIdx.x;
-  int64_t c0 = t * per, c1 = c0 + per;
-  if (c0 > p.chunks) c0 = p.chunks;
-  if (c1 > p.chunks) c1 = p.chunks;
-  const double* in = p.part[PASS] + b * p.chunks * N;
-  double acc[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] = identity(Part<PASS>::op(i));
-  for (int64_t c = c0; c < c1; ++c) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) acc[i] = c == c0 ? in[c * N + i] : combine(Part<PASS>::op(i), acc[i], in[c * N + i]);
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) red[t][i] = acc[i];
-  __syncthreads();
-  if (t != 0) return;
-  const int runs = (int)((p.chunks + per - 1) / per);      // <= 256, every one of them non-empty
+  const int64_t b = blockIdx.x;
   double r[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) r[i] = red[0][i];
-  for (int u = 1; u < runs; ++u) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = combine(Part<PASS>::op(i), r[i], red[u][i]);
-  }
+  run_fold(Part<PASS>(), p.part[PASS] + b * p.chunks * N, p.chunks, red, r);
+  if (threadIdx.x != 0) return;
   double* st = p.a.stats + b * F;
   if (PASS == 0) {
     st[PD_SS_SUM] = r[0]; st[PD_SS_MIN] = r[1]; st[PD_SS_MAX] = r[2]; st[PD_SS_NONFINITE] = r[3];
@@ -147,9 +102,10 @@ template <typename T> __global__ __launch_bounds__(256) void pass_b_kernel(const
     for (int i = t; i < bins; i += 256) lh[i] = 0u;
     __syncthreads();
   }
-  const int64_t blk = blockIdx.x, b = blk / p.chunks, c = blk - b * p.chunks, j0 = c * CHUNK;
-  const int64_t left = p.a.n - j0;
-  const int rem = left < CHUNK ? (int)left : CHUNK;
+  const int64_t blk = blockIdx.x;
+  const ChunkTile tl = chunk_tile(blk, p.chunks, p.a.n, CHUNK);
+  const int64_t b = tl.b, j0 = tl.j0;
+  const int rem = tl.rem;
   const T* x = (const T*)p.a.x + b * p.a.n + j0;
   const T* y = p.a.y ? (const T*)p.a.y + b * p.a.y_sample_stride + j0 : nullptr;
   const double mean = p.a.stats[b * F + PD_SS_SUM] / (double)p.a.n;
@@ -186,7 +142,7 @@ template <typename T> __global__ __launch_bounds__(256) void pass_b_kernel(const
       }
     }
   }
-  block_reduce<1>(acc, red, p.part[1] + blk * Part<1>::N);      // (its barrier also closes the LDS histogram)
+  block_reduce_to<1>(acc, red, p.part[1] + blk * Part<1>::N);      // (its barrier also closes the LDS histogram)
   if (bins > 0) {
     uint32_t* out = p.a.hist + b * bins;
     for (int i = t; i < bins; i += 256) {
@@ -194,13 +150,6 @@ template <typename T> __global__ __launch_bounds__(256) void pass_b_kernel(const
       if (h) atomicAdd(out + i, h);
     }
   }
-}
-
-// chunks per sample, or 0 where the sizes are refused
-int64_t chunks_of(int64_t B, int64_t n) {
-  if (B <= 0 || n <= 0 || B >= (1ll << 31) || n >= (1ll << 62) / B) return 0;
-  const int64_t chunks = (n + CHUNK - 1) / CHUNK;
-  return chunks > ((1ll << 31) - 1) / B ? 0 : chunks;
 }
 
 template <typename T> int launch_all(const Launch& p, hipStream_t st) {
@@ -229,7 +178,7 @@ template <typename T> int launch_all(const Launch& p, hipStream_t st) {
 extern "C" size_t pd_sample_stats_workspace(int64_t B, int64_t n, int bins) {
   using namespace pd;
   if (bins < 0 || bins > MAX_BINS) return 0;
-  return (size_t)(B > 0 && n > 0 ? chunks_of(B, n) * B : 0) * (Part<0>::N + Part<1>::N) * sizeof(double);
+  return (size_t)(B > 0 && n > 0 ? chunks_of(B, n, CHUNK) * B : 0) * (Part<0>::N + Part<1>::N) * sizeof(double);
 }
 
 extern "C" int pd_sample_stats(const pd_sample_stats_args* a, void* stream) {
@@ -250,7 +199,7 @@ extern "C" int pd_sample_stats(const pd_sample_stats_args* a, void* stream) {
   PD_CHECK(a->bins == 0 || a->n < (1ll << 32), PD_ERR_SHAPE, "pd_sample_stats: n must stay below 2^32 with a histogram (uint32 counts)");
   Launch p;
   p.a = *a;
-  p.chunks = chunks_of(a->B, a->n);
+  p.chunks = chunks_of(a->B, a->n, CHUNK);
   PD_CHECK(p.chunks > 0, PD_ERR_SHAPE, "pd_sample_stats: grid too large (more than 2^31 - 1 blocks of %d elements): split the batch", CHUNK);
   const size_t need = (size_t)(p.chunks * a->B) * (Part<0>::N + Part<1>::N) * sizeof(double);
   PD_CHECK(a->workspace_bytes >= need, PD_ERR_ARG, "pd_sample_stats: workspace_bytes %zu below the %zu that pd_sample_stats_workspace asks for",

@@ -14,17 +14,17 @@
 // Over-reads: a position outside the plane is never loaded; its LDS slot gets 0.0 by selection, and a map position that would need it
 // lies outside the valid map and is left out of the sums by selection, never multiplied by zero.
 //
-// Determinism (the rule sample_stats.hip states): element loads only, so nothing depends on alignment; which thread takes which position
-// depends on the position within the plane only; sums run lane (ascending position), wave (xor butterfly), workgroup (waves 0..3), then
-// the fold: runs of consecutive tiles in index order, the runs in index order.  No floating-point atomics.
+// Determinism: element loads only, so nothing depends on alignment; which thread takes which position depends on the position within the
+// plane only; the sums over a tile's positions and over a plane's tiles run in the one fixed order of pd_reduce.h.  No floating-point atomics.
 #include <math.h>
 #include <stddef.h>
-#include "pd_common.h"
+#include "pd_reduce.h"
 
 namespace pd {
 namespace {
 
 constexpr int TH = 16, TW = 32, NT = 256, MAXW = PD_SSIM_MAX_WIN, MAXL = PD_SSIM_MAX_LEVELS;
+static_assert(NT == 256, "pd_reduce.h's block_reduce and run_fold are written for workgroups of 256 threads (four waves)");
 static_assert(offsetof(pd_ssim_args, w32) - offsetof(pd_ssim_args, w0) == (MAXW - 1) * sizeof(double), "the taps w0..w32 are one run of doubles");
 
 __device__ __forceinline__ double widen(float v) { return (double)v; }
@@ -118,17 +118,8 @@ template <typename T> __global__ __launch_bounds__(NT) void ssim_pass_kernel(con
       acc[1] += cs;
     }
   }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc[j] += __shfl_xor(acc[j], m);
-  }
-  if ((t & 63) == 0) {
-    red[t >> 6][0] = acc[0];
-    red[t >> 6][1] = acc[1];
-  }
-  __syncthreads();
-  if (t < 2) p.part[blk * 2 + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+  block_reduce(Ops<Sum, Sum>(), acc, red);
+  if (t == 0) { p.part[blk * 2] = acc[0]; p.part[blk * 2 + 1] = acc[1]; }
 }
 
 // level s from level s - 1: one thread per output element, rows and columns past the last whole pair are dropped
@@ -141,29 +132,14 @@ template <typename T> __global__ __launch_bounds__(NT) void ssim_reduce_kernel(c
   dst[i] = ((widen(s[0]) + widen(s[1])) + (widen(s[Ws]) + widen(s[Ws + 1]))) * 0.25;
 }
 
-// one workgroup per (plane, scale): thread t folds the run of consecutive tiles [t * per, (t + 1) * per) in index order, thread 0 the runs in order
+// one workgroup per (plane, scale) folds the plane's tiles
 __global__ __launch_bounds__(NT) void ssim_fold_kernel(const Fold p) {
   __shared__ double red[NT][2];
   const int64_t blk = blockIdx.x, plane = blk / p.levels;
-  const int s = (int)(blk - plane * p.levels), t = threadIdx.x;
-  const int64_t tiles = p.tiles[s], per = (tiles + NT - 1) / NT;
-  int64_t i0 = t * per, i1 = i0 + per;
-  if (i0 > tiles) i0 = tiles;
-  if (i1 > tiles) i1 = tiles;
-  const double* in = p.part[s] + plane * tiles * 2;
-  double a0 = 0.0, a1 = 0.0;
-  for (int64_t i = i0; i < i1; ++i) {
-    a0 = i == i0 ? in[i * 2] : a0 + in[i * 2];
-    a1 = i == i0 ? in[i * 2 + 1] : a1 + in[i * 2 + 1];
-  }
-  red[t][0] = a0;
-  red[t][1] = a1;
-  __syncthreads();
-  if (t >= 2) return;
-  const int runs = (int)((tiles + per - 1) / per);      // <= NT, every one of them non-empty
-  double r = red[0][t];
-  for (int u = 1; u < runs; ++u) r += red[u][t];
-  p.out[blk * 2 + t] = r / p.npos[s];
+  const int s = (int)(blk - plane * p.levels);
+  double r[2];
+  run_fold(Ops<Sum, Sum>(), p.part[s] + plane * p.tiles[s] * 2, p.tiles[s], red, r);
+  if (threadIdx.x == 0) { p.out[blk * 2] = r[0] / p.npos[s]; p.out[blk * 2 + 1] = r[1] / p.npos[s]; }
 }
 
 // where everything lives, from the sizes alone (the query knows neither win nor whether y is shared: the partials are sized for the smallest
